@@ -10,13 +10,17 @@ Inputs are resident in HBM before the timed region.  value = (N*256)^2 pairs / s
 
     python bench.py [--gpus N] [--steps K] [--warmup W]      # N > 1: starts its own N ranks as child processes
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   # or is started as one of them
+    python bench.py --full                                   # + roofline, exact-row step, secondary workloads, CPU baseline
+    python bench.py --dump-outputs DIR                       # + the last timed step's loss and input gradients as DIR/*.npy
 
 Timing protocol (so that a short driver run and a long builder run report the same number):
   1. clock-settling pre-roll: the step is replayed for --preroll-s seconds (default 1.0) whatever --warmup says
      -- the chip needs ~0.5 s of load before it holds its working clock;
   2. W untimed warm-up steps;
-  3. the K-step region (barrier + synchronize on both sides, MAX over ranks) is timed --repeats times
-     (default 5); ms_per_step / value are the MEDIAN region, min / max are in `config`.
+  3. the K timed steps, split into --repeats regions (default 5) of K / repeats steps, each region timed with barrier +
+     synchronize on both sides, MAX over ranks; ms_per_step / value are the MEDIAN region, min / max are in `config`.
+A plain run does only that; everything else the line can carry (the kernel roofline, the exact-row step, the secondary
+workloads, the CPU baseline, the sharded step's phase timeline) is measured with --full.
 Prints ONE JSON line on rank 0 (see DESIGN.md section "Measurement" for every field).
 """
 import argparse
@@ -39,13 +43,19 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=2000)
     ap.add_argument('--warmup', type=int, default=200)
-    ap.add_argument('--repeats', type=int, default=5, help='how many times the --steps region is timed (median reported)')
+    ap.add_argument('--repeats', type=int, default=5, help='how many regions the --steps timed steps are split into (median region reported)')
     ap.add_argument('--preroll-s', type=float, default=1.0, help='clock-settling pre-roll before the warm-up, seconds')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-eval', action='store_true', help='skip the secondary timings (configs[2] retrieval, shipped shape, loss heads at bs 32, '
-                                                            'configs[4] end to end, COCO-1k alignment grid)')
-    ap.add_argument('--no-cpu-b256', action='store_true', help='skip the live B = 256 CPU baseline (~25 s, ~40 GB of host memory); the committed '
-                                                               'one-off measurement is attached instead')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure the kernel roofline, the exact-row step, the secondary workloads, the CPU '
+                         'baseline and (sharded) the phase timeline; a plain run measures the headline step only')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed (loss, d loss / d image sets, d loss / d caption sets) as DIR/<name>.npy, '
+                         'float32; a fixed, seeded sample of the batch rows where the arrays would exceed DUMP_BUDGET bytes together')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-eval', action='store_true', help='with --full: skip the secondary timings (configs[2] retrieval, shipped shape, '
+                                                            'loss heads at bs 32, configs[4] end to end, COCO-1k alignment grid)')
+    ap.add_argument('--no-cpu-b256', action='store_true', help='with --full: skip the live B = 256 CPU baseline (~25 s, ~40 GB of host memory); '
+                                                               'the committed one-off measurement is attached instead')
     ap.add_argument('--stub-step', action='store_true',
                     help='CPU self-test of the multi-rank protocol (tests/test_launch_cpu.py): gloo, a stub step, the same launcher, '
                          'argument parsing, barriers, MAX over ranks and JSON line -- no GPU, no kernels, no performance claim')
@@ -71,7 +81,12 @@ def parse():
                     help="backward row kernel's unit vectors (ops.set_backward_precision): 'fp16' (the library default: partner rows from "
                          "the forward's packed operands, gradients <= 4.3e-4 of their largest entry off the reference on every fixture, "
                          "gate 5e-4), 'fp16-own' (+ the row's own vector: 5.8e-4 on one D = 64 fixture) or 'exact' (raw fp32 rows: 3e-7)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.stub_step:
+        ap.error('--stub-step computes nothing to dump')
+    return args
 
 
 def kernel_roofline(im, s, il, sl, groups=5, iters=100):
@@ -416,6 +431,28 @@ def shipped_shape_step(dev):
             'score_kernel_us': round(k_us, 2), 'score_kernel_frac': round(k_flops / (k_us * 1e-6) / 1e12 / PEAK_TFLOPS, 4)}
 
 
+DUMP_BUDGET = 48 * 2 ** 20        # bytes --dump-outputs writes at most (the headline's gradients alone are 66 MB)
+
+
+def dump_rows(n, keep):
+    """The rows of a leading (batch) axis of length n that --dump-outputs keeps when it samples: fixed seed, ascending."""
+    import numpy as np
+    return np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: tensor} -> dirname/<name>.npy in float32.  When the arrays exceed DUMP_BUDGET together, each keeps
+    the same share of its leading axis (rows dump_rows(n, keep)); 0-d arrays are written whole."""
+    import numpy as np
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        if total > DUMP_BUDGET and a.ndim > 0:
+            a = a[dump_rows(a.shape[0], max(1, a.shape[0] * DUMP_BUDGET // total))]
+        np.save(os.path.join(dirname, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def stub_main(args, world, rank):
     """--stub-step: the multi-rank PROTOCOL on CPU (gloo): what the driver's `torch.distributed.run ... bench.py --gpus N` relies
     on besides the kernels -- rendezvous on 127.0.0.1, one rank per slot, barriers around the timed region, MAX over ranks,
@@ -636,6 +673,8 @@ def main():
             with torch.cuda.graph(graph):
                 static_loss = crit(im, s, il, sl)
                 static_loss.backward(gradient=seed)
+            # replay writes the captured gradient buffers; an eager step() since then points im.grad / s.grad elsewhere
+            static_grads = (im.grad, s.grad)
 
             def run():
                 graph.replay()
@@ -704,24 +743,29 @@ def main():
     # 2. warm-up
     for _ in range(args.warmup):
         run()
-    # 3. the K-step region, `repeats` times
+    # 3. the K timed steps, in `repeats` regions of (nearly) equal length
+    n_regions = max(1, min(args.repeats, args.steps))
+    region_steps = [args.steps // n_regions + (1 if i < args.steps % n_regions else 0) for i in range(n_regions)]
     region_ms = []
     loss = None
-    for _ in range(max(1, args.repeats)):
+    for n in region_steps:
         fence()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(n):
             loss = run()
         fence()
-        region_ms.append(agree_max(time.perf_counter() - t0) / args.steps * 1e3)
+        region_ms.append(agree_max(time.perf_counter() - t0) / n * 1e3)
     ms = statistics.median(region_ms)
     pairs = (B * world) ** 2
     value = pairs / (ms * 1e-3)
+    if args.dump_outputs and rank == 0:
+        grads = static_grads if launch == 'hipgraph' else (im.grad, s.grad)
+        dump_outputs(args.dump_outputs, {'loss': loss, 'im_grad': grads[0], 's_grad': grads[1]})
 
     # The same step with the EXACT backward row step (raw fp32 rows instead of fp16 partner rows), timed the same way (one region of
     # K steps under the launch mode chosen above), so that the precision trade behind the headline is visible in the line
     bwd_exact_ms = None
-    if not sharded and args.bwd_partners != 'exact':
+    if args.full and not sharded and args.bwd_partners != 'exact':
         old_mode = ops.set_backward_precision('exact')
         try:
             run_x = step
@@ -754,15 +798,16 @@ def main():
 
     phases = None
     if sharded:
-        rec = AD.PhaseRecorder()
-        AD.set_phase_recorder(rec)
-        for _ in range(2 if selftest else 10):
-            rec.begin()
-            step()
-            rec.mark('autograd_tail')
-            rec.end()
-        AD.set_phase_recorder(None)
-        phases = rec.summary()
+        if args.full:
+            rec = AD.PhaseRecorder()
+            AD.set_phase_recorder(rec)
+            for _ in range(2 if selftest else 10):
+                rec.begin()
+                step()
+                rec.mark('autograd_tail')
+                rec.end()
+            AD.set_phase_recorder(None)
+            phases = rec.summary()
         # RCCL prints a version banner through C stdio when the communicator comes up; on a pipe it would
         # surface at exit, AFTER the JSON line.  Push it out now so the JSON line is the last line of stdout.
         # Every rank does it, and rank 0 prints only after all of them have (barrier).
@@ -777,7 +822,12 @@ def main():
     # compact problem in the backward), so ops.set_backward_precision applies to it as to the single-GPU node
     bwd_mode = args.bwd_partners
     if rank == 0:
-        roof = kernel_roofline(im.detach(), s.detach(), il, sl) if not selftest else {'bound': 'mfma', 'note': 'not measured: self-test mode'}
+        if selftest:
+            roof = {'bound': 'mfma', 'note': 'not measured: self-test mode'}
+        elif args.full:
+            roof = kernel_roofline(im.detach(), s.detach(), il, sl)
+        else:
+            roof = {'bound': 'mfma', 'peak': PEAK_TFLOPS, 'unit': 'TFLOP/s', 'note': 'score kernel and forward chain: --full'}
         cfg = {'workload': ('CPU STAND-INS (tests/helpers/cpu_standins.py) under gloo at B=%d/rank, D=%d: the multi-rank step loop, not a measurement; ' % (B, D) if standin else '') +
                            ('SHARED-GPU SELF-TEST: %d ranks on ONE GPU (real kernels, gloo exchange) at B=%d/rank: the multi-rank step loop, not a measurement; ' % (world, B) if shared else '') +
                            'configs[1]: alignment-head triplet loss forward+backward, B=256 synthetic '
@@ -786,7 +836,8 @@ def main():
                             'over %s, caption-block sharding' % (B * world, B * world, 'gloo (self-test)' if selftest else 'RCCL')),
                'global_pairs_per_step': pairs, 'loss': float(loss.detach()), 'launch': launch, 'bwd_partners': bwd_mode, 'bwd_exact_ms_per_step': bwd_exact_ms, 'backward_seed': 'preallocated ones',
                'launch_trial_ms': launch_trial, 'hip_env': {'DEBUG_CLR_GRAPH_PACKET_CAPTURE': os.environ.get('DEBUG_CLR_GRAPH_PACKET_CAPTURE')},
-               'timing': {'preroll_s': args.preroll_s, 'preroll_steps': n_pre, 'repeats': len(region_ms), 'statistic': 'median',
+               'timing': {'preroll_s': args.preroll_s, 'preroll_steps': n_pre, 'repeats': len(region_ms), 'region_steps': region_steps,
+                          'statistic': 'median',
                           'ms_per_step_min': round(min(region_ms), 4), 'ms_per_step_max': round(max(region_ms), 4)},
                'step_tflops_algorithmic': round(value * FLOPS_PER_PAIR / 1e12, 2) if not selftest else None}
         if sharded:
@@ -797,7 +848,7 @@ def main():
             cfg['phases_ms'] = phases          # rank 0's device timeline of one step (10-step mean), see PhaseRecorder
         if standin:
             cfg['standin_calls'] = dict(cpu_standins.CALLS)
-        if world == 1 and not args.no_eval and not selftest:
+        if args.full and world == 1 and not args.no_eval and not selftest:
             sys.path.insert(0, os.path.join(ROOT, 'tools'))
             import benchlib
             for key, fn in (('eval_config3', eval_config3), ('shipped_shape', shipped_shape_step), ('loss_heads_bs32', benchlib.loss_heads_bs32),
@@ -824,7 +875,7 @@ def main():
             'ms_per_step': round(ms, 4), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             'dtype': 'f16', 'data': 'cpu-standin' if standin else ('shared-gpu-selftest' if shared else 'synthetic'), 'config': cfg, 'roofline': roof,
         }
-        if world == 1 and not args.no_cpu_baseline and not selftest:
+        if args.full and world == 1 and not args.no_cpu_baseline and not selftest:
             out['cpu_baseline'] = cpu_baseline(live_b256=not args.no_cpu_b256)
         print(json.dumps(out), flush=True)
     if sharded:

@@ -19,7 +19,7 @@ REQUIRED = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step
 def _bench(*extra):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '40', '--warmup', '5', '--repeats', '2',
-                        '--preroll-s', '0.3', '--no-cpu-baseline', '--no-eval'] + list(extra),
+                        '--preroll-s', '0.3', '--full', '--no-cpu-baseline', '--no-eval'] + list(extra),
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -46,6 +46,46 @@ def test_bench_single_gpu_line():
     assert isinstance(x, float) and 0.9 * d['ms_per_step'] < x < 0.6, x
 
 
+def test_bench_plain_run_times_steps_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full): the headline only, exactly --steps timed steps; --dump-outputs holds the last timed step's loss and
+    input gradients (rows bench.dump_rows() of the batch where sampled) -- what one eager step computes on the same inputs."""
+    import numpy as np
+    import torch
+    import bench
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '100', '--warmup', '5', '--preroll-s', '0.3',
+                        '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
+    for k in REQUIRED:
+        assert k in d, k
+    t = d['config']['timing']
+    assert d['steps'] == 100 and d['warmup'] == 5 and t['repeats'] == 5 and t['region_steps'] == [20] * 5
+    assert abs(d['value'] - 65536 / (d['ms_per_step'] * 1e-3)) <= 1e-3 * d['value'] and 0.1 < d['ms_per_step'] < 0.5
+    assert 'cpu_baseline' not in d and 'eval_config3' not in d['config'] and d['config']['bwd_exact_ms_per_step'] is None
+    assert 'kernel_us' not in d['roofline'] and abs(d['roofline']['step_frac'] - d['value'] * bench.FLOPS_PER_PAIR / 1e12 / 2500.0) < 1e-3
+    assert d['config']['library']['current'] is True
+    out = {n: np.load(str(tmp_path / (n + '.npy'))) for n in ('loss', 'im_grad', 's_grad')}
+    assert all(a.dtype == np.float32 for a in out.values()) and sum(a.nbytes for a in out.values()) <= bench.DUMP_BUDGET
+    keep = out['im_grad'].shape[0]
+    assert out['im_grad'].shape == (keep, 34, 768) and out['s_grad'].shape == (keep, 50, 768) and keep >= 128
+    assert float(out['loss'].reshape(-1)[0]) == d['config']['loss']
+    from aladin_amd import synth
+    from aladin_amd.loss import AlignmentContrastiveLoss
+    im_np, s_np, il, sl = synth.alignment_batch(256, 34, 50, 768, seed=1234, ragged=False)
+    dev = torch.device('cuda:0')
+    im = torch.from_numpy(im_np).to(dev).requires_grad_(True)
+    s = torch.from_numpy(s_np).to(dev).requires_grad_(True)
+    loss = AlignmentContrastiveLoss(0.2, 'dot', True, 'MrSw')(im, s, il, sl)
+    loss.backward()
+    np.testing.assert_allclose(d['config']['loss'], float(loss), rtol=1e-6)
+    rows = bench.dump_rows(256, keep)
+    for name, g in (('im_grad', im.grad), ('s_grad', s.grad)):
+        ref = g.cpu().numpy()[rows]
+        assert np.abs(ref).max() > 0
+        np.testing.assert_allclose(out[name], ref, rtol=1e-5, atol=1e-6 * np.abs(ref).max(), err_msg=name)
+
+
 def test_bench_sharded_step_on_one_rank():
     d0 = _bench()
     d = _bench('--force-sharded')
@@ -69,7 +109,7 @@ def test_bench_four_ranks_sharing_this_gpu_run_the_real_sharded_step():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '4', '--shared-gpu', '--steps', '3', '--warmup', '1'],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '4', '--shared-gpu', '--steps', '3', '--warmup', '1', '--full'],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
@@ -92,7 +132,7 @@ def test_bench_four_ranks_sharing_this_gpu_run_the_real_sharded_step():
 
 def _bench_raw(*args, timeout=900):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '20', '--warmup', '5', '--repeats', '1', '--preroll-s', '0.3'] + list(args),
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '20', '--warmup', '5', '--repeats', '1', '--preroll-s', '0.3', '--full'] + list(args),
                        capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     return json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])

@@ -110,7 +110,7 @@ def test_bench_py_eight_ranks_cpu_standin_runs_the_real_sharded_step():
     env = dict(os.environ, OMP_NUM_THREADS='1')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--cpu-standin', '--steps', '2', '--warmup', '1'],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--cpu-standin', '--steps', '2', '--warmup', '1', '--full'],
                          env=env, capture_output=True, text=True, timeout=800)
     assert out.returncode == 0, out.stderr[-2000:]
     res = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
@@ -136,6 +136,35 @@ def test_bench_py_eight_ranks_cpu_standin_runs_the_real_sharded_step():
     s = torch.from_numpy(np.concatenate([p[1] for p in parts]))
     loss, _, _, _ = cpu_standins.single_process_step(im, s, sum((p[2] for p in parts), []), sum((p[3] for p in parts), []))
     np.testing.assert_allclose(cfg['loss'], float(loss), rtol=1e-5)
+
+
+@pytest.mark.timeout(300)
+def test_bench_py_plain_run_times_steps_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and measures nothing besides the headline; --dump-outputs writes the
+    last timed step's loss and input gradients (rank 0), the same from run to run."""
+    env = dict(os.environ, OMP_NUM_THREADS='1')
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ('run%d' % run)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--cpu-standin', '--steps', '3', '--warmup', '1',
+                              '--dump-outputs', str(d)], env=env, capture_output=True, text=True, timeout=280)
+        assert out.returncode == 0, out.stderr[-2000:]
+        res = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
+        cfg = res['config']
+        assert res['steps'] == 3 and sum(cfg['timing']['region_steps']) == 3 and res['ms_per_step'] > 0
+        assert cfg['phases_ms'] is None and 'cpu_baseline' not in res
+        # every step scores once per rank block: 2 exchanges x (1 trial + 2 tuning) steps, 1 warm-up, 3 timed
+        assert cfg['standin_calls']['hinge_raw'] == 2 * 3 + 1 + 3
+        arrays = {n: np.load(str(d / (n + '.npy'))) for n in ('loss', 'im_grad', 's_grad')}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert arrays['im_grad'].shape == (64, 34, 16) and arrays['s_grad'].shape == (64, 50, 16)
+        assert float(arrays['loss'].reshape(-1)[0]) == cfg['loss'] and np.abs(arrays['im_grad']).max() > 0
+        dumps.append(arrays)
+    for n in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][n], dumps[1][n], err_msg=n)
 
 
 def test_no_self_launch_inside_a_rank_or_for_one_gpu():

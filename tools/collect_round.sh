@@ -26,5 +26,5 @@ bash tools/collect_retrieval_stats.sh "$TAG" > "$O/collect_retrieval_stats.log" 
 # the build container from the merged raw files): its roofline.traffic / mfma_busy_frac then come from this collection, not from
 # a summary of older sources (which bench.py would refuse as stale)
 python3 tools/materialise_profiles.py "$TAG" > "$O/materialise_on_box.log" 2>&1
-python3 bench.py > "$O/bench_line_unprofiled.json" 2> "$O/bench.err"
+python3 bench.py --full > "$O/bench_line_unprofiled.json" 2> "$O/bench.err"
 tail -2 "$O/bench_retrieval.txt"; head -c 400 "$O/bench_line_unprofiled.json"; echo

@@ -7,7 +7,7 @@ cd "$R"
 for spec in "$@"; do
   name=${spec%%=*}; lib=${spec#*=}
   D=/tmp/abks_$name; rm -rf "$D"; mkdir -p "$D"
-  ALADIN_LIB=$R/$lib rocprofv3 --kernel-trace --stats --output-format csv -d "$D" -- python3 "$R/bench.py" --steps 200 --warmup 20 --no-cpu-baseline --no-eval --graph --repeats 1 --preroll-s 0.3 > "$D/log.txt" 2>&1
+  ALADIN_LIB=$R/$lib rocprofv3 --kernel-trace --stats --output-format csv -d "$D" -- python3 "$R/bench.py" --steps 200 --warmup 20 --full --no-cpu-baseline --no-eval --graph --repeats 1 --preroll-s 0.3 > "$D/log.txt" 2>&1
   f=$(find "$D" -name '*kernel_stats.csv' | head -1)
   echo "== $name ($lib)"
   python3 - "$f" <<'P'

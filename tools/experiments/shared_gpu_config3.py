@@ -12,7 +12,7 @@ sys.path.insert(0, ROOT)
 env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
 for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
     env.pop(k, None)
-p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--shared-gpu', '--selftest-batch', '256', '--steps', '3', '--warmup', '1'],
+p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--shared-gpu', '--selftest-batch', '256', '--steps', '3', '--warmup', '1', '--full'],
                    capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
 print('rc', p.returncode, p.stderr[-800:] if p.returncode else '')
 d = json.loads([l for l in p.stdout.splitlines() if l.strip().startswith('{')][-1])
