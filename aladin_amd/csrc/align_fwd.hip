@@ -28,54 +28,15 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <tuple>
+#include <type_traits>
+
 #include "../../include/aladin_hip.h"
 #include "gemm_core.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // geometry
 // ------------------------------------------------------------------------------------------------
-// Column-strip multiplier of the score kernel: 2 doubles the captions per wave (256 x 384 tile for
-// 48-word captions: 1.43x less LDS-DMA traffic per flop, half the barriers per MFMA).
-// Tuning knobs read from the environment exist ONLY in the diagnostic build (-DALADIN_DIAG ->
-// libaladin_hip_diag.so, used by tools/): the product library has no getenv and no alternative kernels.
-#ifdef ALADIN_DIAG
-static int diag_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-#else
-static constexpr int diag_env(const char*, int dflt) { return dflt; }
-#endif
-
-static int scores_strip_mult(int tp16, int mrows) {
-  static const int env = diag_env("ALADIN_ALIGN_STRIP", 2);
-  return (env == 2 && mrows <= 64 && tp16 <= 6) ? 2 : 1;       // tp16 in {1,2,3,4,6}: 24 / tp16 captions per 384-row tile
-}
-
-// Largest leftover handled as side rows (ALADIN_ALIGN_SIDE_MAX, default and maximum 8; 1 when the 32x32x16
-// kernels are forced by ALADIN_ALIGN_STRIP).  Measured at B=256, T=50, D=768 (forward incl. packing): R'=34
-// 0.183 vs 0.271 ms with a second region tile, R'=36 0.200 vs 0.273, R'=38 0.215 vs 0.277, R'=40 0.236 vs 0.276.
-// the 48-row region class (R' 41..56); ALADIN_ALIGN_CLASS48=0 in the diagnostic build falls back to two 32-row tiles (A/B runs)
-static int scores_class48() {
-  static const int v = diag_env("ALADIN_ALIGN_CLASS48", 1);
-  return v != 0;
-}
-
-// the 24- and 40-word caption classes (T' 17..24, 33..40: VinVL's 35-token captions); ALADIN_ALIGN_CLASS40=0 in the diagnostic
-// build pads to whole 16-word tiles as before (A/B runs)
-static int scores_class40() {
-  static const int v = diag_env("ALADIN_ALIGN_CLASS40", 1);
-  return v != 0;
-}
-
-static int scores_side_max() {
-  static int v = -1;
-  if (v < 0) {
-    v = diag_env("ALADIN_ALIGN_SIDE_MAX", 8);
-    if (v < 1) v = 1;
-    if (v > 8) v = 8;
-    if (scores_strip_mult(3, 32) != 2) v = 1;
-  }
-  return v;
-}
-
 extern "C" int aladin_align_geometry(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail, int precision,
                                      aladin_align_geom* g) {
   if (precision != ALADIN_PRECISION_FP16 && precision != ALADIN_PRECISION_SPLIT && precision != ALADIN_PRECISION_SPLIT_TABLE) { aladin_set_error("align_geometry: unknown precision %d", precision); return ALADIN_ERR_ARG; }
@@ -89,30 +50,31 @@ extern "C" int aladin_align_geometry(int Bi, int Bc, int R, int T, int D, int x_
   g->Rq = R - 1 - x_tail; g->Tq = T - 1 - y_tail;
   if (g->Rq > 96 || g->Tq > 96) { aladin_set_error("align_geometry: at most 97 regions / 99 tokens supported (got R=%d T=%d)", R, T); return ALADIN_ERR_UNSUPPORTED; }
   // R' = mrows + rem: `mrows` rows per image in the main operand (16-row MFMA tiles; rows past R' repeat region 0), `rem`
-  // leftover regions per image go through the side GEMM instead of opening another tile.
-  //   33..40  : 32 rows + rem side rows (the 16x16x32 kernel's epilogue takes any rem <= 8; the older 32x32x16 kernels only 1)
+  // leftover regions per image go through the side GEMM instead of opening another tile (measured at B=256, T=50, D=768, forward
+  // incl. packing: R'=34 0.183 vs 0.271 ms with a second region tile, R'=36 0.200 vs 0.273, R'=38 0.215 vs 0.277, R'=40 0.236 vs 0.276).
+  //   33..40  : 32 rows + rem side rows (up to 8)
   //   41..56  : 48 rows (three 16-row tiles) + up to 8 side rows -- VinVL's 50 regions, the shape every shipped YAML trains
   //             on, pays for 48 + 2 rows instead of 64 (round 4; captions must tile a 96-column strip: tp16 in {1, 2, 3, 6})
   //   65      : 64 rows + one side row;   everything else: the next multiple of 32, no side rows
   g->tp16 = cdiv(g->Tq, 16);
   if (g->tp16 == 5) g->tp16 = 6;
-  if (g->Rq > 32 && g->Rq <= 32 + scores_side_max()) { g->mrows = 32; g->rem = g->Rq - 32; }
-  else if (g->Rq > 40 && g->Rq <= 48 + scores_side_max() && scores_side_max() == 8 && 6 % g->tp16 == 0 && scores_class48()) { g->mrows = 48; g->rem = g->Rq > 48 ? g->Rq - 48 : 0; }
-  else if (g->Rq > 64 && g->Rq % 32 == 1 && g->Rq < 96) { g->mrows = 32 * (g->Rq / 32); g->rem = 1; }
+  if (g->Rq > 32 && g->Rq <= 40) { g->mrows = 32; g->rem = g->Rq - 32; }
+  else if (g->Rq > 40 && g->Rq <= 56 && 6 % g->tp16 == 0) { g->mrows = 48; g->rem = g->Rq > 48 ? g->Rq - 48 : 0; }
+  else if (g->Rq == 65) { g->mrows = 64; g->rem = 1; }
   else { g->mrows = 32 * cdiv(g->Rq, 32); g->rem = 0; }
   // split precision: every packed row is three K segments of round_up(D, 64) halfs -- [hi | lo | hi] on the max
   // side, [hi | hi | lo] on the sum side -- so the unchanged main loops contract hi.hi + lo.hi + hi.lo
   g->Dp = round_up(D, 64) * (g->split ? 3 : 1);
   g->img_unit = (g->mrows == 32) ? 8 : 4;                     // images per workgroup tile: 256 rows (192 in the 48-row class, 384 at 96)
-  g->cap_unit = (scores_strip_mult(g->tp16, g->mrows) == 2) ? 24 / g->tp16 : 2 * ((g->tp16 & 1) ? 2 : 1);
+  // captions per unit: one 384-row score tile (the 16x16x32 kernels, up to 64 main rows); two 32-column tiles otherwise
+  g->cap_unit = (g->mrows <= 64) ? 24 / g->tp16 : 2 * ((g->tp16 & 1) ? 2 : 1);
   // rows per caption in y: whole 16-word tiles, except the "half" classes -- T' <= 8 packs a caption into half a tile, T' 17..24
   // into 1.5, T' 33..40 (VinVL's 35-token captions: 35 words of 48 would be 27 % padding) into 2.5: two captions share 1 / 3 / 5
   // tiles and the epilogue splits the middle one between them by lane (caption_add).  Region classes of the 16x16x32 kernels (32,
   // 48 or 64 main rows); every precision except ALADIN_PRECISION_SPLIT_TABLE (the arg-max table kernel of the dense backward keeps
   // whole tiles).  Captions per unit: 384 / 640 rows = whole score tiles (384; 320 and 160 columns) and side GEMM tiles (64 / 128).
   g->trows = 16 * g->tp16;
-  if (precision != ALADIN_PRECISION_SPLIT_TABLE && g->mrows <= 64 && scores_strip_mult(g->tp16, g->mrows) == 2 && scores_class40() &&
-      (g->mrows != 48 || 6 % g->tp16 == 0)) {
+  if (precision != ALADIN_PRECISION_SPLIT_TABLE && g->mrows <= 64) {
     if (g->Tq <= 8) { g->trows = 8; g->cap_unit = 48; }
     else if (g->Tq > 16 && g->Tq <= 24) { g->trows = 24; g->cap_unit = 16; }
     else if (g->Tq > 32 && g->Tq <= 40) { g->trows = 40; g->cap_unit = 16; }
@@ -362,8 +324,7 @@ extern "C" int aladin_align_pack(const aladin_set* im, const aladin_set* s, cons
 // ------------------------------------------------------------------------------------------------
 // side GEMM: E[i][col] = <last region of image i, word col>   (fp32, xe_rows x y_rows)
 // ------------------------------------------------------------------------------------------------
-#define SIDE_STAGES 3
-template <int NT, int SWM, int NS = SIDE_STAGES>
+template <int NT, int SWM, int NS>
 __global__ __launch_bounds__(256) void align_side_gemm_kernel(const half_t* __restrict__ xe, const half_t* __restrict__ y,
                                                               float* __restrict__ E, int64_t ldE, int64_t ldk,
                                                               int ktiles, int n_nblk) {
@@ -391,7 +352,7 @@ __global__ __launch_bounds__(256) void align_side_gemm_kernel(const half_t* __re
         E[(row0 + m * 32 + (r & 3) + 8 * (r >> 2)) * ldE + col0 + n * 32] = acc[m][n][r];
 }
 
-// Diagnostic build only (SCHED == 6 / PROBE instantiations): per-workgroup shader-clock and 100 MHz real-time
+// Diagnostic build only (the PROBE instantiation of align_scores16_kernel): per-workgroup shader-clock and 100 MHz real-time
 // deltas around the main loop -> in-kernel clock = d(memtime)/d(memrealtime) * 100 MHz.
 #ifdef ALADIN_DIAG
 __device__ unsigned long long g_clock_probe[4 * 4096];
@@ -412,17 +373,18 @@ ALADIN_DIAG_API int aladin_debug_read_clock_probe(unsigned long long* host_out, 
 #endif  // ALADIN_DIAG
 
 // ------------------------------------------------------------------------------------------------
-// score kernel
+// score kernel, v_mfma_f32_32x32x16_f16 body (the 96-row region class: R' 66..96)
 //   WM   M-tiles (32 rows) per wave;  Q  M-tiles per image;  images per wave = WM / Q  (2 or 1)
 //   TP16 padded words per caption / 16;  a wave's column strip holds CPS = 1 or 2 whole captions
 // ------------------------------------------------------------------------------------------------
-template <int WGM, int WM, int Q, int TP16, bool HAS_E, int SM, int SCHED>
-__global__ __launch_bounds__(WGM * 128) void align_scores_kernel(const half_t* __restrict__ xm, const half_t* __restrict__ y,
+template <int WM, int Q, int TP16, bool HAS_E>
+__global__ __launch_bounds__(512) void align_scores_kernel(const half_t* __restrict__ xm, const half_t* __restrict__ y,
                                                            const float* __restrict__ E, int64_t ldE,
                                                            float* __restrict__ S, int64_t ldS, int Bi, int Bc,
                                                            int64_t ldk, int ktiles, int n_nblk, int n_blocks) {
-  constexpr int NT = ((TP16 & 1) ? TP16 : TP16 / 2) * SM;
-  constexpr int CPS = ((TP16 & 1) ? 2 : 1) * SM;
+  constexpr int WGM = 4;
+  constexpr int NT = (TP16 & 1) ? TP16 : TP16 / 2;
+  constexpr int CPS = (TP16 & 1) ? 2 : 1;
   constexpr int IPW = WM / Q;
   static_assert(IPW == 1 || IPW % 2 == 0, "one image or pairs of images per wave");
   constexpr int NPAIR = IPW == 1 ? 1 : IPW / 2;
@@ -442,23 +404,7 @@ __global__ __launch_bounds__(WGM * 128) void align_scores_kernel(const half_t* _
 
   const half_t* a_rows = xm + (int64_t)mb * Cfg::BM * ldk;
   const half_t* b_rows = y + (int64_t)nb * Cfg::BN * ldk;
-  // SCHED: 0 = refill burst right after the barrier, 1 = refill spread over the four MFMA groups
-#ifdef ALADIN_DIAG
-  if constexpr (SCHED == 6) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-    gemm_mainloop<Cfg, 2, true, 0, true>(a_rows, b_rows, ldk, ktiles, smem, acc);
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-    if (threadIdx.x == 0 && blockIdx.x < 4096) { g_clock_probe[4 * blockIdx.x] = t1 - t0; g_clock_probe[4 * blockIdx.x + 1] = r1 - r0; g_clock_probe[4 * blockIdx.x + 2] = r0; g_clock_probe[4 * blockIdx.x + 3] = r1; }
-  } else
-#endif
-  if constexpr (SCHED == 2) gemm_mainloop<Cfg, 2, true, 0, true>(a_rows, b_rows, ldk, ktiles, smem, acc);
-  else if constexpr (SCHED == 3) gemm_mainloop<Cfg, 2, true, 0, true, true>(a_rows, b_rows, ldk, ktiles, smem, acc);
-  else if constexpr (SCHED == 7) gemm_mainloop<Cfg, 2, true, 1, true>(a_rows, b_rows, ldk, ktiles, smem, acc);
-  else if constexpr (SCHED == 5) gemm_mainloop<Cfg, 2, true, 3, true, true>(a_rows, b_rows, ldk, ktiles, smem, acc);
-  else if constexpr (SCHED == 8) gemm_mainloop<Cfg, 2, true, 1>(a_rows, b_rows, ldk, ktiles, smem, acc);
-  else if constexpr (SCHED == 9) gemm_mainloop<Cfg, 2, true, 2>(a_rows, b_rows, ldk, ktiles, smem, acc);
-  else if constexpr (SCHED == 1) gemm_mainloop<Cfg, 2, true>(a_rows, b_rows, ldk, ktiles, smem, acc);
-  else gemm_mainloop<Cfg, 2, false>(a_rows, b_rows, ldk, ktiles, smem, acc);
+  gemm_mainloop<Cfg, 2, true>(a_rows, b_rows, ldk, ktiles, smem, acc);      // refill spread over the four MFMA groups
 
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int wm = wave / 2, wn = wave % 2;
@@ -513,22 +459,6 @@ __global__ __launch_bounds__(WGM * 128) void align_scores_kernel(const half_t* _
     if (l5 == 0 && (IPW >= 2 || half == 0) && img < Bi && cap + c < Bc) S[(int64_t)img * ldS + cap + c] = t;
   }
   }
-#ifdef ALADIN_DIAG
-  if constexpr (SCHED == 6) {
-    __syncthreads();
-    if (threadIdx.x == 0 && blockIdx.x < 4096) g_clock_probe[4 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();   // overwrite slot 0 with the exit stamp
-  }
-#endif
-}
-
-static int scores_spread() {
-  static const int v = diag_env("ALADIN_ALIGN_SPREAD", 16);
-  return v;
-}
-
-static int scores_wgm() {
-  static const int v = diag_env("ALADIN_ALIGN_WGM", 4) == 2 ? 2 : 4;
-  return v;
 }
 
 // IEEE-754-2019 maximum (v_maximum3_f32 on gfx950): unlike fmaxf / maxNum it needs no canonicalising v_max x, x, x of its
@@ -716,24 +646,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void align_scores16_tall_kernel(con
   scores16_epilogue_tall<HAS_E, TP16, REMC, Q, HALF, CT, WGM, WGN>(acc, mb, nb, E, ldE, rem, S, ldS, Bi, Bc);
 }
 
-template <bool HAS_E, int TP16, int REMC, int Q = 1, bool HALF = false, int CT = 6, int WGM = 2, int WGN = 4>
-static int launch_scores16_tall(const aladin_align_geom* g, const half_t* xm, const half_t* y, const float* E, float* S,
-                                int64_t ldS, hipStream_t stream) {
-  using Cfg = GemmCfg<WGM, WGN, 4, 3, CT>;
-  const int n_mblk = (int)(g->xm_rows / Cfg::BM), n_nblk = (int)(g->y_rows / Cfg::BN);
-  if ((int64_t)n_mblk * Cfg::BM != g->xm_rows || (int64_t)n_nblk * Cfg::BN != g->y_rows) {
-    aladin_set_error("align_scores16: packed rows do not tile");
-    return ALADIN_ERR_ARG;
-  }
-  auto kern = align_scores16_tall_kernel<HAS_E, TP16, REMC, Q, HALF, CT, WGM, WGN>;
-  static unsigned long long lds_reserved = 0;
-  if (int rc = aladin_reserve_lds((const void*)kern, Cfg::LDS_BYTES, &lds_reserved, "align_scores16_tall")) return rc;
-  const int n_blocks = n_mblk * n_nblk;
-  hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, xm, y, E, g->y_rows, S, ldS, g->Bi,
-                     g->Bc, (int64_t)g->Dp, g->Dp / 64, n_nblk, n_blocks, g->rem);
-  return aladin_check_launch("align_scores16_tall_kernel");
-}
-
 // ------------------------------------------------------------------------------------------------
 // The 48-row region class (R' 41..56: three 16-row tiles per image + up to 8 side rows; round 4).  VinVL's 50 regions -- the
 // shape of every shipped YAML -- used to pay for two 32-row tiles (64 rows, 22 % of the MFMA rows padding).  Wave tile
@@ -831,24 +743,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void align_scores16_r48_kernel(cons
   scores16_epilogue_r48<HAS_E, TP16, REMC, WGM, WGN, CT, HALF>(acc, mb, nb, E, ldE, rem, S, ldS, Bi, Bc);
 }
 
-template <bool HAS_E, int TP16, int REMC, int WGM, int WGN, int CT = 6, bool HALF = false>
-static int launch_scores16_r48_cfg(const aladin_align_geom* g, const half_t* xm, const half_t* y, const float* E, float* S,
-                                   int64_t ldS, hipStream_t stream) {
-  using Cfg = GemmCfg<WGM, WGN, 3, 3, CT>;
-  const int n_mblk = (int)(g->xm_rows / Cfg::BM), n_nblk = (int)(g->y_rows / Cfg::BN);
-  if ((int64_t)n_mblk * Cfg::BM != g->xm_rows || (int64_t)n_nblk * Cfg::BN != g->y_rows) {
-    aladin_set_error("align_scores16_r48: packed rows do not tile");
-    return ALADIN_ERR_ARG;
-  }
-  auto kern = align_scores16_r48_kernel<HAS_E, TP16, REMC, WGM, WGN, CT, HALF>;
-  static unsigned long long lds_reserved = 0;
-  if (int rc = aladin_reserve_lds((const void*)kern, Cfg::LDS_BYTES, &lds_reserved, "align_scores16_r48")) return rc;
-  const int n_blocks = n_mblk * n_nblk;
-  hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, xm, y, E, g->y_rows, S, ldS, g->Bi,
-                     g->Bc, (int64_t)g->Dp, g->Dp / 64, n_nblk, n_blocks, g->rem);
-  return aladin_check_launch("align_scores16_r48_kernel");
-}
-
 // ------------------------------------------------------------------------------------------------
 // 48-row region class x 40-word caption class on large grids: 288 x 320 workgroup tile, 144 x 80 wave tile (THREE images x two
 // captions per wave, 45 accumulators).  The 192 x 320 tile above moves 0.0083 operand bytes through LDS per multiply-add and its
@@ -932,54 +826,6 @@ __global__ __launch_bounds__(512) void align_scores16_r48x3_kernel(const half_t*
     if ((lane & 31) == 0 && imgA < Bi && cap + c < Bc) S[(int64_t)imgA * ldS + cap + c] = tA;
     if (lane == 0 && imgC < Bi && cap + c < Bc) S[(int64_t)imgC * ldS + cap + c] = tC;
   }
-}
-
-template <bool HAS_E, int REMC>
-static int launch_scores16_r48x3(const aladin_align_geom* g, const half_t* xm, const half_t* y, const float* E, float* S, int64_t ldS,
-                                 hipStream_t stream) {
-  using Cfg = CfgR48x3;
-  const int n_mblk = (int)((g->xm_rows + Cfg::BM - 1) / Cfg::BM), n_nblk = (int)(g->y_rows / Cfg::BN);
-  if ((int64_t)n_nblk * Cfg::BN != g->y_rows || g->xm_rows % 48 != 0 || g->xm_rows < 8) { aladin_set_error("align_scores16_r48x3: packed rows do not tile"); return ALADIN_ERR_ARG; }
-  auto kern = align_scores16_r48x3_kernel<HAS_E, REMC>;
-  static unsigned long long lds_reserved = 0;
-  if (int rc = aladin_reserve_lds((const void*)kern, Cfg::LDS_BYTES, &lds_reserved, "align_scores16_r48x3")) return rc;
-  const int n_blocks = n_mblk * n_nblk;
-  hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, xm, y, E, g->y_rows, S, ldS, g->Bi,
-                     g->Bc, (int64_t)g->Dp, g->Dp / 64, n_nblk, n_blocks, g->rem, (int)g->xm_rows);
-  return aladin_check_launch("align_scores16_r48x3_kernel");
-}
-
-template <bool HAS_E, int TP16, int CT = 6, bool HALF = (CT == 5)>
-static int launch_scores16_r48(const aladin_align_geom* g, const half_t* xm, const half_t* y, const float* E, float* S, int64_t ldS,
-                               hipStream_t stream) {
-  // small grids (<= 64 tiles of 192 x 384, e.g. the shipped batch size 32): 96 x 192 tiles of two waves, four times the workgroups
-  const bool small = (g->xm_rows / 192) * (g->y_rows / (64 * CT)) <= 64;
-  if constexpr (CT == 5) {
-    // large grids of the 40-word class: the 288 x 320 tile where it wins.  One workgroup per CU either way, so a grid takes
-    // ceil(tiles / 256) rounds; a 288-row tile takes 1.37x the time of a 192-row one for 1.5x the work (measured at B = 256,
-    // D = 768: 29.0 vs 21.2 us), but B = 256 is 8.0 rounds of the small tile against 5.4 -> 6 of the big one (170 vs 174 us):
-    // the big tile is taken when its rounds come out at least 3 % ahead (ALADIN_ALIGN_R48X3=0/1 forces the choice).
-    static const int forced = diag_env("ALADIN_ALIGN_R48X3", -1);
-    const int64_t n_n = g->y_rows / 320, r192 = ((g->xm_rows / 192) * n_n + 255) / 256, r288 = (((g->xm_rows + 287) / 288) * n_n + 255) / 256;
-    const bool x3 = forced >= 0 ? forced != 0 : (!small && 1.37 * (double)r288 < 0.97 * (double)r192);
-    if (x3) {
-      if constexpr (HAS_E) {
-        if (g->rem == 1) return launch_scores16_r48x3<true, 1>(g, xm, y, E, S, ldS, stream);
-        if (g->rem == 2) return launch_scores16_r48x3<true, 2>(g, xm, y, E, S, ldS, stream);
-        return launch_scores16_r48x3<true, 0>(g, xm, y, E, S, ldS, stream);
-      } else {
-        return launch_scores16_r48x3<false, 1>(g, xm, y, E, S, ldS, stream);
-      }
-    }
-  }
-  if constexpr (HAS_E) {
-    if (g->rem == 2) return small ? launch_scores16_r48_cfg<true, TP16, 2, 1, 2, CT, HALF>(g, xm, y, E, S, ldS, stream)
-                                  : launch_scores16_r48_cfg<true, TP16, 2, 2, 4, CT, HALF>(g, xm, y, E, S, ldS, stream);
-    if (g->rem > 2) return small ? launch_scores16_r48_cfg<true, TP16, 0, 1, 2, CT, HALF>(g, xm, y, E, S, ldS, stream)
-                                 : launch_scores16_r48_cfg<true, TP16, 0, 2, 4, CT, HALF>(g, xm, y, E, S, ldS, stream);
-  }
-  return small ? launch_scores16_r48_cfg<HAS_E, TP16, 1, 1, 2, CT, HALF>(g, xm, y, E, S, ldS, stream)
-               : launch_scores16_r48_cfg<HAS_E, TP16, 1, 2, 4, CT, HALF>(g, xm, y, E, S, ldS, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1250,77 +1096,6 @@ __global__ __launch_bounds__(512) void align_argmax16_r48_kernel(const half_t* _
   argmax16_epilogue_r48<HAS_E, TP16>(acc, mb, nb, E, ldE, rem, im_len, x_tail, Rq, s_len, y_tail, Tq, table, tstride, flags, Bi, Bc);
 }
 
-template <int NT> static int launch_side(const aladin_align_geom* g, const half_t* xe, const half_t* y, float* E, hipStream_t stream);
-
-// g: a SPLIT-precision geometry with 32 or 48 rows per image + up to 8 side rows (R' <= 40, 41..56) or 64 rows and no
-// side rows (R' 57..64), captions tiling a 96-column strip;
-// xm / xe / y: its packed operands; E: its side scratch (g->e_bytes); flags: Bi * Bc bytes, zeroed here.
-int aladin_internal_align_argmax(const aladin_align_geom* g, const void* xm, const void* xe, const void* y, float* E,
-                                 const int32_t* im_len, const int32_t* s_len, uint8_t* table, int tstride, uint8_t* flags,
-                                 hipStream_t stream) {
-  using Cfg = GemmCfg<2, 4, 4, 3>;
-  const bool ok_class = g && g->split && 6 % g->tp16 == 0 && g->trows == 16 * g->tp16 &&
-                        ((g->mrows == 32 && g->rem <= 8) || (g->mrows == 48 && g->rem <= 8) || (g->mrows == 64 && g->rem == 0));
-  if (!ok_class) { aladin_set_error("align_argmax: unsupported tile class (mrows=%d rem=%d tp16=%d split=%d)", g ? g->mrows : -1, g ? g->rem : -1, g ? g->tp16 : -1, g ? g->split : -1); return ALADIN_ERR_UNSUPPORTED; }
-  const int BMc = g->mrows == 48 ? 192 : Cfg::BM;
-  const int n_mblk = (int)(g->xm_rows / BMc), n_nblk = (int)(g->y_rows / Cfg::BN);
-  if ((int64_t)n_mblk * BMc != g->xm_rows || (int64_t)n_nblk * Cfg::BN != g->y_rows) { aladin_set_error("align_argmax: packed rows do not tile"); return ALADIN_ERR_UNSUPPORTED; }
-  if (hipMemsetAsync(flags, 0, (size_t)g->Bi * g->Bc, stream) != hipSuccess) { aladin_set_error("align_argmax: memset failed"); return ALADIN_ERR_HIP; }
-  const int n_blocks = n_mblk * n_nblk;
-  if (g->mrows == 48) {
-    using Cfg48 = GemmCfg<2, 4, 3, 3>;
-    int rc = ALADIN_OK;
-    if (g->rem) {
-      switch (g->tp16) {
-        case 1: case 2: rc = launch_side<1>(g, (const half_t*)xe, (const half_t*)y, E, stream); break;
-        default: rc = launch_side<3>(g, (const half_t*)xe, (const half_t*)y, E, stream); break;
-      }
-      if (rc) return rc;
-    }
-#define ARGMAX48_LAUNCH(HE, TP)                                                                                           \
-  do {                                                                                                                    \
-    auto kern = align_argmax16_r48_kernel<HE, TP>;                                                                        \
-    static unsigned long long lds_reserved = 0;                                                                           \
-    if (int rc2 = aladin_reserve_lds((const void*)kern, Cfg48::LDS_BYTES, &lds_reserved, "align_argmax16_r48")) return rc2; \
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(Cfg48::THREADS), Cfg48::LDS_BYTES, stream, (const half_t*)xm, (const half_t*)y, \
-                       (const float*)E, g->y_rows, g->rem, im_len, g->x_tail, g->Rq, s_len, g->y_tail, g->Tq, table, tstride, flags, g->Bi, g->Bc, \
-                       (int64_t)g->Dp, g->Dp / 64, n_nblk, n_blocks);                                                     \
-  } while (0)
-    if (g->rem) { switch (g->tp16) { case 1: ARGMAX48_LAUNCH(true, 1); break; case 2: ARGMAX48_LAUNCH(true, 2); break; case 3: ARGMAX48_LAUNCH(true, 3); break; default: ARGMAX48_LAUNCH(true, 6); break; } }
-    else { switch (g->tp16) { case 1: ARGMAX48_LAUNCH(false, 1); break; case 2: ARGMAX48_LAUNCH(false, 2); break; case 3: ARGMAX48_LAUNCH(false, 3); break; default: ARGMAX48_LAUNCH(false, 6); break; } }
-#undef ARGMAX48_LAUNCH
-    return aladin_check_launch("align_argmax16_r48_kernel");
-  }
-#define ARGMAX_LAUNCH_Q(HE, TP, QQ)                                                                                     \
-  do {                                                                                                                  \
-    auto kern = align_argmax16_tall_kernel<HE, TP, QQ>;                                                                     \
-    static unsigned long long lds_reserved = 0;                                                                         \
-    if (int rc = aladin_reserve_lds((const void*)kern, Cfg::LDS_BYTES, &lds_reserved, "align_argmax16_tall")) return rc; \
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, (const half_t*)xm, (const half_t*)y, \
-                       (const float*)E, g->y_rows, g->rem, im_len, g->x_tail, g->Rq, s_len, g->y_tail, g->Tq, table, tstride, flags, g->Bi, g->Bc,       \
-                       (int64_t)g->Dp, g->Dp / 64, n_nblk, n_blocks);                                                   \
-  } while (0)
-#define ARGMAX_LAUNCH(HE, TP) ARGMAX_LAUNCH_Q(HE, TP, 1)
-  if (g->mrows == 64) {                              // R' 57..64 (or 41..64 without the 48-row class): an image is two row tiles, no side rows
-    switch (g->tp16) { case 1: ARGMAX_LAUNCH_Q(false, 1, 2); break; case 2: ARGMAX_LAUNCH_Q(false, 2, 2); break; case 3: ARGMAX_LAUNCH_Q(false, 3, 2); break; default: ARGMAX_LAUNCH_Q(false, 6, 2); break; }
-  } else if (g->rem) {
-    int rc = ALADIN_OK;
-    switch (g->tp16) {
-      case 1: rc = launch_side<1>(g, (const half_t*)xe, (const half_t*)y, E, stream); break;
-      case 2: rc = launch_side<1>(g, (const half_t*)xe, (const half_t*)y, E, stream); break;
-      case 3: rc = launch_side<3>(g, (const half_t*)xe, (const half_t*)y, E, stream); break;
-      default: rc = launch_side<3>(g, (const half_t*)xe, (const half_t*)y, E, stream); break;
-    }
-    if (rc) return rc;
-    switch (g->tp16) { case 1: ARGMAX_LAUNCH(true, 1); break; case 2: ARGMAX_LAUNCH(true, 2); break; case 3: ARGMAX_LAUNCH(true, 3); break; default: ARGMAX_LAUNCH(true, 6); break; }
-  } else {
-    switch (g->tp16) { case 1: ARGMAX_LAUNCH(false, 1); break; case 2: ARGMAX_LAUNCH(false, 2); break; case 3: ARGMAX_LAUNCH(false, 3); break; default: ARGMAX_LAUNCH(false, 6); break; }
-  }
-#undef ARGMAX_LAUNCH
-#undef ARGMAX_LAUNCH_Q
-  return aladin_check_launch("align_argmax16_tall_kernel");
-}
-
 // WGM x WGN waves of 64 x 192 each: 4 x 2 with a double buffer is the kernel above; 2 x 1 (128 x 192, two waves) with a
 // three-stage ring is the SMALL-GRID variant: when the 256 x 384 tiling leaves most CUs idle (B <= 64: at most 64
 // workgroups) a workgroup's 12 K steps are a chain of exposed memory latencies (24 us at B = 32, the same as B = 256's
@@ -1376,184 +1151,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void align_scores16_kernel(const ha
 #endif
 }
 
-template <bool HAS_E, int TP16, bool PROBE, int Q, int REMC, int WGM, int WGN, int NS, bool HALF = false>
-static int launch_scores16_cfg(const aladin_align_geom* g, const half_t* xm, const half_t* y, const float* E, float* S,
-                               int64_t ldS, hipStream_t stream) {
-  using Cfg = GemmCfg<WGM, WGN, 2, 6>;
-  const int n_mblk = (int)(g->xm_rows / Cfg::BM), n_nblk = (int)(g->y_rows / Cfg::BN);
-  if ((int64_t)n_mblk * Cfg::BM != g->xm_rows || (int64_t)n_nblk * Cfg::BN != g->y_rows) {
-    aladin_set_error("align_scores16: packed rows do not tile");
-    return ALADIN_ERR_ARG;
-  }
-  auto kern = align_scores16_kernel<HAS_E, TP16, PROBE, Q, REMC, WGM, WGN, NS, HALF>;
-  static unsigned long long lds_reserved = 0;
-  if (int rc = aladin_reserve_lds((const void*)kern, NS * Cfg::STAGE_BYTES, &lds_reserved, "align_scores16")) return rc;
-  const int n_blocks = n_mblk * n_nblk;
-  hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(Cfg::THREADS), NS * Cfg::STAGE_BYTES, stream, xm, y, E, g->y_rows, S, ldS, g->Bi,
-                     g->Bc, (int64_t)g->Dp, g->Dp / 64, n_nblk, n_blocks, g->rem);
-  return aladin_check_launch("align_scores16_kernel");
-}
-
-// HALF: the 24- (TP16 = 2) and 40-word (TP16 = 3) caption classes.  24 words: the same kernels, four captions per 96-column strip.
-// 40 words: two captions per 80-column strip -- the tall kernel with five column tiles, as a 1 x 2-wave 128 x 160 tile for small grids.
-template <bool HAS_E, int TP16 = 3, bool PROBE = false, int Q = 1, int REMC = 1, bool HALF = false>
-static int launch_scores16(const aladin_align_geom* g, const half_t* xm, const half_t* y, const float* E, float* S,
-                           int64_t ldS, hipStream_t stream) {
-  if constexpr (HALF && TP16 == 3) {
-    static_assert(!PROBE, "no clock probe instantiation of the 40-word class");
-    if ((g->xm_rows / 256) * (g->y_rows / 320) <= 64) return launch_scores16_tall<HAS_E, 3, REMC, Q, true, 5, 1, 2>(g, xm, y, E, S, ldS, stream);
-    return launch_scores16_tall<HAS_E, 3, REMC, Q, true, 5, 2, 4>(g, xm, y, E, S, ldS, stream);
-  } else {
-  // small grids (<= 64 tiles of 256 x 384, i.e. B <= 64 at the headline shape): the 128 x 192 / three-stage variant
-  if constexpr (!PROBE) {
-#ifdef ALADIN_DIAG
-    // ALADIN_SCORE_VARIANT=1 / 2: force the two-wave 128 x 192 tile with a 2- / 3-stage ring at any size (experiments)
-    static const int variant = diag_env("ALADIN_SCORE_VARIANT", 0);
-    if (variant == 1) return launch_scores16_cfg<HAS_E, TP16, false, Q, REMC, 2, 1, 2, HALF>(g, xm, y, E, S, ldS, stream);
-    if (variant == 2) return launch_scores16_cfg<HAS_E, TP16, false, Q, REMC, 2, 1, 3, HALF>(g, xm, y, E, S, ldS, stream);
-    if (variant == 4) return launch_scores16_cfg<HAS_E, TP16, false, Q, REMC, 4, 2, 2, HALF>(g, xm, y, E, S, ldS, stream);   // 64 x 192 wave tiles
-#endif
-    if ((g->xm_rows / 256) * (g->y_rows / 384) <= 64)
-      return launch_scores16_cfg<HAS_E, TP16, false, Q, REMC, 2, 1, 3, HALF>(g, xm, y, E, S, ldS, stream);
-    // captions that tile a 96-column strip (one or two 32-row region tiles per image): the 128 x 96 wave tile (14 instead of 16
-    // fragment reads per 32-deep step; -2.4 % on the kernel, bit-identical scores)
-    if constexpr (6 % TP16 == 0) return launch_scores16_tall<HAS_E, TP16, REMC, Q, HALF>(g, xm, y, E, S, ldS, stream);
-  }
-  return launch_scores16_cfg<HAS_E, TP16, PROBE, Q, REMC, 4, 2, 2, HALF>(g, xm, y, E, S, ldS, stream);
-  }
-}
-
-template <int WGM, int WM, int Q, int TP16, bool HAS_E, int SM, int SCHED = 1>
-static int launch_scores_w(const aladin_align_geom* g, const half_t* xm, const half_t* y, const float* E, float* S,
-                           int64_t ldS, hipStream_t stream) {
-  constexpr int NT = ((TP16 & 1) ? TP16 : TP16 / 2) * SM;
-  using Cfg = GemmCfg<WGM, 2, WM, NT>;
-  const int n_mblk = (int)(g->xm_rows / Cfg::BM), n_nblk = (int)(g->y_rows / Cfg::BN);
-  if ((int64_t)n_mblk * Cfg::BM != g->xm_rows || (int64_t)n_nblk * Cfg::BN != g->y_rows) {
-    aladin_set_error("align_scores: packed rows (%lld, %lld) do not tile by (%d, %d)", (long long)g->xm_rows,
-                     (long long)g->y_rows, Cfg::BM, Cfg::BN);
-    return ALADIN_ERR_ARG;
-  }
-  auto kern = align_scores_kernel<WGM, WM, Q, TP16, HAS_E, SM, SCHED>;
-  static unsigned long long lds_reserved = 0;
-  if (int rc = aladin_reserve_lds((const void*)kern, Cfg::LDS_BYTES, &lds_reserved, "align_scores")) return rc;
-  const int n_blocks = n_mblk * n_nblk;
-  hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, xm, y, E, g->y_rows, S, ldS, g->Bi,
-                     g->Bc, (int64_t)g->Dp, g->Dp / 64, n_nblk, n_blocks);
-  return aladin_check_launch("align_scores_kernel");
-}
-
-template <int WM, int Q, int TP16, bool HAS_E, bool HALF = false>
-static int launch_scores(const aladin_align_geom* g, const half_t* xm, const half_t* y, const float* E, float* S,
-                         int64_t ldS, hipStream_t stream) {
-  if constexpr (HALF) {                                // geometry only picks the half classes for the 16x16x32 kernels
-    static_assert(Q <= 2 && TP16 <= 3, "8- / 24- / 40-word captions: one or two 32-row region tiles per image");
-    if constexpr (HAS_E && Q == 1)
-      if (g->rem > 1) return launch_scores16<HAS_E, TP16, false, Q, 0, true>(g, xm, y, E, S, ldS, stream);
-    return launch_scores16<HAS_E, TP16, false, Q, 1, true>(g, xm, y, E, S, ldS, stream);
-  }
-  if constexpr (Q <= 2 && TP16 <= 6)
-    if (scores_strip_mult(TP16, g->mrows) == 2) {
-      // ALADIN_ALIGN_SPREAD: 16 (default) = v_mfma_f32_16x16x32_f16 body; 26 = the same + clock probe
-      // (diagnostic); 3 / 6 = the earlier 32x32x16 body and its clock probe, 7 / 9 = its ablations
-      // (headline class only)
-#ifdef ALADIN_DIAG
-      if constexpr (TP16 == 3 && Q == 1) {
-        if (scores_spread() == 26) return launch_scores16<HAS_E, 3, true>(g, xm, y, E, S, ldS, stream);
-        if (scores_spread() == 3) return launch_scores_w<4, WM, Q, TP16, HAS_E, 2, 3>(g, xm, y, E, S, ldS, stream);
-        if (scores_spread() == 6) return launch_scores_w<4, WM, Q, TP16, HAS_E, 2, 6>(g, xm, y, E, S, ldS, stream);
-        // timing-only ablations of the 32x32x16 body quoted in DESIGN.md (results are wrong by construction)
-        if (scores_spread() == 7) return launch_scores_w<4, WM, Q, TP16, HAS_E, 2, 7>(g, xm, y, E, S, ldS, stream);   // no refill
-        if (scores_spread() == 9) return launch_scores_w<4, WM, Q, TP16, HAS_E, 2, 9>(g, xm, y, E, S, ldS, stream);   // no MFMA
-      }
-#endif
-      if constexpr (HAS_E && Q == 1)
-        if (g->rem > 1) return launch_scores16<HAS_E, TP16, false, Q, 0>(g, xm, y, E, S, ldS, stream);   // several side rows
-      return launch_scores16<HAS_E, TP16, false, Q, 1>(g, xm, y, E, S, ldS, stream);
-    }
-#ifdef ALADIN_DIAG
-  if (scores_wgm() != 4) return launch_scores_w<2, WM, Q, TP16, HAS_E, 1>(g, xm, y, E, S, ldS, stream);
-#endif
-  return launch_scores_w<4, WM, Q, TP16, HAS_E, 1>(g, xm, y, E, S, ldS, stream);
-}
-
-template <int NT, int SWM, int NS = SIDE_STAGES>
-static int launch_side_w(const aladin_align_geom* g, const half_t* xe, const half_t* y, float* E, hipStream_t stream) {
-  using Cfg = GemmCfg<2, 2, SWM, NT>;
-  const int n_mblk = (int)(g->xe_rows / Cfg::BM), n_nblk = (int)(g->y_rows / Cfg::BN);
-  if ((int64_t)n_mblk * Cfg::BM != g->xe_rows || (int64_t)n_nblk * Cfg::BN != g->y_rows) { aladin_set_error("align_side_gemm: packed rows do not tile"); return ALADIN_ERR_ARG; }
-  auto kern = align_side_gemm_kernel<NT, SWM, NS>;
-  constexpr int lds_bytes = NS * Cfg::STAGE_BYTES;
-  static unsigned long long lds_reserved = 0;
-  if (int rc = aladin_reserve_lds((const void*)kern, lds_bytes, &lds_reserved, "align_side_gemm")) return rc;
-  hipLaunchKernelGGL(kern, dim3(n_mblk * n_nblk), dim3(Cfg::THREADS), lds_bytes, stream, xe, y, E, g->y_rows,
-                     (int64_t)g->Dp, g->Dp / 64, n_nblk);
-  return aladin_check_launch("align_side_gemm_kernel");
-}
-
-template <int NT>
-static int launch_side(const aladin_align_geom* g, const half_t* xe, const half_t* y, float* E, hipStream_t stream) {
-  static const int forced = diag_env("ALADIN_SIDE_BIG", -1);
-  // 128-row tiles halve the LDS-DMA traffic of this fill-bound kernel; they pay once there are enough rows
-  // for the grid to stay full: from two side rows per image on (measured at B=256: rem=1 0.187 vs 0.191 ms
-  // forward, rem=2 0.209 vs 0.205, rem=6 0.287 vs 0.275).  ALADIN_SIDE_BIG=0/1 forces the choice.
-  const bool big = (forced >= 0 ? forced != 0 : g->rem >= 2) && g->xe_rows % 128 == 0 && g->xe_rows >= 256;
-  // LDS ring: two stages (two workgroups per CU) once the grid fills the chip, three (one workgroup, deeper prefetch) for the
-  // latency-bound small grids.  tools/ab_side_ns.sh at B = 256, D = 768 (3 -> 2 stages): R' = 33 13.1 -> 13.0 us, R' = 35
-  // 31.9 -> 26.1, R' = 39 63.7 -> 49.9, 50 x 47 19.7 -> 18.2, T' = 17 11.5 -> 10.5, T' = 64 24.5 -> 22.3; B = 64: 10.6 -> 11.6.
-  static const int ns_forced = diag_env("ALADIN_SIDE_NS", 0);
-  const int64_t n_blocks = (g->xe_rows / (big ? 128 : 64)) * (g->y_rows / (64 * NT));
-  const bool two = ns_forced ? ns_forced == 2 : n_blocks >= 128;
-  if (big) return two ? launch_side_w<NT, 2, 2>(g, xe, y, E, stream) : launch_side_w<NT, 2, 3>(g, xe, y, E, stream);
-  return two ? launch_side_w<NT, 1, 2>(g, xe, y, E, stream) : launch_side_w<NT, 1, 3>(g, xe, y, E, stream);
-}
-
-template <int TP16>
-static int dispatch_tp(const aladin_align_geom* g, const half_t* xm, const half_t* xe, const half_t* y, float* E,
-                       float* S, int64_t ldS, int flags, hipStream_t stream) {
-  constexpr int NT = (TP16 & 1) ? TP16 : TP16 / 2;
-  if constexpr (TP16 <= 3)
-    if (g->trows == 16 * TP16 - 8) {                   // 8- / 24- / 40-word captions (aladin_align_geometry): mrows 32, 48 or 64
-      constexpr int NTH = TP16 == 3 ? 2 : 1;             // y_rows is a multiple of 640 (128-column side tiles) / 384 (64)
-      if (g->rem && !(flags & ALADIN_SCORES_REUSE_SIDE)) {
-        int rc = launch_side<NTH>(g, xe, y, E, stream);  // 320-column side tiles measured slower (profiles/r04_ab_side_gemm_stages.txt)
-        if (rc) return rc;
-      }
-      if (g->mrows == 48) {
-        if (g->rem) return launch_scores16_r48<true, TP16, TP16 == 3 ? 5 : 6, true>(g, xm, y, E, S, ldS, stream);
-        return launch_scores16_r48<false, TP16, TP16 == 3 ? 5 : 6, true>(g, xm, y, E, S, ldS, stream);
-      }
-      if (g->mrows == 32) {
-        if (g->rem) return launch_scores<2, 1, TP16, true, true>(g, xm, y, E, S, ldS, stream);
-        return launch_scores<2, 1, TP16, false, true>(g, xm, y, E, S, ldS, stream);
-      }
-      if (g->mrows == 64) {
-        if (g->rem) return launch_scores<2, 2, TP16, true, true>(g, xm, y, E, S, ldS, stream);
-        return launch_scores<2, 2, TP16, false, true>(g, xm, y, E, S, ldS, stream);
-      }
-      aladin_set_error("align_scores: %d-word captions with mrows=%d", g->trows, g->mrows);
-      return ALADIN_ERR_UNSUPPORTED;
-    }
-  if (g->rem) {
-    if (!(flags & ALADIN_SCORES_REUSE_SIDE)) {
-      int rc = launch_side<NT>(g, xe, y, E, stream);
-      if (rc) return rc;
-    }
-    if constexpr (6 % TP16 == 0)
-      if (g->mrows == 48) return launch_scores16_r48<true, TP16>(g, xm, y, E, S, ldS, stream);
-    if (g->mrows == 32) return launch_scores<2, 1, TP16, true>(g, xm, y, E, S, ldS, stream);
-    if (g->mrows == 64) return launch_scores<2, 2, TP16, true>(g, xm, y, E, S, ldS, stream);
-  } else {
-    if constexpr (6 % TP16 == 0)
-      if (g->mrows == 48) return launch_scores16_r48<false, TP16>(g, xm, y, E, S, ldS, stream);
-    if (g->mrows == 32) return launch_scores<2, 1, TP16, false>(g, xm, y, E, S, ldS, stream);
-    if (g->mrows == 64) return launch_scores<2, 2, TP16, false>(g, xm, y, E, S, ldS, stream);
-    if (g->mrows == 96) return launch_scores<3, 3, TP16, false>(g, xm, y, E, S, ldS, stream);
-  }
-  aladin_set_error("align_scores: unsupported tiling mrows=%d rem=%d", g->mrows, g->rem);
-  return ALADIN_ERR_UNSUPPORTED;
-}
-
 // split precision: the operands carry 2^14 each, so S comes out times 2^28 -- scale back (exact)
 __global__ __launch_bounds__(256) void scores_unscale_kernel(float* __restrict__ S, int64_t ldS, int Bi, int Bc) {
   const int64_t n = (int64_t)Bi * Bc;
@@ -1561,26 +1158,242 @@ __global__ __launch_bounds__(256) void scores_unscale_kernel(float* __restrict__
     S[(e / Bc) * ldS + (e % Bc)] *= ALADIN_SPLIT_UNSCALE;
 }
 
+// ------------------------------------------------------------------------------------------------
+// kernel selection and launch
+// ------------------------------------------------------------------------------------------------
+// Score kernel bodies.  Scores are bit-identical across the 16x16x32 bodies wherever they overlap: same MFMA shape, K order and
+// epilogue arithmetic.
+enum ScoreBody {
+  BODY_WIDE,      // align_scores16_kernel: 64 x 192 wave tiles
+  BODY_TALL,      // align_scores16_tall_kernel: 128 x 96 wave tiles (128 x 80 for 40-word captions)
+  BODY_R48,       // align_scores16_r48_kernel: the 48-row region class
+  BODY_R48X3,     // align_scores16_r48x3_kernel: the 48-row region class x 40-word captions on large grids
+  BODY_32X32,     // align_scores_kernel: v_mfma_f32_32x32x16_f16, 96 rows per image
+};
+
+struct ScoreCfg {
+  ScoreBody body;
+  int tp16;       // 16-word column tiles per caption (g->tp16)
+  int half;       // 1: the 8- / 24- / 40-word caption classes (trows = 16 tp16 - 8)
+  int q;          // 32-row region tiles per image
+  int side;       // side rows the epilogue folds in: 0 none, 1 or 2 (a compile-time count), 8 (a run-time count up to 8)
+  int small;      // 1: the small-grid variant of the workgroup tile
+  int probe;      // diagnostic build: the clock-probe instantiation of the WIDE body
+};
+
+// The class table of aladin_align_geometry, with the grid-size rules.  One workgroup per CU: a grid of at most 64 big tiles (B <= 64
+// at the headline shape) leaves most CUs idle, its 12 K steps a chain of exposed memory latencies (24 us at B = 32, the same as
+// B = 256's whole wave of tiles); the small-grid variants (a quarter of the waves per workgroup, a deeper ring) halve it.
+static ScoreCfg select_scores(const aladin_align_geom* g) {
+  ScoreCfg c = {};
+  c.tp16 = g->tp16;
+  c.half = g->trows != 16 * g->tp16;
+  c.q = g->mrows / 32;
+  c.side = g->rem <= 1 ? g->rem : (g->rem == 2 && g->mrows == 48) ? 2 : 8;   // VinVL's 50 regions = 48 + 2: a count of its own
+  const bool words40 = c.half && c.tp16 == 3;                                  // two captions per 80-column strip
+  const int64_t M = g->xm_rows, N = g->y_rows;
+  if (g->mrows == 96) { c.body = BODY_32X32; return c; }                      // R' 66..96
+  if (g->mrows == 48) {                                                        // R' 41..56
+    c.body = BODY_R48;
+    c.small = (M / 192) * (N / (words40 ? 320 : 384)) <= 64;
+    if (words40 && !c.small) {
+      // the 288 x 320 tile where it wins: a grid takes ceil(tiles / 256) rounds; a 288-row tile takes 1.37x the time of a 192-row
+      // one for 1.5x the work (measured at B = 256, D = 768: 29.0 vs 21.2 us), but B = 256 is 8.0 rounds of the small tile against
+      // 5.4 -> 6 of the big one (170 vs 174 us): the big tile is taken when its rounds come out at least 3 % ahead
+      const int64_t n_n = N / 320, r192 = ((M / 192) * n_n + 255) / 256, r288 = (((M + 287) / 288) * n_n + 255) / 256;
+      if (1.37 * (double)r288 < 0.97 * (double)r192) c.body = BODY_R48X3;
+    }
+    return c;
+  }
+  // 32 or 64 main rows per image (R' <= 40, 57..65)
+  if (words40) { c.body = BODY_TALL; c.small = (M / 256) * (N / 320) <= 64; return c; }
+  c.small = (M / 256) * (N / 384) <= 64;
+  // large grids of captions that tile a 96-column strip: the 128 x 96 wave tile (14 instead of 16 fragment reads per 32-deep step;
+  // -2.4 % on the kernel, bit-identical scores)
+  c.body = (c.small || 6 % c.tp16 != 0) ? BODY_WIDE : BODY_TALL;
+#ifdef ALADIN_DIAG
+  // ALADIN_CLOCK_PROBE=1 (diagnostic build): the headline class (32 main rows + at most one side row, 48-word captions) runs the
+  // 4 x 2-wave WIDE body with the clock probe (tools/experiments/clock_probe.py)
+  static const bool probe = getenv("ALADIN_CLOCK_PROBE") != nullptr;
+  if (probe && !c.half && c.tp16 == 3 && c.q == 1 && c.side <= 1) { c.body = BODY_WIDE; c.small = 0; c.probe = 1; }
+#endif
+  return c;
+}
+
+struct SideCfg {
+  int nt;         // 32-column tiles per wave (whole captions: y_rows is a multiple of the 64 nt-column workgroup tile)
+  int big;        // 1: 128-row tiles
+  int two;        // 1: a two-stage LDS ring, else three
+};
+
+// 128-row tiles halve the LDS-DMA traffic of this fill-bound kernel; they pay once there are enough rows for the grid to stay
+// full: from two side rows per image on (measured at B=256: rem=1 0.187 vs 0.191 ms forward, rem=2 0.209 vs 0.205, rem=6 0.287
+// vs 0.275).  LDS ring: two stages (two workgroups per CU) once the grid fills the chip, three (one workgroup, deeper prefetch) for
+// the latency-bound small grids (profiles/r04_ab_side_gemm_stages.txt).  320-column tiles for the 40-word class measured slower.
+static SideCfg select_side(const aladin_align_geom* g) {
+  SideCfg c;
+  const bool half = g->trows != 16 * g->tp16;
+  c.nt = half ? (g->tp16 == 3 ? 2 : 1) : (g->tp16 & 1) ? g->tp16 : g->tp16 / 2;
+  c.big = g->rem >= 2 && g->xe_rows % 128 == 0 && g->xe_rows >= 256;
+  c.two = (g->xe_rows / (c.big ? 128 : 64)) * (g->y_rows / (64 * c.nt)) >= 128;
+  return c;
+}
+
+// f(std::integral_constant<int, v>...) for run-time values v, each drawn from its Set: every combination of the sets is compiled,
+// so the callers instantiate kernels only under `if constexpr` rules (the configurations the selection above can return).
+template <int... Vs> struct Set {};
+template <class F> static int with_values(F&& f) { return f(); }
+template <int... Vs, class... Rest, class F>
+static int with_values(F&& f, Set<Vs...>, int v, Rest... rest) {
+  int rc = ALADIN_ERR_UNSUPPORTED;
+  const bool hit = ((v == Vs && ((rc = with_values([&](auto... cs) { return f(std::integral_constant<int, Vs>(), cs...); }, rest...)), true)) || ...);
+  if (!hit) aladin_set_error("align: no kernel for tile parameter %d", v);
+  return rc;
+}
+
+static int no_kernel(const char* what) {
+  aladin_set_error("%s: no kernel for this tile class", what);
+  return ALADIN_ERR_UNSUPPORTED;
+}
+
+// Workgroup tile of a launch: BM x BN over the packed rows; m_rows must be a multiple of m_unit (BM, or the image unit of a kernel
+// whose last row tile may hang over the end).
+struct Tiles { int bm, bn, m_unit, threads, lds; };
+template <class Cfg> static constexpr Tiles tiles_of(int lds = Cfg::LDS_BYTES, int m_unit = Cfg::BM) {
+  return Tiles{Cfg::BM, Cfg::BN, m_unit, Cfg::THREADS, lds};
+}
+
+// The one launch path of this file: tile check, dynamic LDS reserved once per device, launch, launch check.
+// args(n_nblk, n_blocks) returns the kernel's arguments as a tuple.
+template <auto KERN, class Args>
+static int launch_tiles(const char* what, Tiles t, int64_t m_rows, int64_t n_rows, hipStream_t stream, Args args) {
+  const int64_t n_mblk = (m_rows + t.bm - 1) / t.bm, n_nblk = n_rows / t.bn;
+  if (m_rows % t.m_unit != 0 || n_nblk * t.bn != n_rows) {
+    aladin_set_error("%s: packed rows (%lld, %lld) do not tile by (%d, %d)", what, (long long)m_rows, (long long)n_rows, t.bm, t.bn);
+    return ALADIN_ERR_ARG;
+  }
+  static unsigned long long lds_reserved = 0;
+  if (int rc = aladin_reserve_lds((const void*)KERN, t.lds, &lds_reserved, what)) return rc;
+  const int n_blocks = (int)(n_mblk * n_nblk);
+  std::apply([&](auto... a) { hipLaunchKernelGGL(KERN, dim3(n_blocks), dim3(t.threads), t.lds, stream, a...); }, args((int)n_nblk, n_blocks));
+  return aladin_check_launch(what);
+}
+
+static int launch_side(const aladin_align_geom* g, const half_t* xe, const half_t* y, float* E, hipStream_t stream) {
+  const SideCfg c = select_side(g);
+  return with_values([&](auto nt, auto big, auto two) {
+    constexpr int SWM = big ? 2 : 1, NS = two ? 2 : 3;
+    using Cfg = GemmCfg<2, 2, SWM, nt>;
+    return launch_tiles<align_side_gemm_kernel<nt, SWM, NS>>("align_side_gemm_kernel", tiles_of<Cfg>(NS * Cfg::STAGE_BYTES), g->xe_rows,
+                                                            g->y_rows, stream, [&](int n_nblk, int) {
+      return std::make_tuple(xe, y, E, (int64_t)g->y_rows, (int64_t)g->Dp, g->Dp / 64, n_nblk);
+    });
+  }, Set<1, 2, 3>(), c.nt, Set<0, 1>(), c.big, Set<0, 1>(), c.two);
+}
+
+static int launch_scores(const ScoreCfg& c, const aladin_align_geom* g, const half_t* xm, const half_t* y, const float* E, float* S,
+                         int64_t ldS, hipStream_t stream) {
+  const int64_t M = g->xm_rows, N = g->y_rows;
+  auto args = [=](int n_nblk, int n_blocks) {
+    return std::make_tuple(xm, y, E, N, S, ldS, g->Bi, g->Bc, (int64_t)g->Dp, g->Dp / 64, n_nblk, n_blocks, g->rem);
+  };
+  if (c.body == BODY_32X32)
+    return with_values([&](auto tp16) {
+      using Cfg = GemmCfg<4, 2, 3, (tp16 & 1) ? tp16 : tp16 / 2>;
+      return launch_tiles<align_scores_kernel<3, 3, tp16, false>>("align_scores_kernel", tiles_of<Cfg>(), M, N, stream, [&](int n_nblk, int n_blocks) {
+        return std::make_tuple(xm, y, E, N, S, ldS, g->Bi, g->Bc, (int64_t)g->Dp, g->Dp / 64, n_nblk, n_blocks);
+      });
+    }, Set<1, 2, 3, 4, 6>(), c.tp16);
+  if (c.body == BODY_R48X3)
+    return with_values([&](auto side) {
+      return launch_tiles<align_scores16_r48x3_kernel<side != 0, side == 8 ? 0 : side == 0 ? 1 : side>>(
+          "align_scores16_r48x3_kernel", tiles_of<CfgR48x3>(CfgR48x3::LDS_BYTES, 48), M, N, stream,
+          [&](int n_nblk, int n_blocks) { return std::tuple_cat(args(n_nblk, n_blocks), std::make_tuple((int)M)); });
+    }, Set<0, 1, 2, 8>(), c.side);
+#ifdef ALADIN_DIAG
+  if (c.probe)
+    return with_values([&](auto side) {
+      using Cfg = GemmCfg<4, 2, 2, 6>;
+      return launch_tiles<align_scores16_kernel<side != 0, 3, true>>("align_scores16_kernel", tiles_of<Cfg>(), M, N, stream, args);
+    }, Set<0, 1>(), c.side);
+#endif
+  return with_values([&](auto tp16, auto half, auto q, auto side, auto small) -> int {
+    constexpr int TP16 = tp16, Q = q, SIDE = side;
+    constexpr bool HALF = half, SMALL = small, HAS_E = SIDE != 0;
+    constexpr int REMC = SIDE == 8 ? 0 : SIDE == 0 ? 1 : SIDE;     // compile-time side-row count (0: run-time; 1 when unused)
+    constexpr bool cols = HALF ? TP16 <= 3 : true;                  // 8 / 24 / 40 words
+    constexpr bool rows = Q == 1 ? SIDE != 2 : SIDE <= 1;            // WIDE / TALL: 64 main rows take R' 65's one side row only
+    constexpr bool words40 = HALF && TP16 == 3;
+    constexpr int CT = words40 ? 5 : 6;
+    if (c.body == BODY_WIDE) {
+      // small grids: 2 x 1 waves (128 x 192) with a three-stage ring; large grids: 4 x 2 waves with a double buffer (64-word
+      // captions, which do not tile the tall body's 96-column strip)
+      if constexpr (cols && rows && !words40 && (SMALL || (TP16 == 4 && !HALF))) {
+        using Cfg = GemmCfg<SMALL ? 2 : 4, SMALL ? 1 : 2, 2, 6>;
+        constexpr int NS = SMALL ? 3 : 2;
+        return launch_tiles<align_scores16_kernel<HAS_E, TP16, false, Q, REMC, Cfg::WGM, Cfg::WGN, NS, HALF>>(
+            "align_scores16_kernel", tiles_of<Cfg>(NS * Cfg::STAGE_BYTES), M, N, stream, args);
+      }
+    } else if (c.body == BODY_TALL) {
+      // 2 x 4 waves; the 40-word class's small grids: 1 x 2 waves (128 x 160)
+      if constexpr (cols && rows && 6 % TP16 == 0 && (!SMALL || words40)) {
+        using Cfg = GemmCfg<SMALL ? 1 : 2, SMALL ? 2 : 4, 4, 3, CT>;
+        return launch_tiles<align_scores16_tall_kernel<HAS_E, TP16, REMC, Q, HALF, CT, Cfg::WGM, Cfg::WGN>>(
+            "align_scores16_tall_kernel", tiles_of<Cfg>(), M, N, stream, args);
+      }
+    } else if (c.body == BODY_R48) {
+      // 2 x 4 waves (192 x 384, or 192 x 320 for 40-word captions); small grids: 1 x 2 waves
+      if constexpr (cols && Q == 1 && 6 % TP16 == 0) {
+        using Cfg = GemmCfg<SMALL ? 1 : 2, SMALL ? 2 : 4, 3, 3, CT>;
+        return launch_tiles<align_scores16_r48_kernel<HAS_E, TP16, REMC, Cfg::WGM, Cfg::WGN, CT, HALF>>(
+            "align_scores16_r48_kernel", tiles_of<Cfg>(), M, N, stream, args);
+      }
+    }
+    return no_kernel("align_scores");
+  }, Set<1, 2, 3, 4, 6>(), c.tp16, Set<0, 1>(), c.half, Set<1, 2>(), c.q, Set<0, 1, 2, 8>(), c.side, Set<0, 1>(), c.small);
+}
+
+// g: a SPLIT-precision geometry with 32 or 48 rows per image + up to 8 side rows (R' <= 40, 41..56) or 64 rows and no
+// side rows (R' 57..64), captions tiling a 96-column strip;
+// xm / xe / y: its packed operands; E: its side scratch (g->e_bytes); flags: Bi * Bc bytes, zeroed here.
+int aladin_internal_align_argmax(const aladin_align_geom* g, const void* xm, const void* xe, const void* y, float* E,
+                                 const int32_t* im_len, const int32_t* s_len, uint8_t* table, int tstride, uint8_t* flags,
+                                 hipStream_t stream) {
+  const bool ok_class = g && g->split && 6 % g->tp16 == 0 && g->trows == 16 * g->tp16 &&
+                        ((g->mrows == 32 && g->rem <= 8) || (g->mrows == 48 && g->rem <= 8) || (g->mrows == 64 && g->rem == 0));
+  if (!ok_class) { aladin_set_error("align_argmax: unsupported tile class (mrows=%d rem=%d tp16=%d split=%d)", g ? g->mrows : -1, g ? g->rem : -1, g ? g->tp16 : -1, g ? g->split : -1); return ALADIN_ERR_UNSUPPORTED; }
+  if (hipMemsetAsync(flags, 0, (size_t)g->Bi * g->Bc, stream) != hipSuccess) { aladin_set_error("align_argmax: memset failed"); return ALADIN_ERR_HIP; }
+  if (g->rem)
+    if (int rc = launch_side(g, (const half_t*)xe, (const half_t*)y, E, stream)) return rc;
+  auto args = [&](int n_nblk, int n_blocks) {
+    return std::make_tuple((const half_t*)xm, (const half_t*)y, (const float*)E, (int64_t)g->y_rows, g->rem, im_len, g->x_tail, g->Rq, s_len,
+                           g->y_tail, g->Tq, table, tstride, flags, g->Bi, g->Bc, (int64_t)g->Dp, g->Dp / 64, n_nblk, n_blocks);
+  };
+  // 48 rows: align_argmax16_r48_kernel; 32 rows (Q = 1, side rows from E) or 64 (Q = 2, none): align_argmax16_tall_kernel
+  return with_values([&](auto tp16, auto has_e, auto q) -> int {
+    if (g->mrows == 48) {
+      if constexpr (q == 1) return launch_tiles<align_argmax16_r48_kernel<has_e, tp16>>("align_argmax16_r48_kernel", tiles_of<GemmCfg<2, 4, 3, 3>>(),
+                                                                                      g->xm_rows, g->y_rows, stream, args);
+    } else if constexpr (q == 1 || !has_e) {
+      return launch_tiles<align_argmax16_tall_kernel<has_e, tp16, q>>("align_argmax16_tall_kernel", tiles_of<GemmCfg<2, 4, 4, 3>>(),
+                                                                       g->xm_rows, g->y_rows, stream, args);
+    }
+    return no_kernel("align_argmax");
+  }, Set<1, 2, 3, 6>(), g->tp16, Set<0, 1>(), g->rem != 0, Set<1, 2>(), g->mrows == 64 ? 2 : 1);
+}
+
 int aladin_internal_scores(const void* xm, const void* xe, const void* y, const aladin_align_geom* g, void* e_scratch, float* S,
                            int64_t ldS, int flags, void* stream) {
   if (!xm || !y || !g || !S || (g->rem && (!xe || !e_scratch))) { aladin_set_error("align_scores: null argument"); return ALADIN_ERR_ARG; }
   if (ldS < g->Bc) { aladin_set_error("align_scores: ldS %lld < Bc %d", (long long)ldS, g->Bc); return ALADIN_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  const half_t* a = (const half_t*)xm; const half_t* b = (const half_t*)xe; const half_t* c = (const half_t*)y;
-  float* E = (float*)e_scratch;
   if (g->trows != 16 * g->tp16 && !(g->trows == 16 * g->tp16 - 8 && g->tp16 <= 3)) { aladin_set_error("align_scores: bad geometry (trows=%d tp16=%d)", g->trows, g->tp16); return ALADIN_ERR_ARG; }
-  int rc;
-  switch (g->tp16) {
-    case 1: rc = dispatch_tp<1>(g, a, b, c, E, S, ldS, flags, st); break;
-    case 2: rc = dispatch_tp<2>(g, a, b, c, E, S, ldS, flags, st); break;
-    case 3: rc = dispatch_tp<3>(g, a, b, c, E, S, ldS, flags, st); break;
-    case 4: rc = dispatch_tp<4>(g, a, b, c, E, S, ldS, flags, st); break;
-    case 6: rc = dispatch_tp<6>(g, a, b, c, E, S, ldS, flags, st); break;
-    default:
-      aladin_set_error("align_scores: unsupported padded caption length %d", 16 * g->tp16);
-      return ALADIN_ERR_UNSUPPORTED;
-  }
-  if (rc || !g->split) return rc;
+  if (g->tp16 < 1 || g->tp16 > 6 || g->tp16 == 5) { aladin_set_error("align_scores: unsupported padded caption length %d", 16 * g->tp16); return ALADIN_ERR_UNSUPPORTED; }
+  hipStream_t st = (hipStream_t)stream;
+  float* E = (float*)e_scratch;
+  if (g->rem && !(flags & ALADIN_SCORES_REUSE_SIDE))
+    if (int rc = launch_side(g, (const half_t*)xe, (const half_t*)y, E, st)) return rc;
+  if (int rc = launch_scores(select_scores(g), g, (const half_t*)xm, (const half_t*)y, E, S, ldS, st)) return rc;
+  if (!g->split) return ALADIN_OK;
   const int64_t n = (int64_t)g->Bi * g->Bc;
   int grid = (int)((n + 255) / 256); if (grid > 2048) grid = 2048;
   hipLaunchKernelGGL(scores_unscale_kernel, dim3(grid), dim3(256), 0, st, S, ldS, g->Bi, g->Bc);

@@ -106,22 +106,6 @@ __device__ __forceinline__ half8 lds_frag(const char* stage, int row, int kk, in
   return *reinterpret_cast<const half8*>(stage + row * 128 + phys * 16);
 }
 
-// MFMA step on one 32x32 accumulator.  SHAPE16 (timing-only ablation): two v_mfma_f32_16x16x32_f16 on
-// two 4-register slices of the same accumulator -- equal flops, meaningless values -- to measure the
-// clock / time the chip holds with that instruction shape before committing to its fragment layout.
-template <bool SHAPE16>
-__device__ __forceinline__ void mfma_step(const half8& a, const half8& b, f32x16& c) {
-  if constexpr (!SHAPE16) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  } else {
-    f32x4 lo = {c[0], c[1], c[2], c[3]}, hi = {c[4], c[5], c[6], c[7]};
-    lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, lo, 0, 0, 0);
-    hi = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, hi, 0, 0, 0);
-    c[0] = lo[0]; c[1] = lo[1]; c[2] = lo[2]; c[3] = lo[3];
-    c[4] = hi[0]; c[5] = hi[1]; c[6] = hi[2]; c[7] = hi[3];
-  }
-}
-
 // s_waitcnt vmcnt(n) with a run-time n <= 32 (the instruction needs an immediate)
 __device__ __forceinline__ void wait_vmcnt(int n) {
   switch (n) {
@@ -143,7 +127,7 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
 // wave's older LDS-DMA groups must have landed), ONE raw s_barrier (publishes step kt to every
 // wave and proves every wave is done reading buffer (kt-1) % NS), then the refill of that buffer
 // is issued before the MFMAs of step kt.  acc must be initialised by the caller.
-template <class Cfg, int NS = 2, bool SPREAD = false, int ABLATE = 0, bool PIPE = false, bool PRIO = false>
+template <class Cfg, int NS = 2, bool SPREAD = false>
 __device__ __forceinline__ void gemm_mainloop(const half_t* __restrict__ a_rows, const half_t* __restrict__ b_rows,
                                               int64_t ldk, int ktiles, char* smem, f32x16 (&acc)[Cfg::WM][Cfg::WN],
                                               const half_t* __restrict__ a_rows2 = nullptr, int a_split = Cfg::BM,
@@ -166,75 +150,29 @@ __device__ __forceinline__ void gemm_mainloop(const half_t* __restrict__ a_rows,
     wait_vmcnt(n_issued * (ahead < NS - 2 ? ahead : NS - 2));
     __builtin_amdgcn_s_barrier();
     const char* cur = smem + (kt % NS) * Cfg::STAGE_BYTES;
-    const bool refill = (ABLATE != 1) && (kt + NS - 1 < ktiles);      // ABLATE 1: timing-only build without refills
+    const bool refill = kt + NS - 1 < ktiles;
     char* nxt = smem + ((kt + NS - 1) % NS) * Cfg::STAGE_BYTES;
     if (!SPREAD && refill) gemm_stage<Cfg>(a_rows, a_rows2, a_split, b_rows, ldk, kt + NS - 1, nxt, wave, lane_off, skip);
-    if constexpr (PIPE && Cfg::WM == 2 && Cfg::WN >= 4) {
-      // Software-pipelined 16-deep steps.  Step kk runs the four MFMAs on (a0,a1) x (b0,b1) first;
-      // b0,b1 are then dead and are refilled with step kk+1's values together with a second pair
-      // of A registers, under the remaining 2*(WN-2) MFMAs.  Step kk+1 therefore starts with its
-      // first four MFMAs ready and only has to fetch b2.. -- one exposed LDS latency per K step
-      // (at kk = 0) instead of four.  Costs 8 extra VGPRs.
-      half8 a_cur[2], a_nxt[2], b01[2], brest[Cfg::WN - 2];
-      a_cur[0] = lds_frag(cur, a_row0, 0, lane);
-      a_cur[1] = lds_frag(cur, a_row0 + 32, 0, lane);
-      b01[0] = lds_frag(cur, b_row0, 0, lane);
-      b01[1] = lds_frag(cur, b_row0 + 32, 0, lane);
 #pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
+    for (int kk = 0; kk < 4; ++kk) {
+      half8 af[Cfg::WM], bf[Cfg::WN];
 #pragma unroll
-        for (int n = 2; n < Cfg::WN; ++n) brest[n - 2] = lds_frag(cur, b_row0 + n * 32, kk, lane);
-        if (SPREAD && refill) {
-          constexpr int CPW = Cfg::CHUNKS_PER_WAVE;
-          if (kk == 0) gemm_stage<Cfg, 0, (CPW + 3) / 4>(a_rows, a_rows2, a_split, b_rows, ldk, kt + NS - 1, nxt, wave, lane_off);
-          if (kk == 1) gemm_stage<Cfg, (CPW + 3) / 4, (2 * CPW + 3) / 4>(a_rows, a_rows2, a_split, b_rows, ldk, kt + NS - 1, nxt, wave, lane_off);
-          if (kk == 2) gemm_stage<Cfg, (2 * CPW + 3) / 4, (3 * CPW + 3) / 4>(a_rows, a_rows2, a_split, b_rows, ldk, kt + NS - 1, nxt, wave, lane_off);
-          if (kk == 3) gemm_stage<Cfg, (3 * CPW + 3) / 4, CPW>(a_rows, a_rows2, a_split, b_rows, ldk, kt + NS - 1, nxt, wave, lane_off);
-        }
-        mfma_step<ABLATE == 3>(a_cur[0], b01[0], acc[0][0]);
-        mfma_step<ABLATE == 3>(a_cur[1], b01[0], acc[1][0]);
-        mfma_step<ABLATE == 3>(a_cur[0], b01[1], acc[0][1]);
-        mfma_step<ABLATE == 3>(a_cur[1], b01[1], acc[1][1]);
-        __builtin_amdgcn_sched_barrier(0);
-        if (kk < 3) {
-          b01[0] = lds_frag(cur, b_row0, kk + 1, lane);
-          b01[1] = lds_frag(cur, b_row0 + 32, kk + 1, lane);
-          a_nxt[0] = lds_frag(cur, a_row0, kk + 1, lane);
-          a_nxt[1] = lds_frag(cur, a_row0 + 32, kk + 1, lane);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (PRIO) __builtin_amdgcn_s_setprio(1);
+      for (int a = 0; a < Cfg::WM; ++a) af[a] = lds_frag(cur, a_row0 + a * 32, kk, lane);
 #pragma unroll
-        for (int n = 2; n < Cfg::WN; ++n) {
-          mfma_step<ABLATE == 3>(a_cur[0], brest[n - 2], acc[0][n]);
-          mfma_step<ABLATE == 3>(a_cur[1], brest[n - 2], acc[1][n]);
-        }
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
-        if (kk < 3) { a_cur[0] = a_nxt[0]; a_cur[1] = a_nxt[1]; }
+      for (int n = 0; n < Cfg::WN; ++n) bf[n] = lds_frag(cur, b_row0 + n * 32, kk, lane);
+      if (SPREAD && refill) {
+        // a quarter of the refill per MFMA group instead of one burst after the barrier
+        constexpr int CPW = Cfg::CHUNKS_PER_WAVE;
+        if (kk == 0) gemm_stage<Cfg, 0, (CPW + 3) / 4>(a_rows, a_rows2, a_split, b_rows, ldk, kt + NS - 1, nxt, wave, lane_off);
+        if (kk == 1) gemm_stage<Cfg, (CPW + 3) / 4, (2 * CPW + 3) / 4>(a_rows, a_rows2, a_split, b_rows, ldk, kt + NS - 1, nxt, wave, lane_off);
+        if (kk == 2) gemm_stage<Cfg, (2 * CPW + 3) / 4, (3 * CPW + 3) / 4>(a_rows, a_rows2, a_split, b_rows, ldk, kt + NS - 1, nxt, wave, lane_off);
+        if (kk == 3) gemm_stage<Cfg, (3 * CPW + 3) / 4, CPW>(a_rows, a_rows2, a_split, b_rows, ldk, kt + NS - 1, nxt, wave, lane_off);
       }
-    } else {
 #pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        half8 af[Cfg::WM], bf[Cfg::WN];
+      for (int a = 0; a < Cfg::WM; ++a)
 #pragma unroll
-        for (int a = 0; a < Cfg::WM; ++a) af[a] = lds_frag(cur, a_row0 + a * 32, kk, lane);
-#pragma unroll
-        for (int n = 0; n < Cfg::WN; ++n) bf[n] = lds_frag(cur, b_row0 + n * 32, kk, lane);
-        if (SPREAD && refill) {
-          // a quarter of the refill per MFMA group instead of one burst after the barrier
-          constexpr int CPW = Cfg::CHUNKS_PER_WAVE;
-          if (kk == 0) gemm_stage<Cfg, 0, (CPW + 3) / 4>(a_rows, a_rows2, a_split, b_rows, ldk, kt + NS - 1, nxt, wave, lane_off);
-          if (kk == 1) gemm_stage<Cfg, (CPW + 3) / 4, (2 * CPW + 3) / 4>(a_rows, a_rows2, a_split, b_rows, ldk, kt + NS - 1, nxt, wave, lane_off);
-          if (kk == 2) gemm_stage<Cfg, (2 * CPW + 3) / 4, (3 * CPW + 3) / 4>(a_rows, a_rows2, a_split, b_rows, ldk, kt + NS - 1, nxt, wave, lane_off);
-          if (kk == 3) gemm_stage<Cfg, (3 * CPW + 3) / 4, CPW>(a_rows, a_rows2, a_split, b_rows, ldk, kt + NS - 1, nxt, wave, lane_off);
-        }
-#pragma unroll
-        for (int a = 0; a < Cfg::WM; ++a)
-#pragma unroll
-          for (int n = 0; n < Cfg::WN; ++n)
-            if (ABLATE != 2) acc[a][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[a], bf[n], acc[a][n], 0, 0, 0);
-            else { asm volatile("" :: "v"(af[a]), "v"(bf[n])); }      // ABLATE 2: timing-only build without MFMAs
-      }
+        for (int n = 0; n < Cfg::WN; ++n)
+          acc[a][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[a], bf[n], acc[a][n], 0, 0, 0);
     }
   }
 }

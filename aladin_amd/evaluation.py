@@ -136,7 +136,7 @@ def encode_data_packed(model, data_loader, log_step=10, logging=print, precision
     return img_store, cap_store, list(img_store.lengths), list(cap_store.lengths)
 
 
-def _is_store(x):
+def _is_packed_store(x):
     from .store import PackedSetStore, StoreView
     return isinstance(x, (PackedSetStore, StoreView))
 
@@ -157,9 +157,9 @@ def compute_sim_matrix(img, cap, img_len=None, cap_len=None, mode='matching', pr
     Both arguments may instead be PackedSetStore / StoreView objects (encode_data_packed).
     """
     dev = _device()
-    if _is_store(img) != _is_store(cap):
+    if _is_packed_store(img) != _is_packed_store(cap):
         raise ValueError('compute_sim_matrix: pass two stores or two tensors')
-    if _is_store(img):                            # packed 16-bit stores (encode_data_packed): lengths travel with them
+    if _is_packed_store(img):                            # packed 16-bit stores (encode_data_packed): lengths travel with them
         from .store import alignment_scores_from_stores
         with torch.no_grad():
             if mode == 'matching':
@@ -280,7 +280,7 @@ def _memo_key(images, captions, img_lenghts, cap_lenghts, measure, sim_function)
         if isinstance(x, torch.Tensor):
             objs.append(x)
             return ('t', x.data_ptr(), tuple(x.shape), tuple(x.stride()), x._version, str(x.device))
-        if _is_store(x):
+        if _is_packed_store(x):
             st = getattr(x, 'store', x)
             objs.extend([x, st])
             return ('s', st.n_rows, len(st), hash(tuple(getattr(x, 'ids', ()))), len(x))
@@ -320,7 +320,7 @@ def _eval_scores(images, captions, img_lenghts, cap_lenghts, measure, sim_functi
 
 
 def _eval_scores_uncached(images, captions, img_lenghts, cap_lenghts, measure, sim_function):
-    if _is_store(images):
+    if _is_packed_store(images):
         ims = images.view(slice(0, None, CAPS_PER_IMG))
         if measure == 'order':
             with torch.no_grad():

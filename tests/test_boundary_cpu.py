@@ -70,7 +70,7 @@ def test_source_hash_follows_every_input_of_the_build(tmp_path):
 def test_library_exports_nothing_but_the_declared_symbols():
     """The converse: the product library's dynamic symbol table holds the header's entry points and nothing
     else -- no debug probes, no kernel handles, no C++ helpers (-fvisibility=hidden + csrc/exports.map) -- and
-    reads no environment variable (tuning knobs and timing-only ablation kernels live in the separate
+    reads no environment variable (clock probes and phase stamps live in the separate
     libaladin_hip_diag.so, `make -C aladin_amd/csrc diag`)."""
     import subprocess
     from aladin_amd import _lib

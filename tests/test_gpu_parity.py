@@ -990,9 +990,9 @@ def test_packed_store_scores_are_bit_identical_and_smaller():
     dense_bytes = images.nbytes + captions.nbytes
     assert si.nbytes() + sc.nbytes() < (0.25 if si.precision == 'fp16' else 0.5) * dense_bytes
     S_dense = E.compute_sim_matrix(images[0::5], captions, il[0::5], cl, mode='alignment')
-    S_store = E.compute_sim_matrix(si.view(slice(0, None, 5)), sc, mode='alignment')
-    assert torch.equal(S_dense, S_store)
-    assert torch.equal(S_store[:, 3], torch.zeros_like(S_store[:, 3]))        # no scored word -> exact 0 column
+    S_packed = E.compute_sim_matrix(si.view(slice(0, None, 5)), sc, mode='alignment')
+    assert torch.equal(S_dense, S_packed)
+    assert torch.equal(S_packed[:, 3], torch.zeros_like(S_packed[:, 3]))        # no scored word -> exact 0 column
     # arbitrary sub-grids through index views
     N = images.shape[0]
     pick_i, pick_c = [N - 5, 0, 15, 5], [7, 3, N - 1, 4, N // 2]

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Scores of the bench batch (B = 256, full lengths) and of a ragged batch from whatever library / variant the environment
-selects (ALADIN_LIB, ALADIN_SCORE_VARIANT ... of the diag build), saved for a bit-for-bit comparison between variants:
+"""Scores of the bench batch (B = 256, full lengths) and of a ragged batch from the library ALADIN_LIB selects, saved for a
+bit-for-bit comparison between two builds (an old library built from another checkout against the new one):
 
-    python tools/check_variant.py save gpurun_out/S_base.pt
-    ALADIN_LIB=aladin_amd/lib/libaladin_hip_diag.so ALADIN_SCORE_VARIANT=1 python tools/check_variant.py save gpurun_out/S_v1.pt
-    python tools/check_variant.py cmp gpurun_out/S_base.pt gpurun_out/S_v1.pt
+    ALADIN_LIB=/path/to/old/libaladin_hip.so python tools/check_variant.py save S_old.pt
+    python tools/check_variant.py save S_new.pt
+    python tools/check_variant.py cmp S_old.pt S_new.pt
 """
 import os
 import sys
