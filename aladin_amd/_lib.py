@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # ALADIN_LIB points at an alternative build of the same ABI (kernel A/B runs, tools/ab_bench.py)
 LIB_PATH = os.environ.get('ALADIN_LIB') or os.path.join(_HERE, 'lib', 'libaladin_hip.so')
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 PRECISION_FP16, PRECISION_SPLIT = 0, 1      # ALADIN_PRECISION_* of include/aladin_hip.h
 BWD_PARTNERS_FP16, BWD_DENSE, BWD_DENSE_GATHER, TRIPLET_BWD_BASE_WORKSPACE, BWD_OWN_ROW_FP16 = 1, 2, 4, 8, 16      # ALADIN_BWD_*, ALADIN_TRIPLET_BWD_BASE_WORKSPACE
 
@@ -18,6 +18,7 @@ BWD_PARTNERS_FP16, BWD_DENSE, BWD_DENSE_GATHER, TRIPLET_BWD_BASE_WORKSPACE, BWD_
 SYMBOLS = [
     'aladin_version', 'aladin_last_error', 'aladin_align_geometry', 'aladin_align_pack', 'aladin_align_scores',
     'aladin_align_bwd_workspace_bytes', 'aladin_align_bwd',
+    'aladin_align_long_geometry', 'aladin_align_long_scores', 'aladin_align_long_bwd_workspace_bytes', 'aladin_align_long_bwd',
     'aladin_align_triplet_workspace_bytes', 'aladin_align_triplet_fwd', 'aladin_align_triplet_bwd', 'aladin_heads_small_fwd_argmax',
     'aladin_hinge_workspace_bytes', 'aladin_hinge_fwd_bwd', 'aladin_hinge_fused',
     'aladin_listnet_workspace_bytes', 'aladin_listnet_fwd_bwd',
@@ -71,6 +72,10 @@ def _declare(lib):
         'aladin_align_scores': (C.c_int, [PK, G, p, p, i64, i32, p]),
         'aladin_align_bwd_workspace_bytes': (sz, [G, i32]),
         'aladin_align_bwd': (C.c_int, [SV, SV, G, PK, p, i64, p, p, p, GV, GV, p, i32, p]),
+        'aladin_align_long_geometry': (C.c_int, [i32, i32, i32, i32, i32, i32, i32, i32, G]),
+        'aladin_align_long_scores': (C.c_int, [PK, G, p, i64, p]),
+        'aladin_align_long_bwd_workspace_bytes': (sz, [G]),
+        'aladin_align_long_bwd': (C.c_int, [SV, SV, G, PK, p, i64, p, GV, GV, p, i32, p]),
         'aladin_align_triplet_workspace_bytes': (sz, [G]),
         'aladin_align_triplet_fwd': (C.c_int, [SV, SV, G, f32, PK, p, i64, p, p, p, p]),
         'aladin_align_triplet_bwd': (C.c_int, [SV, SV, G, PK, p, p, GV, GV, p, i32, p]),

@@ -204,6 +204,7 @@ class ALADModel(nn.Module):
         return (self.graphed and not self._graph_bypass and log and torch.is_grad_enabled() and img_emb.is_cuda
                 and any(t.requires_grad for t in (img_emb, cap_emb, img_emb_set, cap_emb_seq))
                 and 'regularizehidden' not in self.losses_types and self._fused_heads_ok(img_emb)
+                and not ops.is_long(img_emb_set.shape[0], cap_emb_seq.shape[0])          # long sets: the eager step
                 and not torch.cuda.is_current_stream_capturing())
 
     def forward_loss_total(self, img_emb, cap_emb, img_emb_set, cap_emb_seq, img_lengths, cap_lengths, reg_loss, epoch=0,
@@ -220,7 +221,9 @@ class ALADModel(nn.Module):
                 from .graphs import GraphedLossStep
                 self._graph_step = GraphedLossStep(self, log='deferred')
             return self._graph_step(img_emb, cap_emb, img_emb_set, cap_emb_seq, img_lengths, cap_lengths, reg_loss, epoch, distill_epoch)
-        if not self._fused_heads_ok(img_emb):
+        # long sets at bs <= SMALL_BATCH_MAX: the composed path (the fused small-batch heads stop at the tile classes)
+        long_small = img_emb.shape[0] <= ops.SMALL_BATCH_MAX and ops.is_long(img_emb_set.shape[0], cap_emb_seq.shape[0])
+        if not self._fused_heads_ok(img_emb) or long_small:
             d = self.forward_loss(img_emb, cap_emb, img_emb_set, cap_emb_seq, img_lengths, cap_lengths, reg_loss, log=log)
             return self.weighted_total(d, epoch, distill_epoch), d
         wants_matching = 'matching' in self.config['training']['loss-type']

@@ -100,6 +100,46 @@ def align_geometry(Bi, Bc, R, T, D, x_tail=0, y_tail=2, precision=None):
     return g
 
 
+# Long sets: past the tile classes of aladin_align_geometry (more than 96 scored positions on either side) the packed layout,
+# the score kernel and the backward are those of csrc/align_long.hip (aladin_align_long_*), up to LONG_POSITIONS positions per
+# set.  Shapes inside the classes never take them, except under LONG_PATH_FORCE (tests / tools: the long kernels against the
+# tile kernels on the same shape).
+LONG_POSITIONS = 512
+LONG_PATH_FORCE = False
+
+
+class LongGeom(_lib.AlignGeom):
+    """struct aladin_align_geom from aladin_align_long_geometry: the layout the long-set kernels read."""
+
+
+def is_long(R, T, x_tail=0, y_tail=2):
+    """Does a (max side R positions) x (sum side T positions) problem take the long-set kernels?"""
+    return LONG_PATH_FORCE or R - 1 - x_tail > 96 or T - 1 - y_tail > 96
+
+
+def long_geometry(Bi, Bc, R, T, D, x_tail=0, y_tail=2, precision=None):
+    """Packed layout of the long-set kernels (aladin_align_long_geometry) for up to LONG_POSITIONS positions per set."""
+    prec = _precision_code(precision)
+    key = ('long', Bi, Bc, R, T, D, x_tail, y_tail, prec)
+    g = _GEOM_CACHE.get(key)
+    if g is None:
+        g = LongGeom()
+        _lib.check(_lib.load().aladin_align_long_geometry(Bi, Bc, R, T, D, x_tail, y_tail, prec, C.byref(g)), 'align_long_geometry')
+        if len(_GEOM_CACHE) < 1024:
+            _GEOM_CACHE[key] = g
+    return g
+
+
+def _scoring_geometry(Bi, Bc, R, T, D, x_tail, y_tail, precision=None):
+    """The layout the scoring path packs for: the tile classes, or past them the long-set layout."""
+    if is_long(R, T, x_tail, y_tail):
+        if R > LONG_POSITIONS or T > LONG_POSITIONS:
+            raise ValueError('aladin_amd: alignment scores support at most %d positions per set (got %d on the max side, %d on the '
+                             'sum side)' % (LONG_POSITIONS, R, T))
+        return long_geometry(Bi, Bc, R, T, D, x_tail, y_tail, precision)
+    return align_geometry(Bi, Bc, R, T, D, x_tail, y_tail, precision)
+
+
 def _set_view(t, len_t):
     """struct aladin_set of a (B, N, D) tensor with a unit inner stride."""
     return _lib.SetView(t.data_ptr(), t.stride(0), t.stride(1), len_t.data_ptr())
@@ -148,8 +188,11 @@ def pack_captions(s, s_len_t, geom, rnorm=None):
 def scores_from_packed(xm, xe, y, geom, out=None, e_scratch=None, reuse_side=False):
     lib = _lib.load()
     S = out if out is not None else torch.empty((geom.Bi, geom.Bc), dtype=torch.float32, device=xm.device)
-    e = e_scratch if e_scratch is not None else _workspace(geom.e_bytes, xm.device)
     pk = _packed_struct(xm, xe, y)
+    if isinstance(geom, LongGeom):
+        _lib.check(lib.aladin_align_long_scores(C.byref(pk), C.byref(geom), _ptr(S), S.stride(0), _stream()), 'align_long_scores')
+        return S
+    e = e_scratch if e_scratch is not None else _workspace(geom.e_bytes, xm.device)
     _lib.check(lib.aladin_align_scores(C.byref(pk), C.byref(geom), _ptr(e), _ptr(S), S.stride(0), 1 if reuse_side else 0, _stream()),
                'align_scores')
     return S
@@ -175,9 +218,9 @@ def _check_backward_supported(im, s, x_tail, y_tail):
     if D % 4 != 0 or D > 1024:
         raise ValueError('aladin_amd: differentiable alignment scores need D <= 1024 (got D=%d; the public entry points pad a '
                          'feature size that is not a multiple of 4); score under torch.no_grad()' % D)
-    if R - 1 - x_tail > 96 or T - 1 - y_tail > 96:          # = the packed geometry's own limits (aladin_align_geometry)
-        raise ValueError('aladin_amd: alignment scores support at most 96 scored positions per set '
-                         '(got %d on the max side, %d on the sum side)' % (R - 1 - x_tail, T - 1 - y_tail))
+    if R > LONG_POSITIONS or T > LONG_POSITIONS:            # = the long-set geometry's limit (aladin_align_long_geometry)
+        raise ValueError('aladin_amd: alignment scores support at most %d positions per set '
+                         '(got %d on the max side, %d on the sum side)' % (LONG_POSITIONS, R, T))
 
 
 def pack_sets(im, s, im_len_t, s_len_t, geom, norms=True):
@@ -200,7 +243,7 @@ def _align_forward(im, s, im_len_t, s_len_t, x_tail=0, y_tail=2, precision=None,
     Bc, T, D2 = s.shape
     if D != D2:
         raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (D, D2))
-    geom = align_geometry(Bi, Bc, R, T, D, x_tail, y_tail, precision)
+    geom = _scoring_geometry(Bi, Bc, R, T, D, x_tail, y_tail, precision)
     packed = pack_sets(_rows_inner_contig(im), _rows_inner_contig(s), im_len_t, s_len_t, geom, norms=norms)
     return scores_from_packed(packed[1], packed[2], packed[3], geom), packed
 
@@ -308,6 +351,8 @@ def _align_backward(im, s, im_len_t, s_len_t, dS, gscale=None, packed=None, pair
     ld_dS = dS.shape[1]            # (not stride(0): a contiguous (1, n) view may report any leading stride)
     Bi, R, D = im.shape
     Bc, T, _ = s.shape
+    if isinstance(packed[0] if packed is not None else None, LongGeom) or (packed is None and is_long(R, T, *x_tails)):
+        return _align_backward_long(im, s, im_len_t, s_len_t, dS, ld_dS, gscale, packed, x_tails)
     d_im, d_s = _grad_like(im), _grad_like(s)
     have = packed is not None and packed[1] is not None
     dense_flag = _lib.BWD_DENSE if (dense and DENSE_BACKWARD and have and Bi * Bc >= DENSE_MIN_PAIRS) else 0
@@ -330,6 +375,25 @@ def _align_backward(im, s, im_len_t, s_len_t, dS, gscale=None, packed=None, pair
     return d_im, d_s
 
 
+def _align_backward_long(im, s, im_len_t, s_len_t, dS, ld_dS, gscale, packed, x_tails):
+    """aladin_align_long_bwd: the pair-list path for any dS (a dense one included), the row step's unit vectors as
+    set_backward_precision() says when the forward's packed operands are at hand."""
+    lib = _lib.load()
+    Bi, R, D = im.shape
+    Bc, T, _ = s.shape
+    d_im, d_s = _grad_like(im), _grad_like(s)
+    have = packed is not None and packed[1] is not None
+    geom = packed[0] if packed is not None else long_geometry(Bi, Bc, R, T, D, *x_tails)
+    pk = _packed_struct(packed[1], packed[2], packed[3], packed[4] if len(packed) > 4 else None) if have else None
+    flags = _bwd_flags(packed) if have else 0
+    _LAST_BWD_FLAGS[0] = 0
+    ws = _workspace(lib.aladin_align_long_bwd_workspace_bytes(C.byref(geom)), im.device)
+    vi, vs, gi, gs = _set_view(im, im_len_t), _set_view(s, s_len_t), _grad_view(d_im), _grad_view(d_s)
+    _lib.check(lib.aladin_align_long_bwd(C.byref(vi), C.byref(vs), C.byref(geom), C.byref(pk) if pk is not None else None, _ptr(dS), ld_dS,
+                                         _ptr(gscale), C.byref(gi), C.byref(gs), _ptr(ws), flags, _stream()), 'align_long_bwd')
+    return d_im, d_s
+
+
 _TRIPLET_WS = {}
 
 
@@ -345,6 +409,8 @@ def _triplet_forward(im, s, im_len_t, s_len_t, margin, loss_out=None):
     covered (the caller composes the generic calls)."""
     Bi, R, D = im.shape
     Bc, T, _ = s.shape
+    if is_long(R, T):
+        return None
     geom = align_geometry(Bi, Bc, R, T, D)
     if not _triplet_fused_ok(geom):
         return None
@@ -647,7 +713,9 @@ def _scores_nograd(xs, ys, x_len, y_len, x_tail, y_tail, precision):
     x_len, y_len = _host_lengths(x_len), _host_lengths(y_len)
     dev = xs.device
     plan = None
-    if len(x_len) * len(y_len) >= BUCKET_MIN_PAIRS:
+    # a grid whose trimmed sets are past the tile classes is one launch of the long-set kernels (no length classes beyond 96)
+    if len(x_len) * len(y_len) >= BUCKET_MIN_PAIRS and \
+            not is_long(min(xs.shape[1], max(x_len) + 1), min(ys.shape[1], max(y_len)), x_tail, y_tail):
         plan = grid_plan(('dense', tuple(x_len), tuple(y_len), x_tail, y_tail, xs.shape[1], ys.shape[1]),
                          lambda: _needed_positions(x_len, x_tail, xs.shape[1], True),
                          lambda: _needed_positions(y_len, y_tail, ys.shape[1], False), dev)
@@ -680,7 +748,7 @@ def _scores_nograd_block(xs, ys, x_len, y_len, x_tail, y_tail, precision, x_tota
     dev = xs.device
     x_len_t, y_len_t = lengths_tensor(x_len, dev), lengths_tensor(y_len, dev)
     Bx, By, D = xs.shape[0], ys.shape[0], xs.shape[2]
-    geom = align_geometry(Bx, By, n_eff, m_eff, D, x_tail, y_tail, precision)
+    geom = _scoring_geometry(Bx, By, n_eff, m_eff, D, x_tail, y_tail, precision)
     if geom.e_bytes <= E_SCRATCH_LIMIT:
         return _align_forward(xs, ys, x_len_t, y_len_t, x_tail, y_tail, precision, norms=False)[0]
     step = max(geom.cap_unit, int(By * E_SCRATCH_LIMIT // geom.e_bytes) // geom.cap_unit * geom.cap_unit)

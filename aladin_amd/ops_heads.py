@@ -9,7 +9,7 @@ from . import _lib
 from . import ops as _al
 from ._ops_common import _RAW_STREAM, _stream, _ptr, _require_gpu, _rows_inner_contig, _LEN_CACHE, lengths_tensor, _ld, _workspace
 from .ops import (_FILL_HINT, _align_backward, _align_forward, _caption_fill, _check_backward_supported, _check_sets, _density_probe,
-                  _packed_from_buf, _packed_struct, _pair_kernel_covers, _set_view, _triplet_backward, _triplet_forward)
+                  _packed_from_buf, _packed_struct, _pair_kernel_covers, _set_view, _triplet_backward, _triplet_forward, is_long)
 from .ops_losses import _hinge_raw, _sgemm, dot_scores
 
 
@@ -282,7 +282,10 @@ def small_batch_loss_heads(img_emb, cap_emb, im_set, s_seq, im_len, s_len, margi
             from .ops import _pad_features
             im_set, s_seq = _pad_features(im_set, s_seq)          # D % 4 != 0: zero features, dropped again by autograd
     w = (float(weights.get('matching', 0.0)), float(weights.get('alignment', 0.0)), float(weights.get('distillation', 0.0)))
-    node = _SmallHeads if img_emb.shape[0] <= SMALL_BATCH_MAX else _BigHeads
+    # long sets never reach the small-batch kernels (their tile classes stop at 96 scored positions): the general node
+    long_sets = im_set is not None and s_seq is not None and flags & (HEAD_ALIGN_HINGE | HEAD_LISTNET) and \
+        is_long(im_set.shape[1], s_seq.shape[1])
+    node = _SmallHeads if img_emb.shape[0] <= SMALL_BATCH_MAX and not long_sets else _BigHeads
     _FILL_HINT[0] = _caption_fill(s_len, s_seq.shape[1]) if (node is _BigHeads and not max_violation and flags & HEAD_ALIGN_HINGE) else None
     return node.apply(img_emb, cap_emb, im_set, s_seq, im_len_t, s_len_t, margin, max_violation, flags, w, temperature, eps)
 

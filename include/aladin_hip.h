@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ALADIN_ABI_VERSION 11
+#define ALADIN_ABI_VERSION 12
 
 /* The library is built with -fvisibility=hidden: the entry points declared here are its ONLY exports. */
 #if defined(__GNUC__)
@@ -72,7 +72,8 @@ typedef struct aladin_set_grad {
 typedef struct aladin_align_geom {
   int32_t Bi, Bc, R, T, D;      /* inputs: im (Bi,R,D), s (Bc,T,D)                              */
   int32_t Rq, Tq;               /* R-1 regions and T-3 words take part (alad/loss.py:87-88)     */
-  int32_t mrows;                /* rows per image in the main operand xm: 32, 48, 64 or 96 (rows past R' repeat region 0) */
+  int32_t mrows;                /* rows per image in the main operand xm: 32, 48, 64 or 96 (rows past R' repeat region 0);
+                                   round_up(R', 32) up to 512 from aladin_align_long_geometry */
   int32_t rem;                  /* leftover regions per image (R' - mrows when positive) that go through the side GEMM: <= 8 */
   int32_t tp16;                 /* 16-word column tiles a caption needs: ceil(trows / 16)       */
   int32_t trows;                /* rows per caption in y: 16 * tp16, or 16 * tp16 - 8 = 8 / 24 / 40 (T' <= 8 / 17..24 / 33..40
@@ -174,6 +175,33 @@ ALADIN_API int aladin_align_bwd(const aladin_set* im, const aladin_set* s, const
                                 const aladin_packed* packed, const float* dS, int64_t ld_dS, const float* gscale,
                                 const int32_t* pairs, const int32_t* pair_count, const aladin_set_grad* d_im,
                                 const aladin_set_grad* d_s, void* workspace, int flags, void* stream);
+
+/* Long sets: more than 96 scored positions on either side (the tile classes of aladin_align_geometry stop there), up to
+ * 512 positions per set -- R <= 512 and T <= 512, i.e. up to 511 scored regions on the max side and 509 scored words on the sum
+ * side (csrc/align_long.hip).  aladin_align_geometry keeps its limits; shapes past them take these entry points:
+ *   aladin_align_long_geometry   the packed layout: mrows = round_up(R', 32) rows per max-side sample (rows past R' repeat its
+ *                                first scored position), no side rows (rem 0, xe_bytes 0, e_bytes 0), trows = round_up(T', 16)
+ *                                rows per sum-side sample, cap_unit = 512 / trows samples per score workgroup, Bc_pad rounded to
+ *                                it; rnorm is [xm rows | y rows].  ALADIN_PRECISION_FP16 or ALADIN_PRECISION_SPLIT; R or T past
+ *                                512: ALADIN_ERR_UNSUPPORTED.  aladin_align_pack packs for this geometry as for the other one.
+ *   aladin_align_long_scores     S (Bi x Bc, row stride ldS) from the packed operands, both precisions; bitwise reproducible.
+ *   aladin_align_long_bwd        the backward of aladin_align_bwd for these shapes, any dS (the pair-list path also for a dense
+ *                                dS): the non-zero pairs of dS are compacted, every word's arg-max region of every listed pair is
+ *                                decided in fp32 from the raw rows (16-bit table entries), and one wave per output row gathers
+ *                                the partner rows.  flags: ALADIN_BWD_PARTNERS_FP16 (partner rows from `packed`, which then
+ *                                needs xm, y and rnorm) and ALADIN_BWD_OWN_ROW_FP16 (with it: the row's own unit vector too);
+ *                                `packed` may be NULL otherwise.  D % 4 == 0, D <= 1024, fp16 operands (split is forward-only).
+ *                                d_im / d_s fully written (zeros outside the alignment), no atomics.
+ * Every entry point takes only a geometry of aladin_align_long_geometry (ALADIN_ERR_ARG otherwise). */
+ALADIN_API int aladin_align_long_geometry(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail, int precision,
+                                          aladin_align_geom* out);
+ALADIN_API int aladin_align_long_scores(const aladin_packed* packed, const aladin_align_geom* geom, float* S, int64_t ldS,
+                                        void* stream);
+ALADIN_API size_t aladin_align_long_bwd_workspace_bytes(const aladin_align_geom* geom);
+ALADIN_API int aladin_align_long_bwd(const aladin_set* im, const aladin_set* s, const aladin_align_geom* geom,
+                                     const aladin_packed* packed, const float* dS, int64_t ld_dS, const float* gscale,
+                                     const aladin_set_grad* d_im, const aladin_set_grad* d_s, void* workspace, int flags,
+                                     void* stream);
 
 /* The training step of AlignmentContrastiveLoss(max_violation=True, aggregation='MrSw') -- every shipped YAML,
  * alad/loss.py:79-159 through alad/alad_model.py:386 -- as ONE call per direction, so that an eager drop-in module costs one
