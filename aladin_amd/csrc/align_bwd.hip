@@ -20,39 +20,33 @@
 //                     results are bitwise reproducible and every output row is written exactly once
 //                     (rows outside the alignment -- region 0, token 0, the last two tokens, padding
 //                     -- get exact zeros, as in the reference).
+//
+//   Host side (end of the file): BwdProblem (bwd_common.hpp) describes the problem, bwd_check validates it before anything is
+//   launched, and one small function per stage does the work.  The exported entry points compose the stages:
+//     aladin_align_bwd               check -> (table of all pairs | the caller's list | list from dS) -> table from the list
+//                                    -> (rows by GEMM, align_bwd_dense.hip | rows by gather)
+//     aladin_align_triplet_fwd       check -> pack -> scores -> table from the hinge statistics
+//     aladin_align_triplet_bwd       check -> rows by gather
+//     aladin_heads_small_fwd_argmax  check -> statistics -> table from the statistics
 #include "../../include/aladin_hip.h"
+#include "bwd_common.hpp"
 #include "gemm_core.hpp"
 #include "hinge_common.hpp"
 #include "small_heads_common.hpp"
 
 #define NO_GRAD 255
 
-struct BwdWs {
-  int* counter;      // [64] ints, [0] = number of listed pairs
-  int* pairs;        // Bi*Bc
-  uint8_t* table;    // Bi*Bc rows of TQP = round_up(Tq,16) bytes
-};
-static inline int table_stride(int Tq) { return (Tq + 15) / 16 * 16; }
-
-static size_t bwd_ws_layout(int Bi, int Bc, int Tq, char* base, BwdWs* ws) {
-  size_t off = 0;
-  if (ws) ws->counter = (int*)(base + off);
-  off += 256;
-  if (ws) ws->pairs = (int*)(base + off);
-  off += ((size_t)Bi * Bc * 4 + 255) / 256 * 256;
-  if (ws) ws->table = (uint8_t*)(base + off);
-  off += ((size_t)Bi * Bc * table_stride(Tq) + 255) / 256 * 256;
-  return off;
-}
+using BwdWs = PairWs<uint8_t>;      // the table: Bi*Bc rows of table_stride(Tq) bytes
 
 static size_t bwd_base_bytes(int Bi, int Bc, int T) {
   if (Bi < 1 || Bc < 1 || T < 2) return 0;
-  return bwd_ws_layout(Bi, Bc, T - 1, nullptr, nullptr);      // sized for the longest possible word axis (tail 0)
+  return pair_ws_layout<uint8_t>(Bi, Bc, T - 1, nullptr, nullptr);      // sized for the longest possible word axis (tail 0)
 }
 
 // ALADIN_BWD_DENSE scratch behind the base workspace: the split-precision operands of the arg-max tile kernel
-// (align_fwd.hip: aladin_internal_align_argmax), its side scratch and one flag byte per pair
-struct DenseWs { void* xm; void* xe; void* y; float* E; uint8_t* flags; };
+// (align_fwd.hip: aladin_internal_align_argmax), its side scratch and one flag byte per pair; behind them the scratch of the
+// GEMM row step (align_bwd_dense.hip)
+struct DenseWs { void* xm; void* xe; void* y; float* E; uint8_t* flags; void* rows; };
 static size_t dense_ws_layout(const aladin_align_geom* gs, char* base, DenseWs* ws) {
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
   size_t off = 0;
@@ -66,6 +60,7 @@ static size_t dense_ws_layout(const aladin_align_geom* gs, char* base, DenseWs* 
   off += up((size_t)gs->e_bytes + 16);
   if (ws) ws->flags = (uint8_t*)(base + off);
   off += up((size_t)gs->Bi * gs->Bc);
+  if (ws) ws->rows = base + off;
   return off;
 }
 // the tile classes the arg-max kernel covers; fills the split geometry of the problem
@@ -83,13 +78,13 @@ extern "C" size_t aladin_align_bwd_workspace_bytes(const aladin_align_geom* g, i
   if (n == 0 || !(flags & ALADIN_BWD_DENSE)) return n;
   // exact: the largest need over the three tail conventions a caller can pack (image / caption, role-swapped, none) --
   // [split operands + side scratch + flags | GEMM row step: transposed operands + split-K partial sums], laid out by
-  // align_bwd_impl exactly as here
+  // aladin_align_bwd exactly as here
   size_t need = 0;
   const int tails[3][2] = {{0, 2}, {2, 0}, {0, 0}};
   for (auto& t : tails) {
     aladin_align_geom gs;
     if (!dense_supported(Bi, Bc, R, T, D, t[0], t[1], &gs)) continue;
-    const size_t b = dense_ws_layout(&gs, nullptr, nullptr) + aladin_internal_dense_rows_bytes(Bi, Bc, R, T, D, t[0], t[1]);
+    const size_t b = dense_ws_layout(&gs, nullptr, nullptr) + aladin_internal_dense_rows_bytes(&gs);
     need = b > need ? b : need;
   }
   n += need;
@@ -201,10 +196,9 @@ __global__ __launch_bounds__(256) void bwd_pair_argmax_kernel(
       // accumulator row = (r&3) + 8*(r>>2) + 4*h  -> needs the norm of THAT row, held by lane (row)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-        const float n2 = __shfl(ss, row, 64);
-        const float inv = 1.0f / fmaxf(sqrtf(n2), 1e-12f);
-        blk[tm * 32 + row][tn * 32 + l5] = acc[r] * inv;   // the caption norm is a positive column factor: irrelevant for argmax / sign
+        const int row = cos_tile_row(r, h);
+        const float inv = cos_tile_inv_norm(ss, row);
+        blk[tm * 32 + row][tn * 32 + l5] = acc[r] * inv;
       }
     }
     __syncthreads();
@@ -507,28 +501,6 @@ struct RowAcc {
   }
 };
 
-// FULL: D == 256 NCH (D = 768, 512, 256, 1024): every lane's columns exist and the loads need no per-chunk exec-mask branch
-template <int NCH, bool FULL>
-__device__ __forceinline__ void load_row(const float* __restrict__ p, int D, int lane, float4 (&v)[NCH]) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int col = lane * 4 + 256 * c;
-    v[c] = (FULL || col < D) ? *reinterpret_cast<const float4*>(p + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-template <int NCH>
-__device__ __forceinline__ float row_sumsq(const float4 (&v)[NCH]) {
-  float ss = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) ss += v[c].x * v[c].x + v[c].y * v[c].y + v[c].z * v[c].z + v[c].w * v[c].w;
-  return ss;
-}
-template <int NCH>
-__device__ __forceinline__ void axpy_row(float f, const float4 (&v)[NCH], RowAcc<NCH>& acc) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) { acc.a[c].x += f * v[c].x; acc.a[c].y += f * v[c].y; acc.a[c].z += f * v[c].z; acc.a[c].w += f * v[c].w; }
-}
-
 // gather one or two partner rows (r1 == nullptr: one); both loads are issued before either is used
 template <int NCH, bool FULL>
 __device__ __forceinline__ void gather2(const float* __restrict__ r0, float g0, const float* __restrict__ r1, float g1, int D,
@@ -538,10 +510,10 @@ __device__ __forceinline__ void gather2(const float* __restrict__ r0, float g0, 
   if (r1 != nullptr) {                                   // wave-uniform
     load_row<NCH, FULL>(r1, D, lane, v1);
     const float n1 = wave_sum(row_sumsq<NCH>(v1));
-    axpy_row<NCH>(g1 / fmaxf(sqrtf(n1), 1e-12f), v1, acc);
+    axpy_row<NCH>(g1 / fmaxf(sqrtf(n1), 1e-12f), v1, acc.a);
   }
   const float n0 = wave_sum(row_sumsq<NCH>(v0));
-  axpy_row<NCH>(g0 / fmaxf(sqrtf(n0), 1e-12f), v0, acc);
+  axpy_row<NCH>(g0 / fmaxf(sqrtf(n0), 1e-12f), v0, acc.a);
 }
 
 // The opt-in ALADIN_BWD_PARTNERS_FP16 form of the gather: partner rows come from the forward's PACKED operands -- unit
@@ -549,27 +521,15 @@ __device__ __forceinline__ void gather2(const float* __restrict__ r0, float g0, 
 // The 2^-12 relative rounding of the partners puts the gradients ~1.5e-4 of their maximum off the reference's (inside
 // north_star's 1e-3; the exact path holds 3e-5), which is why it is not the default.
 template <int NCH, bool FULL>
-__device__ __forceinline__ void load_row_h(const half_t* __restrict__ p, int D, int lane, float4 (&v)[NCH]) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int col = lane * 4 + 256 * c;
-    if (FULL || col < D) {
-      const uint2 raw = *reinterpret_cast<const uint2*>(p + col);
-      const half_t* h = reinterpret_cast<const half_t*>(&raw);
-      v[c] = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
-    } else v[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-template <int NCH, bool FULL>
 __device__ __forceinline__ void gather2_h(const half_t* __restrict__ r0, float g0, const half_t* __restrict__ r1, float g1, int D,
                                           int lane, RowAcc<NCH>& acc) {
   float4 v0[NCH], v1[NCH];
   load_row_h<NCH, FULL>(r0, D, lane, v0);
   if (r1 != nullptr) {                                   // wave-uniform
     load_row_h<NCH, FULL>(r1, D, lane, v1);
-    axpy_row<NCH>(g1, v1, acc);
+    axpy_row<NCH>(g1, v1, acc.a);
   }
-  axpy_row<NCH>(g0, v0, acc);
+  axpy_row<NCH>(g0, v0, acc.a);
 }
 // where the packers put region `r` of max-side sample `b` / word `w` of sum-side sample `b` (aladin_align_geometry)
 struct PackedRows { const half_t* xm; const half_t* xe; const half_t* y; int Dp, main_rows, rem, ycap; const float* rnorm; int64_t xe_row0, y_row0; };
@@ -774,178 +734,171 @@ __global__ __launch_bounds__(256) void bwd_rows_kernel(
   }
 }
 
-// phases of align_bwd_impl: everything (list or compaction -> pair argmax -> rows); the rows alone (the table is already in the
-// workspace); or hinge statistics + the merged [pair argmax | hinge finish] kernel (forward of the fused triplet node)
-enum { BWD_ALL = 0, BWD_ROWS = 1, BWD_HINGE_ARGMAX = 2 };
-struct HingeArgs { const float* S; int64_t ldS; float margin; float* loss; float* dS; void* workspace; const SmallFin* small; };
+// ------------------------------------------------------------------------------------------------
+// host side.  The stages name their kernels in the order the code object has always held them (first use decides where a
+// template's instantiation lands): the layout is part of what a benchmark measures, and it is the parent's byte for byte.
+// ------------------------------------------------------------------------------------------------
+// Classes the fp16 pair kernel covers (the comment above PairCfg).  ops._pair_kernel_covers is the Python mirror of this.
+static bool pair16_covers(const aladin_align_geom* g) {
+  return (g->mrows == 32 || g->mrows == 48 || (g->mrows == 64 && g->rem == 0)) && g->tp16 <= 4;
+}
+static inline int bwd_Rq(const aladin_align_geom* g) { return g->R - 1 - g->x_tail; }
+static inline int bwd_Tq(const aladin_align_geom* g) { return g->T - 1 - g->y_tail; }
 
-static int align_bwd_impl(const float* im, int64_t im_sb, int64_t im_sr, const int32_t* im_len, const float* s,
-                          int64_t s_sb, int64_t s_st, const int32_t* s_len, int Bi, int Bc, int R, int T, int D,
-                          const float* dS, int64_t ld_dS, const float* gscale, const void* xm, const void* xe,
-                          const void* y, const float* rnorm, const aladin_align_geom* g, const int32_t* pairs_in, const int32_t* count_in,
-                          float* d_im, float* d_s, void* workspace, void* stream, int x_tail = 0, int y_tail = 2,
-                          int64_t dim_sb = 0, int64_t dim_sr = 0, int64_t ds_sb = 0, int64_t ds_st = 0,
-                          int phase = BWD_ALL, const HingeArgs* ha = nullptr, int flags = 0) {
-  if (phase == BWD_HINGE_ARGMAX) {                        // no gradients yet: the argmax table (and the hinge) only
-    if (!ha || !ha->S || !ha->loss || !ha->dS || !ha->workspace || Bi != Bc || ha->ldS < Bc) { aladin_set_error("hinge_argmax: bad argument"); return ALADIN_ERR_ARG; }
-    if (ha->small && Bc > SB_MAX) { aladin_set_error("heads_small: B = %d > %d", Bc, SB_MAX); return ALADIN_ERR_UNSUPPORTED; }
-    dS = ha->dS; ld_dS = Bc;
-  }
-  const bool wants_grads = phase != BWD_HINGE_ARGMAX;     // that phase only fills the argmax table: no gradient buffers yet
-  if (dim_sb == 0 && dim_sr == 0) { dim_sb = (int64_t)R * D; dim_sr = D; }          // contiguous (Bi, R, D) / (Bc, T, D) outputs
-  if (ds_sb == 0 && ds_st == 0) { ds_sb = (int64_t)T * D; ds_st = D; }
-  if (wants_grads && (dim_sb % 4 || dim_sr % 4 || ds_sb % 4 || ds_st % 4 || ((uintptr_t)d_im & 15) || ((uintptr_t)d_s & 15))) {
-    aladin_set_error("align_bwd: gradient rows must be 16-byte aligned (strides %lld %lld %lld %lld)", (long long)dim_sb, (long long)dim_sr, (long long)ds_sb, (long long)ds_st);
+// im, s and g have passed bwd_common_check
+static BwdProblem bwd_problem(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* p, void* stream) {
+  const aladin_packed* pk = (p && p->xm && p->y) ? p : nullptr;
+  return BwdProblem{*im, *s, g, pk, pk && pair16_covers(g), (hipStream_t)stream};
+}
+static BwdWs bwd_ws(const BwdProblem& pr, void* workspace) { BwdWs ws; pair_ws_layout(pr.g->Bi, pr.g->Bc, bwd_Tq(pr.g), (char*)workspace, &ws); return ws; }
+
+// Every argument check behind the entry points' own (null set, split geometry, unknown flag bits), before anything is launched.
+// d_im / d_s: the gradient views (grad_ok), or nullptr for the stages that write no gradients (the hinge tables).
+static int bwd_check(const BwdProblem& pr, const float* dS, int64_t ld_dS, const aladin_set_grad* d_im, const aladin_set_grad* d_s,
+                     const void* workspace, int flags) {
+  const aladin_align_geom* g = pr.g;
+  const aladin_set &im = pr.im, &s = pr.s;
+  if (d_im && d_s && (d_im->stride_b % 4 || d_im->stride_r % 4 || d_s->stride_b % 4 || d_s->stride_r % 4 || ((uintptr_t)d_im->data & 15) || ((uintptr_t)d_s->data & 15))) {
+    aladin_set_error("align_bwd: gradient rows must be 16-byte aligned (strides %lld %lld %lld %lld)", (long long)d_im->stride_b, (long long)d_im->stride_r, (long long)d_s->stride_b, (long long)d_s->stride_r);
     return ALADIN_ERR_ARG;
   }
-  if (!im || !s || !im_len || !s_len || !dS || (wants_grads && (!d_im || !d_s)) || !workspace) { aladin_set_error("align_bwd: null argument"); return ALADIN_ERR_ARG; }
-  if (Bi < 1 || Bc < 1 || R < 2 + x_tail || T < 2 + y_tail || D < 1 || ld_dS < Bc) { aladin_set_error("align_bwd: bad sizes"); return ALADIN_ERR_ARG; }
-  const int Rq = R - 1 - x_tail;
-  if (Rq > PA_MAXR - 2 || Rq >= NO_GRAD || T - 1 - y_tail > PA_MAXT) { aladin_set_error("align_bwd: at most %d regions / %d words", PA_MAXR - 2, PA_MAXT); return ALADIN_ERR_UNSUPPORTED; }
-  if (D % 4 != 0 || D > 1024 || im_sb % 4 || im_sr % 4 || s_sb % 4 || s_st % 4 || ((uintptr_t)im & 15) || ((uintptr_t)s & 15)) {
-    aladin_set_error("align_bwd: needs D %% 4 == 0, D <= 1024 and 16-byte aligned rows (D=%d)", D);
+  if (!set_ok(&im) || !set_ok(&s) || !dS || !workspace) { aladin_set_error("align_bwd: null argument"); return ALADIN_ERR_ARG; }
+  if (g->Bi < 1 || g->Bc < 1 || g->R < 2 + g->x_tail || g->T < 2 + g->y_tail || g->D < 1 || ld_dS < g->Bc) { aladin_set_error("align_bwd: bad sizes"); return ALADIN_ERR_ARG; }
+  if (bwd_Rq(g) > PA_MAXR - 2 || bwd_Rq(g) >= NO_GRAD || bwd_Tq(g) > PA_MAXT) { aladin_set_error("align_bwd: at most %d regions / %d words", PA_MAXR - 2, PA_MAXT); return ALADIN_ERR_UNSUPPORTED; }
+  if (g->D % 4 != 0 || g->D > 1024 || im.stride_b % 4 || im.stride_r % 4 || s.stride_b % 4 || s.stride_r % 4 || ((uintptr_t)im.data & 15) || ((uintptr_t)s.data & 15)) {
+    aladin_set_error("align_bwd: needs D %% 4 == 0, D <= 1024 and 16-byte aligned rows (D=%d)", g->D);
     return ALADIN_ERR_UNSUPPORTED;
   }
-  const bool packed = xm && y && g && (g->mrows == 32 || g->mrows == 48 || (g->mrows == 64 && g->rem == 0)) && g->tp16 <= 4;   // shapes the fp16 pair kernel covers
-  if (xm && y && g && (g->Bi != Bi || g->Bc != Bc || g->R != R || g->T != T || g->D != D || (g->rem && !xe))) {
-    aladin_set_error("align_bwd: packed operands do not belong to this problem");
+  if (pr.pk && g->rem && !pr.pk->xe) { aladin_set_error("align_bwd: packed operands do not belong to this problem"); return ALADIN_ERR_ARG; }
+  if ((flags & ALADIN_BWD_OWN_ROW_FP16) && !(flags & ALADIN_BWD_PARTNERS_FP16)) { aladin_set_error("align_bwd: ALADIN_BWD_OWN_ROW_FP16 goes with ALADIN_BWD_PARTNERS_FP16"); return ALADIN_ERR_ARG; }
+  // ALADIN_BWD_PARTNERS_FP16: the row step gathers from the packed fp16 operands (must be this problem's, non-split)
+  if ((flags & ALADIN_BWD_PARTNERS_FP16) && (!pr.pk || !pr.pk->rnorm || g->split)) {
+    aladin_set_error("align_bwd: ALADIN_BWD_PARTNERS_FP16 needs the forward's fp16 packed operands (xm, xe, y, rnorm) and their geometry");
     return ALADIN_ERR_ARG;
   }
-  hipStream_t st = (hipStream_t)stream;
-  BwdWs ws;
-  const int Tq = T - 1 - y_tail, tstride = table_stride(Tq);
-  bwd_ws_layout(Bi, Bc, Tq, (char*)workspace, &ws);
+  return ALADIN_OK;
+}
+
+// ---- stage: list from dS ------------------------------------------------------------------------------------------------------------
+int aladin_internal_compact_pairs(const float* dS, int64_t ld, int Bi, int Bc, int* counter, int* pairs, const char* entry, hipStream_t st) {
+  if (hipMemsetAsync(counter, 0, 256, st) != hipSuccess) { aladin_set_error("%s: memset failed", entry); return ALADIN_ERR_HIP; }
   const int64_t n = (int64_t)Bi * Bc;
-  int rc = ALADIN_OK;
-  if (phase == BWD_HINGE_ARGMAX) {
-    if (!packed) { aladin_set_error("hinge_argmax: needs the packed fp16 operands of a class the fp16 pair kernel covers (R' <= 64, <= 64 padded words)"); return ALADIN_ERR_UNSUPPORTED; }
-    if (ha->small) {                                      // small-batch heads: their own statistics kernel ran already
-      int npb = (3 * Bc + 7) / 8 * 8;
-      const PairHinge hfs = {nullptr, 0, 0.f, nullptr, nullptr, nullptr, nullptr, Bc, npb, nullptr};
-      SmallFin sfin = *ha->small;
-      sfin.dST = (float*)ws.pairs;                        // the list region is free in this mode: it carries dS^T
-      hipLaunchKernelGGL(bwd_pair_argmax16_kernel<2>, dim3(npb + cdiv(Bc * Bc, 256)), dim3(256),
-                         (size_t)PAIR_STAGES * PairCfg::STAGE_BYTES, st, (const half_t*)xm, (const half_t*)xe, (const half_t*)y,
-                         g->Dp, g->mrows, g->rem, g->trows, (int)g->xe_rows, (int)g->y_rows, im, im_sb, im_sr, im_len, s, s_sb, s_st,
-                         s_len, Bc, Rq, Tq, D, nullptr, nullptr, ws.table, tstride, x_tail, y_tail, hfs, sfin);
-      return aladin_check_launch("bwd_pair_argmax16_kernel<small heads>");
-    }
-    rc = aladin_internal_hinge_stats(ha->S, ha->ldS, Bc, ha->margin, 1, ha->workspace, nullptr, st);
-    if (rc) return rc;
-    const float* val = (const float*)ha->workspace;
-    const int* arg = (const int*)(val + 2 * (size_t)Bc);
-    int npb = (3 * Bc + 7) / 8 * 8; if (npb > 2048) npb = 2048;
-    const int nfin = Bc < 1024 ? Bc : 1024;
-    const PairHinge hf = {ha->S, ha->ldS, ha->margin, val, arg, ha->loss, ha->dS, Bc, npb, (float*)ws.pairs};
-    hipLaunchKernelGGL(bwd_pair_argmax16_kernel<1>, dim3(npb + nfin), dim3(256), (size_t)PAIR_STAGES * PairCfg::STAGE_BYTES, st,
-                       (const half_t*)xm, (const half_t*)xe, (const half_t*)y, g->Dp, g->mrows, g->rem, g->trows, (int)g->xe_rows,
-                       (int)g->y_rows, im, im_sb, im_sr, im_len, s, s_sb, s_st, s_len, Bc, Rq, Tq, D, nullptr, nullptr,
-                       ws.table, tstride, x_tail, y_tail, hf, SmallFin{});
-    return aladin_check_launch("bwd_pair_argmax16_kernel<hinge>");
-  }
-  // ALADIN_BWD_DENSE: (almost) every pair carries a gradient.  The table of ALL pairs comes from the forward's own tile
-  // kernel in split precision (64 pairs per workgroup sharing their panels); only the pairs with a word it could not
-  // decide go through the one-workgroup-per-pair exact kernel below.
-  bool dense = false;
-  char* dense_rows_scratch = nullptr;
-  // (the few flagged pairs go through the fp16 pair kernel where it covers the shape, the fp32 one otherwise: R' > 33)
-  if ((flags & ALADIN_BWD_DENSE) && phase == BWD_ALL) {
-    aladin_align_geom gs;
-    if (dense_supported(Bi, Bc, R, T, D, x_tail, y_tail, &gs)) {
-      DenseWs dw;
-      const size_t dense_bytes = dense_ws_layout(&gs, (char*)workspace + bwd_ws_layout(Bi, Bc, T - 1, nullptr, nullptr), &dw);
-      dense_rows_scratch = (char*)workspace + bwd_ws_layout(Bi, Bc, T - 1, nullptr, nullptr) + dense_bytes;      // both 256-multiples
-      {
-        const aladin_set vi = {im, im_sb, im_sr, im_len}, vs = {s, s_sb, s_st, s_len};
-        const aladin_packed pd = {dw.xm, dw.xe, dw.y, nullptr};
-        rc = aladin_internal_pack(&vi, &vs, &gs, &pd, st);
-      }
-      if (rc) return rc;
-      rc = aladin_internal_align_argmax(&gs, dw.xm, dw.xe, dw.y, dw.E, im_len, s_len, ws.table, tstride, dw.flags, st);
-      if (rc) return rc;
-      if (hipMemsetAsync(ws.counter, 0, 256, st) != hipSuccess) { aladin_set_error("align_bwd: memset failed"); return ALADIN_ERR_HIP; }
-      int grid = (int)((n + 255) / 256); if (grid > 1024) grid = 1024;
-      hipLaunchKernelGGL(bwd_compact_flagged_kernel, dim3(grid), dim3(256), 0, st, dS, ld_dS, Bi, Bc, dw.flags, ws.counter, ws.pairs);
-      rc = aladin_check_launch("bwd_compact_flagged_kernel");
-      if (rc) return rc;
-      dense = true;
-    }
-  }
-  if (dense) {
-    // list = the undecided pairs
-  } else if (phase == BWD_ROWS) {
-    // the argmax table of this problem is already in the workspace (aladin_hinge_argmax_fused)
-  } else if (pairs_in && count_in) {                    // list already built by aladin_hinge_fused
-    ws.pairs = const_cast<int*>(pairs_in);
-    ws.counter = const_cast<int*>(count_in);
-  } else {
-    if (hipMemsetAsync(ws.counter, 0, 256, st) != hipSuccess) { aladin_set_error("align_bwd: memset failed"); return ALADIN_ERR_HIP; }
-    int grid = (int)((n + 255) / 256); if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(bwd_compact_kernel, dim3(grid), dim3(256), 0, st, dS, ld_dS, Bi, Bc, ws.counter, ws.pairs);
-    rc = aladin_check_launch("bwd_compact_kernel");
-    if (rc) return rc;
-  }
-  int pgrid = (int)(n < 2048 ? n : 2048);
-  if (phase == BWD_ROWS) {
-  } else if (packed) {
-    hipLaunchKernelGGL(bwd_pair_argmax16_kernel<0>, dim3(pgrid), dim3(256), (size_t)PAIR_STAGES * PairCfg::STAGE_BYTES, st,
-                       (const half_t*)xm, (const half_t*)xe, (const half_t*)y, g->Dp, g->mrows, g->rem, g->trows, (int)g->xe_rows,
-                       (int)g->y_rows, im, im_sb, im_sr, im_len, s, s_sb, s_st, s_len, Bc, Rq, Tq, D, ws.counter, ws.pairs,
-                       ws.table, tstride, x_tail, y_tail, PairHinge{}, SmallFin{});
-    rc = aladin_check_launch("bwd_pair_argmax16_kernel");
-  } else {
-    hipLaunchKernelGGL(bwd_pair_argmax_kernel, dim3(pgrid), dim3(256), 0, st, im, im_sb, im_sr, im_len, s, s_sb, s_st,
-                       s_len, Bc, Rq, Tq, D, ws.counter, ws.pairs, ws.table, tstride, x_tail, y_tail);
-    rc = aladin_check_launch("bwd_pair_argmax_kernel");
-  }
-  if (rc) return rc;
-  const int64_t rows = (int64_t)Bi * R + (int64_t)Bc * T;
-  const unsigned rgrid = (unsigned)((rows + 3) / 4);
-  const int nch = (D + 255) / 256;
-  if (dense && dense_rows_scratch && !(flags & ALADIN_BWD_DENSE_GATHER)) {
-    // every pair carries a gradient: the row step as two MFMA GEMMs over the table (align_bwd_dense.hip)
-    rc = aladin_internal_dense_rows(im, im_sb, im_sr, im_len, s, s_sb, s_st, s_len, Bi, Bc, R, T, D, x_tail, y_tail, dS, ld_dS, gscale,
-                                    ws.table, reinterpret_cast<const unsigned*>(ws.counter) + 1, d_im, d_s, dim_sb, dim_sr, ds_sb, ds_st,
-                                    (flags & ALADIN_BWD_PARTNERS_FP16) != 0, dense_rows_scratch, st);
-    if (rc != ALADIN_ERR_UNSUPPORTED) return rc;
-  }
-  // ALADIN_BWD_PARTNERS_FP16: gather the partner rows from the packed fp16 operands (must be this problem's, non-split)
+  int grid = (int)((n + 255) / 256); if (grid > 1024) grid = 1024;
+  hipLaunchKernelGGL(bwd_compact_kernel, dim3(grid), dim3(256), 0, st, dS, ld, Bi, Bc, counter, pairs);
+  return aladin_check_launch("bwd_compact_kernel");
+}
+
+// the one launch of the fp16 pair kernel: SRC 0 walks (counter, pairs); SRC 1 / 2 derive the pairs from hf / sf and run the
+// element-wise pass in the workgroups past hf.n_pair_blocks
+template <int SRC>
+static int launch_pair16(const BwdProblem& pr, const int* counter, const int* pairs, uint8_t* table, int grid, const PairHinge& hf,
+                         const SmallFin& sf, const char* what) {
+  const aladin_align_geom* g = pr.g;
+  hipLaunchKernelGGL(bwd_pair_argmax16_kernel<SRC>, dim3(grid), dim3(256), (size_t)PAIR_STAGES * PairCfg::STAGE_BYTES, pr.st,
+                     (const half_t*)pr.pk->xm, (const half_t*)pr.pk->xe, (const half_t*)pr.pk->y, g->Dp, g->mrows, g->rem, g->trows,
+                     (int)g->xe_rows, (int)g->y_rows, pr.im.data, pr.im.stride_b, pr.im.stride_r, pr.im.len, pr.s.data, pr.s.stride_b,
+                     pr.s.stride_r, pr.s.len, g->Bc, bwd_Rq(g), bwd_Tq(g), g->D, counter, pairs, table, table_stride(bwd_Tq(g)), g->x_tail,
+                     g->y_tail, hf, sf);
+  return aladin_check_launch(what);
+}
+
+// ---- stage: table from the hinge statistics (no list, no gradients yet) ---------------------------------------------------------------
+// The checks of both hinge-table stages.  hinge_ws: where the statistics live; small: the small-batch heads' form.
+static int hinge_table_check(const BwdProblem& pr, const float* S, int64_t ldS, const float* loss, const float* dS, const void* hinge_ws,
+                             const void* bwd_workspace, bool small) {
+  const aladin_align_geom* g = pr.g;
+  if (!S || !loss || !dS || !hinge_ws || g->Bi != g->Bc || ldS < g->Bc) { aladin_set_error("hinge_argmax: bad argument"); return ALADIN_ERR_ARG; }
+  if (small && g->Bc > SB_MAX) { aladin_set_error("heads_small: B = %d > %d", g->Bc, SB_MAX); return ALADIN_ERR_UNSUPPORTED; }
+  if (int rc = bwd_check(pr, dS, g->Bc, nullptr, nullptr, bwd_workspace, 0)) return rc;
+  if (!pr.pair16) { aladin_set_error("hinge_argmax: needs the packed fp16 operands of a class the fp16 pair kernel covers (R' <= 64, <= 64 padded words)"); return ALADIN_ERR_UNSUPPORTED; }
+  return ALADIN_OK;
+}
+// small-batch heads: their own statistics kernel ran already (SRC 2)
+static int table_from_small_heads(const BwdProblem& pr, SmallFin sf, const BwdWs& ws) {
+  const int B = pr.g->Bc, npb = (3 * B + 7) / 8 * 8;
+  const PairHinge hf = {nullptr, 0, 0.f, nullptr, nullptr, nullptr, nullptr, B, npb, nullptr};
+  sf.dST = (float*)ws.pairs;
+  return launch_pair16<2>(pr, nullptr, nullptr, ws.table, npb + cdiv(B * B, 256), hf, sf, "bwd_pair_argmax16_kernel<small heads>");
+}
+// hardest-negative hinge: statistics, then ONE launch of [pair arg-max | hinge element-wise pass] (SRC 1).  The list region of
+// the workspace is free in these stages: it carries dS^T for the row step.
+static int table_from_hinge(const BwdProblem& pr, const float* S, int64_t ldS, float margin, float* loss, float* dS, void* hinge_ws,
+                            const BwdWs& ws) {
+  const int B = pr.g->Bc;
+  if (int rc = aladin_internal_hinge_stats(S, ldS, B, margin, 1, hinge_ws, nullptr, pr.st)) return rc;
+  const float* val = (const float*)hinge_ws;
+  const int* arg = (const int*)(val + 2 * (size_t)B);
+  int npb = (3 * B + 7) / 8 * 8; if (npb > 2048) npb = 2048;
+  const int nfin = B < 1024 ? B : 1024;
+  const PairHinge hf = {S, ldS, margin, val, arg, loss, dS, B, npb, (float*)ws.pairs};
+  return launch_pair16<1>(pr, nullptr, nullptr, ws.table, npb + nfin, hf, SmallFin{}, "bwd_pair_argmax16_kernel<hinge>");
+}
+
+// ---- stage: table from a pair list --------------------------------------------------------------------------------------------------
+// fp16 pair kernel where it covers the class and the packed operands are at hand, the fp32 kernel from the raw rows otherwise
+static int table_from_list(const BwdProblem& pr, const int* counter, const int* pairs, uint8_t* table) {
+  const aladin_align_geom* g = pr.g;
+  const int64_t n = (int64_t)g->Bi * g->Bc;
+  const int grid = (int)(n < 2048 ? n : 2048);
+  if (pr.pair16) return launch_pair16<0>(pr, counter, pairs, table, grid, PairHinge{}, SmallFin{}, "bwd_pair_argmax16_kernel");
+  hipLaunchKernelGGL(bwd_pair_argmax_kernel, dim3(grid), dim3(256), 0, pr.st, pr.im.data, pr.im.stride_b, pr.im.stride_r, pr.im.len,
+                     pr.s.data, pr.s.stride_b, pr.s.stride_r, pr.s.len, g->Bc, bwd_Rq(g), bwd_Tq(g), g->D, counter, pairs, table,
+                     table_stride(bwd_Tq(g)), g->x_tail, g->y_tail);
+  return aladin_check_launch("bwd_pair_argmax_kernel");
+}
+
+// ---- stage: table of ALL pairs (ALADIN_BWD_DENSE) -------------------------------------------------------------------------------------
+// (Almost) every pair carries a gradient: the table comes from the forward's own tile kernel in split precision (64 pairs per
+// workgroup sharing their panels).  Leaves in the list the pairs with a word it could not decide, for table_from_list, and in
+// counter[1..3] the statistics of dS the GEMM row step scales by.
+static int table_all_pairs(const BwdProblem& pr, const aladin_align_geom* gs, const DenseWs& dw, const float* dS, int64_t ld_dS, const BwdWs& ws) {
+  const aladin_packed pd = {dw.xm, dw.xe, dw.y, nullptr};
+  if (int rc = aladin_internal_pack(&pr.im, &pr.s, gs, &pd, pr.st)) return rc;
+  if (int rc = aladin_internal_align_argmax(gs, dw.xm, dw.xe, dw.y, dw.E, pr.im.len, pr.s.len, ws.table, table_stride(bwd_Tq(pr.g)), dw.flags, pr.st)) return rc;
+  if (hipMemsetAsync(ws.counter, 0, 256, pr.st) != hipSuccess) { aladin_set_error("align_bwd: memset failed"); return ALADIN_ERR_HIP; }
+  const int64_t n = (int64_t)pr.g->Bi * pr.g->Bc;
+  int grid = (int)((n + 255) / 256); if (grid > 1024) grid = 1024;
+  hipLaunchKernelGGL(bwd_compact_flagged_kernel, dim3(grid), dim3(256), 0, pr.st, dS, ld_dS, pr.g->Bi, pr.g->Bc, dw.flags, ws.counter, ws.pairs);
+  return aladin_check_launch("bwd_compact_flagged_kernel");
+}
+
+// ---- stage: rows by gather ------------------------------------------------------------------------------------------------------------
+// the 24 row kernels: NCH 1..4 x FULL x {exact, P16, P16 + O16}
+template <int NCH>
+static void launch_rows(const BwdProblem& pr, const float* dS, int64_t ld_dS, const float* dST, const float* gscale, const uint8_t* table,
+                        const aladin_set_grad* d_im, const aladin_set_grad* d_s, const PackedRows& pk, bool p16, bool o16) {
+  const aladin_align_geom* g = pr.g;
+  const int64_t rows = (int64_t)g->Bi * g->R + (int64_t)g->Bc * g->T;
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, pr.st, pr.im.data, pr.im.stride_b, pr.im.stride_r, pr.im.len,
+                       pr.s.data, pr.s.stride_b, pr.s.stride_r, pr.s.len, g->Bi, g->Bc, g->R, g->T, g->D, dS, ld_dS, dST, gscale, table,
+                       table_stride(bwd_Tq(g)), d_im->data, d_s->data, g->x_tail, g->y_tail, d_im->stride_b, d_im->stride_r, d_s->stride_b,
+                       d_s->stride_r, pk);
+  };
+  const bool full = g->D == 256 * NCH;
+  if (full) o16 ? go(bwd_rows_kernel<NCH, true, true, true>) : p16 ? go(bwd_rows_kernel<NCH, true, true, false>) : go(bwd_rows_kernel<NCH, true, false, false>);
+  else o16 ? go(bwd_rows_kernel<NCH, false, true, true>) : p16 ? go(bwd_rows_kernel<NCH, false, true, false>) : go(bwd_rows_kernel<NCH, false, false, false>);
+}
+// dST: the transposed copy of dS the fused hinge left in the list region, or nullptr
+static int rows_gather(const BwdProblem& pr, const float* dS, int64_t ld_dS, const float* dST, const float* gscale, const uint8_t* table,
+                       const aladin_set_grad* d_im, const aladin_set_grad* d_s, int flags) {
+  const aladin_align_geom* g = pr.g;
   const bool p16 = (flags & ALADIN_BWD_PARTNERS_FP16) != 0, o16 = (flags & ALADIN_BWD_OWN_ROW_FP16) != 0;
-  if (o16 && !p16) { aladin_set_error("align_bwd: ALADIN_BWD_OWN_ROW_FP16 goes with ALADIN_BWD_PARTNERS_FP16"); return ALADIN_ERR_ARG; }
   PackedRows pk = {nullptr, nullptr, nullptr, 0, 0, 0, 0, nullptr, 0, 0};
-  if (p16) {
-    if (!xm || !y || !rnorm || !g || g->split || (g->rem && !xe) || g->Bi != Bi || g->Bc != Bc || g->R != R || g->T != T || g->D != D) {
-      aladin_set_error("align_bwd: ALADIN_BWD_PARTNERS_FP16 needs the forward's fp16 packed operands (xm, xe, y, rnorm) and their geometry");
-      return ALADIN_ERR_ARG;
-    }
-    pk = PackedRows{(const half_t*)xm, (const half_t*)xe, (const half_t*)y, g->Dp, g->mrows, g->rem, g->trows, rnorm, g->xm_rows, g->xm_rows + g->xe_rows};
+  if (p16) pk = PackedRows{(const half_t*)pr.pk->xm, (const half_t*)pr.pk->xe, (const half_t*)pr.pk->y, g->Dp, g->mrows, g->rem, g->trows, pr.pk->rnorm, g->xm_rows, g->xm_rows + g->xe_rows};
+  switch ((g->D + 255) / 256) {
+    case 1: launch_rows<1>(pr, dS, ld_dS, dST, gscale, table, d_im, d_s, pk, p16, o16); break;
+    case 2: launch_rows<2>(pr, dS, ld_dS, dST, gscale, table, d_im, d_s, pk, p16, o16); break;
+    case 3: launch_rows<3>(pr, dS, ld_dS, dST, gscale, table, d_im, d_s, pk, p16, o16); break;
+    default: launch_rows<4>(pr, dS, ld_dS, dST, gscale, table, d_im, d_s, pk, p16, o16); break;
   }
-#define LAUNCH_ROWS_FP(N, F, P)  do { if (o16) LAUNCH_ROWS_FPO(N, F, P, P); else LAUNCH_ROWS_FPO(N, F, P, false); } while (0)
-#define LAUNCH_ROWS_FPO(N, F, P, O)                                                                                      \
-  hipLaunchKernelGGL((bwd_rows_kernel<N, F, P, O>), dim3(rgrid), dim3(256), 0, st, im, im_sb, im_sr, im_len, s, s_sb, s_st, s_len, \
-                     Bi, Bc, R, T, D, dS, ld_dS, phase == BWD_ROWS ? (const float*)ws.pairs : (const float*)nullptr, gscale, ws.table, tstride, d_im, d_s, x_tail, y_tail, dim_sb, dim_sr, ds_sb, ds_st, pk)
-#define LAUNCH_ROWS_F(N, F) do { if (p16) LAUNCH_ROWS_FP(N, F, true); else LAUNCH_ROWS_FP(N, F, false); } while (0)
-#define LAUNCH_ROWS(N) do { if (D == 256 * (N)) LAUNCH_ROWS_F(N, true); else LAUNCH_ROWS_F(N, false); } while (0)
-  switch (nch) {
-    case 1: LAUNCH_ROWS(1); break;
-    case 2: LAUNCH_ROWS(2); break;
-    case 3: LAUNCH_ROWS(3); break;
-    default: LAUNCH_ROWS(4); break;
-  }
-#undef LAUNCH_ROWS
-#undef LAUNCH_ROWS_F
-#undef LAUNCH_ROWS_FP
-#undef LAUNCH_ROWS_FPO
   return aladin_check_launch("bwd_rows_kernel");
 }
 
-// ---- the exported forms (include/aladin_hip.h, ABI 11) ----------------------------------------------------------------------
-static bool set_ok(const aladin_set* v) { return v && v->data && v->len; }
-static bool grad_ok(const aladin_set_grad* v) { return v && v->data && v->stride_b >= 1 && v->stride_r >= 1; }
+// ---- the exported forms (include/aladin_hip.h, ABI 12) ----------------------------------------------------------------------
 static const char* bwd_common_check(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g) {
   if (!g) return "null geometry";
   if (!set_ok(im) || !set_ok(s)) return "null set";
-  if (g->split) return nullptr;
   return nullptr;
 }
 
@@ -957,11 +910,35 @@ extern "C" int aladin_align_bwd(const aladin_set* im, const aladin_set* s, const
   if (flags & ~(ALADIN_BWD_PARTNERS_FP16 | ALADIN_BWD_OWN_ROW_FP16 | ALADIN_BWD_DENSE | ALADIN_BWD_DENSE_GATHER)) { aladin_set_error("align_bwd: unknown flags %d", flags); return ALADIN_ERR_ARG; }
   if (!grad_ok(d_im) || !grad_ok(d_s)) { aladin_set_error("align_bwd: bad gradient views"); return ALADIN_ERR_ARG; }
   if ((pairs == nullptr) != (pair_count == nullptr)) { aladin_set_error("align_bwd: pairs and pair_count go together"); return ALADIN_ERR_ARG; }
-  const bool have = p && p->xm && p->y;
-  return align_bwd_impl(im->data, im->stride_b, im->stride_r, im->len, s->data, s->stride_b, s->stride_r, s->len, g->Bi, g->Bc, g->R, g->T,
-                        g->D, dS, ld_dS, gscale, have ? p->xm : nullptr, have ? p->xe : nullptr, have ? p->y : nullptr,
-                        have ? p->rnorm : nullptr, have ? g : nullptr, pairs, pair_count, d_im->data, d_s->data, workspace, stream, g->x_tail,
-                        g->y_tail, d_im->stride_b, d_im->stride_r, d_s->stride_b, d_s->stride_r, BWD_ALL, nullptr, flags);
+  const BwdProblem pr = bwd_problem(im, s, g, p, stream);
+  if (int rc = bwd_check(pr, dS, ld_dS, d_im, d_s, workspace, flags)) return rc;
+  const BwdWs ws = bwd_ws(pr, workspace);
+  // the pair list: the undecided pairs of the dense table, the caller's (aladin_hinge_fused built it), or the non-zeros of dS
+  const int* counter = ws.counter;
+  const int* list = ws.pairs;
+  aladin_align_geom gs;
+  DenseWs dw;
+  const bool dense = (flags & ALADIN_BWD_DENSE) && dense_supported(g->Bi, g->Bc, g->R, g->T, g->D, g->x_tail, g->y_tail, &gs);
+  int rc = ALADIN_OK;
+  if (dense) {
+    dense_ws_layout(&gs, (char*)workspace + bwd_base_bytes(g->Bi, g->Bc, g->T), &dw);
+    rc = table_all_pairs(pr, &gs, dw, dS, ld_dS, ws);
+  } else if (pairs) {
+    counter = pair_count; list = pairs;
+  } else {
+    rc = aladin_internal_compact_pairs(dS, ld_dS, g->Bi, g->Bc, ws.counter, ws.pairs, "align_bwd", pr.st);
+  }
+  if (rc) return rc;
+  // (the few listed pairs of a dense table go through the fp16 pair kernel where it covers the shape, the fp32 one otherwise: R' > 33)
+  rc = table_from_list(pr, counter, list, ws.table);
+  if (rc) return rc;
+  if (dense && !(flags & ALADIN_BWD_DENSE_GATHER)) {
+    // every pair carries a gradient: the row step as two MFMA GEMMs over the table (align_bwd_dense.hip)
+    rc = aladin_internal_dense_rows(pr, dS, ld_dS, gscale, ws.table, reinterpret_cast<const unsigned*>(ws.counter) + 1, d_im, d_s,
+                                    (flags & ALADIN_BWD_PARTNERS_FP16) != 0, dw.rows);
+    if (rc != ALADIN_ERR_UNSUPPORTED) return rc;
+  }
+  return rows_gather(pr, dS, ld_dS, nullptr, gscale, ws.table, d_im, d_s, flags);
 }
 
 // workspace of the fused training node: [side-GEMM scratch | hinge statistics | backward base workspace (table, dS^T)]
@@ -978,8 +955,7 @@ static size_t triplet_ws_layout(const aladin_align_geom* g, char* base, TripletW
   return off;
 }
 static bool triplet_supported(const aladin_align_geom* g) {
-  return g->Bi == g->Bc && !g->split && (g->mrows == 32 || g->mrows == 48 || (g->mrows == 64 && g->rem == 0)) && g->tp16 <= 4 &&
-         g->D % 4 == 0 && g->D <= 1024;
+  return g->Bi == g->Bc && !g->split && pair16_covers(g) && g->D % 4 == 0 && g->D <= 1024;
 }
 
 extern "C" size_t aladin_align_triplet_workspace_bytes(const aladin_align_geom* g) {
@@ -987,6 +963,7 @@ extern "C" size_t aladin_align_triplet_workspace_bytes(const aladin_align_geom* 
   return triplet_ws_layout(g, nullptr, nullptr);
 }
 
+// pack -> scores -> hinge table
 extern "C" int aladin_align_triplet_fwd(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, float margin,
                                         const aladin_packed* p, float* S, int64_t ldS, float* loss, float* dS, void* workspace,
                                         void* stream) {
@@ -999,42 +976,36 @@ extern "C" int aladin_align_triplet_fwd(const aladin_set* im, const aladin_set* 
   }
   TripletWs w;
   triplet_ws_layout(g, (char*)workspace, &w);
-  int rc = aladin_internal_pack(im, s, g, p, (hipStream_t)stream);
-  if (rc) return rc;
-  rc = aladin_internal_scores(p->xm, p->xe, p->y, g, w.e, S, ldS, 0, stream);
-  if (rc) return rc;
-  const HingeArgs ha = {S, ldS, margin, loss, dS, w.hinge, nullptr};
-  return align_bwd_impl(im->data, im->stride_b, im->stride_r, im->len, s->data, s->stride_b, s->stride_r, s->len, g->Bi, g->Bc, g->R, g->T,
-                        g->D, nullptr, 0, nullptr, p->xm, p->xe, p->y, p->rnorm, g, nullptr, nullptr, nullptr, nullptr, w.bwd, stream,
-                        g->x_tail, g->y_tail, 0, 0, 0, 0, BWD_HINGE_ARGMAX, &ha);
+  const BwdProblem pr = bwd_problem(im, s, g, p, stream);
+  if (int rc = hinge_table_check(pr, S, ldS, loss, dS, w.hinge, w.bwd, false)) return rc;
+  if (int rc = aladin_internal_pack(im, s, g, p, pr.st)) return rc;
+  if (int rc = aladin_internal_scores(p->xm, p->xe, p->y, g, w.e, S, ldS, 0, stream)) return rc;
+  return table_from_hinge(pr, S, ldS, margin, loss, dS, w.hinge, bwd_ws(pr, w.bwd));
 }
 
-// bwd_ws: the backward base workspace itself (aladin_heads_small_fwd_argmax's caller) or nullptr = inside the triplet workspace
-static int triplet_bwd_impl(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* p, const float* dS,
-                            const float* gscale, const aladin_set_grad* d_im, const aladin_set_grad* d_s, void* bwd_ws, int flags,
-                            void* stream) {
-  if (flags & ~(ALADIN_BWD_PARTNERS_FP16 | ALADIN_BWD_OWN_ROW_FP16)) { aladin_set_error("align_triplet_bwd: unknown flags %d", flags); return ALADIN_ERR_ARG; }
-  if (!grad_ok(d_im) || !grad_ok(d_s) || !dS || !bwd_ws) { aladin_set_error("align_triplet_bwd: null argument"); return ALADIN_ERR_ARG; }
-  return align_bwd_impl(im->data, im->stride_b, im->stride_r, im->len, s->data, s->stride_b, s->stride_r, s->len, g->Bi, g->Bc, g->R, g->T,
-                        g->D, dS, g->Bc, gscale, p ? p->xm : nullptr, p ? p->xe : nullptr, p ? p->y : nullptr, p ? p->rnorm : nullptr, g,
-                        nullptr, nullptr, d_im->data, d_s->data, bwd_ws, stream, g->x_tail, g->y_tail, d_im->stride_b, d_im->stride_r,
-                        d_s->stride_b, d_s->stride_r, BWD_ROWS, nullptr, flags);
-}
-
+// the row step on the table a hinge-table stage left in the workspace (with dS^T in the list region)
 extern "C" int aladin_align_triplet_bwd(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* p,
                                         const float* dS, const float* gscale, const aladin_set_grad* d_im, const aladin_set_grad* d_s,
                                         void* workspace, int flags, void* stream) {
   if (const char* e = bwd_common_check(im, s, g)) { aladin_set_error("align_triplet_bwd: %s", e); return ALADIN_ERR_ARG; }
   if (!workspace) { aladin_set_error("align_triplet_bwd: null workspace"); return ALADIN_ERR_ARG; }
-  void* bwd_ws = workspace;
+  // the backward base workspace itself (aladin_heads_small_fwd_argmax's caller), or the one inside the triplet workspace
+  void* bwd_workspace = workspace;
   if (!(flags & ALADIN_TRIPLET_BWD_BASE_WORKSPACE)) {
     TripletWs w;
     triplet_ws_layout(g, (char*)workspace, &w);
-    bwd_ws = w.bwd;
+    bwd_workspace = w.bwd;
   }
-  return triplet_bwd_impl(im, s, g, p, dS, gscale, d_im, d_s, bwd_ws, flags & ~ALADIN_TRIPLET_BWD_BASE_WORKSPACE, stream);
+  flags &= ~ALADIN_TRIPLET_BWD_BASE_WORKSPACE;
+  if (flags & ~(ALADIN_BWD_PARTNERS_FP16 | ALADIN_BWD_OWN_ROW_FP16)) { aladin_set_error("align_triplet_bwd: unknown flags %d", flags); return ALADIN_ERR_ARG; }
+  if (!grad_ok(d_im) || !grad_ok(d_s) || !dS || !bwd_workspace) { aladin_set_error("align_triplet_bwd: null argument"); return ALADIN_ERR_ARG; }
+  const BwdProblem pr = bwd_problem(im, s, g, p, stream);
+  if (int rc = bwd_check(pr, dS, g->Bc, d_im, d_s, bwd_workspace, flags)) return rc;
+  const BwdWs ws = bwd_ws(pr, bwd_workspace);
+  return rows_gather(pr, dS, g->Bc, (const float*)ws.pairs, gscale, ws.table, d_im, d_s, flags);
 }
 
+// statistics -> hinge table
 extern "C" int aladin_heads_small_fwd_argmax(const float* img, int64_t ld_img, const float* cap, int64_t ld_cap, const float* S,
                                              int64_t ld_S, int D_emb, float margin, int flags, float temperature, float eps,
                                              float w_match, float w_align, float w_dist, float* M, float* terms, float* total,
@@ -1049,14 +1020,11 @@ extern "C" int aladin_heads_small_fwd_argmax(const float* img, int64_t ld_img, c
   if (!(flags & SB_ALIGN_HINGE) || !S || ld_S < B || !dS || !terms || !heads_workspace || D_emb < 1) { aladin_set_error("heads_small_fwd_argmax: the alignment hinge with its dS is what this entry point is for (flags=%d)", flags); return ALADIN_ERR_ARG; }
   const bool need_m = (flags & (SB_MATCH_HINGE | SB_LISTNET)) != 0;
   if (need_m && (!img || !cap || !M || ld_img < D_emb || ld_cap < D_emb)) { aladin_set_error("heads_small_fwd_argmax: missing operand for flags %d", flags); return ALADIN_ERR_ARG; }
+  const BwdProblem pr = bwd_problem(im, s, geom, p, stream);
+  if (int rc = hinge_table_check(pr, S, ld_S, terms, dS, heads_workspace, bwd_workspace, true)) return rc;
   float* st = (float*)heads_workspace;
-  int rc = aladin_internal_heads_small_stats(img, ld_img, cap, ld_cap, S, ld_S, B, D_emb, margin, 1, flags, temperature, eps, M, st,
-                                             nullptr, (hipStream_t)stream);
-  if (rc) return rc;
+  if (int rc = aladin_internal_heads_small_stats(img, ld_img, cap, ld_cap, S, ld_S, B, D_emb, margin, 1, flags, temperature, eps, M, st, nullptr, pr.st)) return rc;
   const SmallFin f = {M, S, ld_S, B, margin, 1, flags, temperature, eps, w_match, w_align, w_dist, st, terms, total, dM_hinge,
                       dM_listnet, dS, nullptr, nullptr, nullptr};
-  const HingeArgs ha = {S, ld_S, margin, terms, dS, heads_workspace, &f};
-  return align_bwd_impl(im->data, im->stride_b, im->stride_r, im->len, s->data, s->stride_b, s->stride_r, s->len, geom->Bi, geom->Bc,
-                        geom->R, geom->T, geom->D, nullptr, 0, nullptr, p->xm, p->xe, p->y, p->rnorm, geom, nullptr, nullptr, nullptr, nullptr,
-                        bwd_workspace, stream, geom->x_tail, geom->y_tail, 0, 0, 0, 0, BWD_HINGE_ARGMAX, &ha);
+  return table_from_small_heads(pr, f, bwd_ws(pr, bwd_workspace));
 }

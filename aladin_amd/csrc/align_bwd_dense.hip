@@ -20,6 +20,7 @@
 // Within each group of 8 k the order is sigma = [0,2,1,3,4,6,5,7] on BOTH operands (free for the transposed copy; on the
 // generated side it makes "flag bytes -> two halfs of a dword" one shift + one and).
 #include "../../include/aladin_hip.h"
+#include "bwd_common.hpp"
 #include "gemm_core.hpp"
 #include <type_traits>
 #pragma clang diagnostic ignored "-Winline-asm"     // m0 is ours around the LDS-DMA asm: no builtin of this file uses it
@@ -514,8 +515,9 @@ struct DrPlan {
   size_t off_xt, off_yt, off_gx, off_gy, bytes;
 };
 
-static bool dr_plan(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail, int parts, DrPlan* p) {
-  p->Rq = R - 1 - x_tail; p->Tq = T - 1 - y_tail;
+static bool dr_plan(const aladin_align_geom* g, int parts, DrPlan* p) {
+  const int Bi = g->Bi, Bc = g->Bc, D = g->D;
+  p->Rq = g->R - 1 - g->x_tail; p->Tq = g->T - 1 - g->y_tail;
   if (p->Rq < 8 || p->Tq < 1 || p->Rq > 96 || D % 4 != 0 || D > 1024) return false;      // Rq >= 8: <= 34 images per 256-row tile (AUX slot)
   p->tstride = (p->Tq + 15) / 16 * 16;
   p->RK = (p->Rq + 7) / 8 * 8;
@@ -540,31 +542,28 @@ static bool dr_plan(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail,
   return true;
 }
 
-size_t aladin_internal_dense_rows_bytes(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail) {
+size_t aladin_internal_dense_rows_bytes(const aladin_align_geom* g) {
   DrPlan p;
-  return dr_plan(Bi, Bc, R, T, D, x_tail, y_tail, 2, &p) ? p.bytes + 256 : 0;
+  return dr_plan(g, 2, &p) ? p.bytes + 256 : 0;
 }
 
 // table: final arg-max table ((Bi * Bc) rows of tstride bytes, NO_GRAD = 255 for clamped / padded words); dsmax: bits of
 // max |dS| (device); scratch: aladin_internal_dense_rows_bytes(...) bytes, 256-aligned.  Returns ALADIN_ERR_UNSUPPORTED when
 // the shape is outside the GEMM form (the caller then runs bwd_rows_kernel).
-int aladin_internal_dense_rows(const float* im, int64_t im_sb, int64_t im_sr, const int32_t* im_len, const float* s, int64_t s_sb,
-                               int64_t s_st, const int32_t* s_len, int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail,
-                               const float* dS, int64_t ld_dS, const float* gscale, const uint8_t* table, const unsigned* dsmax,
-                               float* d_im, float* d_s, int64_t dim_sb, int64_t dim_sr, int64_t ds_sb, int64_t ds_st, int fp16_only,
-                               void* scratch, hipStream_t st) {
-  const int parts = fp16_only ? 1 : 2;
+int aladin_internal_dense_rows(const BwdProblem& pr, const float* dS, int64_t ld_dS, const float* gscale, const uint8_t* table,
+                               const unsigned* dsmax, const aladin_set_grad* d_im, const aladin_set_grad* d_s, int fp16_only, void* scratch) {
+  const aladin_align_geom* g = pr.g;
+  const aladin_set &im = pr.im, &s = pr.s;
+  const int Bi = g->Bi, Bc = g->Bc, D = g->D, parts = fp16_only ? 1 : 2;
   DrPlan p;
-  if (!dr_plan(Bi, Bc, R, T, D, x_tail, y_tail, 2, &p)) return ALADIN_ERR_UNSUPPORTED;
-  if ((im_sb | im_sr | s_sb | s_st) % 4 != 0 || ((uintptr_t)im & 15) || ((uintptr_t)s & 15) || (int64_t)Bi * ld_dS >= (1ll << 31)) return ALADIN_ERR_UNSUPPORTED;
+  if (!dr_plan(g, 2, &p)) return ALADIN_ERR_UNSUPPORTED;
+  if ((im.stride_b | im.stride_r | s.stride_b | s.stride_r) % 4 != 0 || ((uintptr_t)im.data & 15) || ((uintptr_t)s.data & 15) || (int64_t)Bi * ld_dS >= (1ll << 31)) return ALADIN_ERR_UNSUPPORTED;
   char* base = (char*)scratch;
-  half_t* xt = (half_t*)(base + p.off_xt);
-  half_t* yt = (half_t*)(base + p.off_yt);
-  float* gx = (float*)(base + p.off_gx);
-  float* gy = (float*)(base + p.off_gy);
+  half_t *xt = (half_t*)(base + p.off_xt), *yt = (half_t*)(base + p.off_yt);
+  float *gx = (float*)(base + p.off_gx), *gy = (float*)(base + p.off_gy);
 
-  hipLaunchKernelGGL(dense_transpose_kernel, dim3((unsigned)(p.KX / 32)), dim3(256), 0, st, DrSet{im, im_sb, im_sr, Bi, p.RK, p.Rq}, D, p.Dq, p.KX, xt, parts);
-  hipLaunchKernelGGL(dense_transpose_kernel, dim3((unsigned)(p.KY / 32)), dim3(256), 0, st, DrSet{s, s_sb, s_st, Bc, p.tstride, p.Tq}, D, p.Dq, p.KY, yt, parts);
+  hipLaunchKernelGGL(dense_transpose_kernel, dim3((unsigned)(p.KX / 32)), dim3(256), 0, pr.st, DrSet{im.data, im.stride_b, im.stride_r, Bi, p.RK, p.Rq}, D, p.Dq, p.KX, xt, parts);
+  hipLaunchKernelGGL(dense_transpose_kernel, dim3((unsigned)(p.KY / 32)), dim3(256), 0, pr.st, DrSet{s.data, s.stride_b, s.stride_r, Bc, p.tstride, p.Tq}, D, p.Dq, p.KY, yt, parts);
   if (int rc = aladin_check_launch("dense_transpose_kernel")) return rc;
 
   DrArgs ax = {table, p.tstride, dS, ld_dS, dsmax, yt, p.KY, (int64_t)p.Dq * p.KY, gx, (int64_t)p.MX * D,
@@ -577,16 +576,17 @@ int aladin_internal_dense_rows(const float* im, int64_t im_sb, int64_t im_sr, co
     constexpr int lds = 2 * ((NP) == 1 ? 1 : 2) * DR_BN * 128 + DR_AUX_SLOTS * DR_AUX_BYTES + 32768;                                                           \
     static unsigned long long lds_reserved = 0;                                                                         \
     if (int rc = aladin_reserve_lds((const void*)kern, lds, &lds_reserved, "dense_rows_gemm")) return rc;               \
-    hipLaunchKernelGGL(kern, dim3((unsigned)((ARGS).n_mblk * (ARGS).n_nblk * (ARGS).SK)), dim3(DR_THREADS), lds, st, ARGS); \
+    hipLaunchKernelGGL(kern, dim3((unsigned)((ARGS).n_mblk * (ARGS).n_nblk * (ARGS).SK)), dim3(DR_THREADS), lds, pr.st, ARGS); \
   } while (0)
   if (fp16_only) { DR_LAUNCH(0, 1, ax); DR_LAUNCH(1, 1, ay); }
   else { DR_LAUNCH(0, 3, ax); DR_LAUNCH(1, 3, ay); }
 #undef DR_LAUNCH
   if (int rc = aladin_check_launch("dense_rows_gemm_kernel")) return rc;
 
-  DrFinish f = {im, im_sb, im_sr, im_len, s, s_sb, s_st, s_len, Bi, Bc, R, T, D, x_tail, y_tail, p.tstride,
-                gx, (int64_t)p.MX * D, p.SKX, gy, (int64_t)p.MY * D, p.SKY, dsmax, gscale, d_im, d_s, dim_sb, dim_sr, ds_sb, ds_st};
-  const int64_t rows = (int64_t)Bi * R + (int64_t)Bc * T;
-  hipLaunchKernelGGL(dense_rows_finish_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, f);
+  DrFinish f = {im.data, im.stride_b, im.stride_r, im.len, s.data, s.stride_b, s.stride_r, s.len, Bi, Bc, g->R, g->T, D, g->x_tail, g->y_tail,
+                p.tstride, gx, (int64_t)p.MX * D, p.SKX, gy, (int64_t)p.MY * D, p.SKY, dsmax, gscale, d_im->data, d_s->data,
+                d_im->stride_b, d_im->stride_r, d_s->stride_b, d_s->stride_r};
+  const int64_t rows = (int64_t)Bi * g->R + (int64_t)Bc * g->T;
+  hipLaunchKernelGGL(dense_rows_finish_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, pr.st, f);
   return aladin_check_launch("dense_rows_finish_kernel");
 }

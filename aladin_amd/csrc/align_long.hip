@@ -13,7 +13,7 @@
 //                over any number of row tiles is more in-lane max steps.  The per-tile word sums meet in LDS and every
 //                score is the sum of its caption's tiles in a fixed order: no atomics, bitwise reproducible.  Split
 //                precision is the same kernel over the three-segment K of the split packers.
-// backward       1. compact the non-zero pairs of dS;
+// backward       1. compact the non-zero pairs of dS (the compaction of align_bwd.hip: aladin_internal_compact_pairs);
 //                2. per pair the arg-max region of every word in fp32 (v_mfma_f32_32x32x2_f32 from the raw rows, as the
 //                   fallback of align_bwd.hip) over 32-word windows and 32-region tiles with a running arg-max: the recorded
 //                   winner is the fp32 winner for every word, with no fp16 screening to re-decide.  16-bit entries
@@ -25,7 +25,7 @@
 #include <string.h>
 
 #include "../../include/aladin_hip.h"
-#include "common.hpp"
+#include "bwd_common.hpp"
 
 #define LONG_MAX_POS 512
 #define LONG_NO_GRAD 0xFFFFu
@@ -158,43 +158,11 @@ extern "C" int aladin_align_long_scores(const aladin_packed* p, const aladin_ali
 // ------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------
-struct LongWs {
-  int* counter;      // [64] ints, [0] = number of listed pairs
-  int* pairs;        // Bi*Bc
-  uint16_t* table;   // Bi*Bc rows of round_up(Tq, 16) entries
-};
-static inline int long_tstride(int Tq) { return (Tq + 15) / 16 * 16; }
-
-static size_t long_ws_layout(const aladin_align_geom* g, char* base, LongWs* ws) {
-  size_t off = 0;
-  if (ws) ws->counter = (int*)(base + off);
-  off += 256;
-  if (ws) ws->pairs = (int*)(base + off);
-  off += ((size_t)g->Bi * g->Bc * 4 + 255) / 256 * 256;
-  if (ws) ws->table = (uint16_t*)(base + off);
-  off += ((size_t)g->Bi * g->Bc * long_tstride(g->Tq) * 2 + 255) / 256 * 256;
-  return off;
-}
+using LongWs = PairWs<uint16_t>;     // the table: Bi*Bc rows of table_stride(Tq) 16-bit entries
 
 extern "C" size_t aladin_align_long_bwd_workspace_bytes(const aladin_align_geom* g) {
   if (!long_geom_ok(g)) return 0;
-  return long_ws_layout(g, nullptr, nullptr);
-}
-
-__global__ __launch_bounds__(256) void long_compact_kernel(const float* __restrict__ dS, int64_t ld, int Bi, int Bc,
-                                                           int* __restrict__ counter, int* __restrict__ pairs) {
-  const int64_t n = (int64_t)Bi * Bc;
-  for (int64_t e0 = (int64_t)blockIdx.x * blockDim.x; e0 < n; e0 += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t e = e0 + threadIdx.x;
-    bool nz = false;
-    if (e < n) nz = dS[(e / Bc) * ld + (e % Bc)] != 0.f;
-    const unsigned long long mask = __ballot(nz);
-    const int lane = threadIdx.x & 63;
-    int base = 0;
-    if (lane == 0 && mask) base = atomicAdd(counter, __popcll(mask));      // list order is irrelevant: one workgroup per pair
-    base = __shfl(base, 0, 64);
-    if (nz) pairs[base + __popcll(mask & ((1ull << lane) - 1))] = (int)e;
-  }
+  return pair_ws_layout<uint16_t>(g->Bi, g->Bc, g->Tq, nullptr, nullptr);
 }
 
 // (value, index) of the larger; the smaller index on a tie (the first maximum, as a scan in region order finds it)
@@ -261,9 +229,8 @@ __global__ __launch_bounds__(256) void long_pair_argmax_kernel(
         // accumulator row = (r&3) + 8*(r>>2) + 4*h, column l5 = word; the caption norm is a positive column factor
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-          const float n2 = __shfl(ss, row, 64);
-          const float v = acc[r] * (1.0f / fmaxf(sqrtf(n2), 1e-12f));
+          const int row = cos_tile_row(r, h);
+          const float v = acc[r] * cos_tile_inv_norm(ss, row);
           const int rg = tm * 32 + row;
           if (rg < Li) argmax_take(best, arg, v, rg);
         }
@@ -285,46 +252,18 @@ __global__ __launch_bounds__(256) void long_pair_argmax_kernel(
   }
 }
 
-template <int NCH>
-__device__ __forceinline__ void long_load_row(const float* __restrict__ p, int D, int lane, float4 (&v)[NCH]) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int col = lane * 4 + 256 * c;
-    v[c] = col < D ? *reinterpret_cast<const float4*>(p + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-template <int NCH>
-__device__ __forceinline__ void long_load_row_h(const half_t* __restrict__ p, int D, int lane, float4 (&v)[NCH]) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int col = lane * 4 + 256 * c;
-    if (col < D) {
-      const uint2 raw = *reinterpret_cast<const uint2*>(p + col);
-      const half_t* hh = reinterpret_cast<const half_t*>(&raw);
-      v[c] = make_float4((float)hh[0], (float)hh[1], (float)hh[2], (float)hh[3]);
-    } else v[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-template <int NCH>
-__device__ __forceinline__ void long_axpy(float f, const float4 (&v)[NCH], float4 (&acc)[NCH]) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) { acc[c].x += f * v[c].x; acc[c].y += f * v[c].y; acc[c].z += f * v[c].z; acc[c].w += f * v[c].w; }
-}
 // partner row: a raw fp32 row normalised here, or (P16) the forward's packed unit vector
 template <int NCH, bool P16>
 __device__ __forceinline__ void long_gather(const float* __restrict__ raw, const half_t* __restrict__ packed, float g, int D, int lane,
                                             float4 (&acc)[NCH]) {
   float4 v[NCH];
   if constexpr (P16) {
-    long_load_row_h<NCH>(packed, D, lane, v);
-    long_axpy<NCH>(g, v, acc);
+    load_row_h<NCH, false>(packed, D, lane, v);
+    axpy_row<NCH>(g, v, acc);
   } else {
-    long_load_row<NCH>(raw, D, lane, v);
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) ss += v[c].x * v[c].x + v[c].y * v[c].y + v[c].z * v[c].z + v[c].w * v[c].w;
-    ss = wave_sum(ss);
-    long_axpy<NCH>(g / fmaxf(sqrtf(ss), 1e-12f), v, acc);
+    load_row<NCH, false>(raw, D, lane, v);
+    const float ss = wave_sum(row_sumsq<NCH>(v));
+    axpy_row<NCH>(g / fmaxf(sqrtf(ss), 1e-12f), v, acc);
   }
 }
 
@@ -365,9 +304,9 @@ __global__ __launch_bounds__(256) void long_rows_kernel(
   float own_inv = 0.f;
   if (idx >= 0 && idx < L) {
     if constexpr (O16) {
-      if (is_img) { long_load_row_h<NCH>(pk.xm + ((int64_t)own_b * pk.mrows + idx) * pk.Dp, D, lane, xv); own_inv = pk.rnorm[(int64_t)own_b * pk.mrows + idx]; }
-      else { long_load_row_h<NCH>(pk.y + ((int64_t)own_b * pk.trows + idx) * pk.Dp, D, lane, xv); own_inv = pk.rnorm[pk.y_row0 + (int64_t)own_b * pk.trows + idx]; }
-    } else long_load_row<NCH>(xrow, D, lane, xv);
+      if (is_img) { load_row_h<NCH, false>(pk.xm + ((int64_t)own_b * pk.mrows + idx) * pk.Dp, D, lane, xv); own_inv = pk.rnorm[(int64_t)own_b * pk.mrows + idx]; }
+      else { load_row_h<NCH, false>(pk.y + ((int64_t)own_b * pk.trows + idx) * pk.Dp, D, lane, xv); own_inv = pk.rnorm[pk.y_row0 + (int64_t)own_b * pk.trows + idx]; }
+    } else load_row<NCH, false>(xrow, D, lane, xv);
     const float gs = gscale ? *gscale : 1.f;
     const int nb = is_img ? Bc : Bi;
     for (int p0 = 0; p0 < nb; p0 += 64) {
@@ -451,9 +390,6 @@ static int launch_long_rows(bool p16, bool o16, dim3 grid, hipStream_t st, const
   return aladin_check_launch("long_rows_kernel");
 }
 
-static bool set_ok(const aladin_set* v) { return v && v->data && v->len; }
-static bool grad_ok(const aladin_set_grad* v) { return v && v->data && v->stride_b >= 1 && v->stride_r >= 1; }
-
 extern "C" int aladin_align_long_bwd(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* p,
                                      const float* dS, int64_t ld_dS, const float* gscale, const aladin_set_grad* d_im,
                                      const aladin_set_grad* d_s, void* workspace, int flags, void* stream) {
@@ -468,13 +404,10 @@ extern "C" int aladin_align_long_bwd(const aladin_set* im, const aladin_set* s, 
   if (ld_dS < g->Bc) { aladin_set_error("align_long_bwd: ld_dS %lld < Bc %d", (long long)ld_dS, g->Bc); return ALADIN_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   LongWs ws;
-  long_ws_layout(g, (char*)workspace, &ws);
-  const int tstride = long_tstride(g->Tq);
-  if (hipMemsetAsync(ws.counter, 0, 256, st) != hipSuccess) { aladin_set_error("align_long_bwd: hipMemsetAsync failed"); return ALADIN_ERR_HIP; }
+  pair_ws_layout(g->Bi, g->Bc, g->Tq, (char*)workspace, &ws);
+  const int tstride = table_stride(g->Tq);
+  if (int rc = aladin_internal_compact_pairs(dS, ld_dS, g->Bi, g->Bc, ws.counter, ws.pairs, "align_long_bwd", st)) return rc;     // list order is irrelevant: one workgroup per pair
   const int64_t n = (int64_t)g->Bi * g->Bc;
-  const int cblocks = (int)(((n + 255) / 256) < 1024 ? (n + 255) / 256 : 1024);
-  hipLaunchKernelGGL(long_compact_kernel, dim3(cblocks), dim3(256), 0, st, dS, ld_dS, g->Bi, g->Bc, ws.counter, ws.pairs);
-  if (int rc = aladin_check_launch("long_compact_kernel")) return rc;
   const int pblocks = (int)(n < 2048 ? n : 2048);
   hipLaunchKernelGGL(long_pair_argmax_kernel, dim3(pblocks), dim3(256), 0, st, im->data, im->stride_b, im->stride_r, im->len, s->data,
                      s->stride_b, s->stride_r, s->len, g->Bc, g->Rq, g->Tq, g->D, ws.counter, ws.pairs, ws.table, tstride, g->x_tail,

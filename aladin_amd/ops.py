@@ -16,7 +16,8 @@ from .ops_losses import _DotScores, _hinge_raw        # (the other names of ops_
 
 def _pair_kernel_covers(geom):
     """Shapes the fp16 pair kernel of the backward covers (csrc/align_bwd.hip: bwd_pair_argmax16_kernel): a 64-row block per
-    pair = the image's 32 / 48 main rows + a window on its side rows, or its 64 main rows; at most 64 padded words."""
+    pair = the image's 32 / 48 main rows + a window on its side rows, or its 64 main rows; at most 64 padded words.
+    The Python mirror of pair16_covers() in csrc/align_bwd.hip."""
     return (geom.mrows in (32, 48) or (geom.mrows == 64 and geom.rem == 0)) and geom.tp16 <= 4
 
 
@@ -69,13 +70,19 @@ def set_backward_precision(mode):
     return old
 
 
+def _bwd_precision_bits(have_rnorm):
+    """The set_backward_precision() mode as ALADIN_BWD_* flag bits, for a backward that holds the forward's fp16 packed operands;
+    have_rnorm: their inverse norms are there too (without them only the exact row step can run)."""
+    if _BWD_PARTNERS[0] != 'fp16' or not have_rnorm:
+        return 0
+    return _lib.BWD_PARTNERS_FP16 | (_lib.BWD_OWN_ROW_FP16 if _BWD_OWN_ROW_FP16[0] else 0)
+
+
 def _bwd_flags(packed):
     """flags word of the backward entry points for this problem: ALADIN_BWD_PARTNERS_FP16 when the setting asks for it and the
     forward's packed operands WITH their inverse norms are at hand (a 5-tuple from _align_forward / pack_sets)."""
-    if _BWD_PARTNERS[0] == 'fp16' and packed is not None and len(packed) > 4 and packed[1] is not None and packed[3] is not None \
-            and packed[4] is not None and not packed[0].split:
-        return _lib.BWD_PARTNERS_FP16 | (_lib.BWD_OWN_ROW_FP16 if _BWD_OWN_ROW_FP16[0] else 0)
-    return 0
+    return _bwd_precision_bits(packed is not None and len(packed) > 4 and packed[1] is not None and packed[3] is not None
+                               and packed[4] is not None and not packed[0].split)
 
 
 def _precision_code(precision):
@@ -451,9 +458,7 @@ def _triplet_backward(im, s, im_len_t, s_len_t, geom, pk, dS, ws, gscale, base_w
     left in `ws`.  pk: struct aladin_packed of the forward's operands (with rnorm for the fp16 row step)."""
     lib = _lib.load()
     d_im, d_s = _grad_like(im), _grad_like(s)
-    flags = _lib.BWD_PARTNERS_FP16 if (_BWD_PARTNERS[0] == 'fp16' and pk.rnorm) else 0
-    if flags and _BWD_OWN_ROW_FP16[0]:
-        flags |= _lib.BWD_OWN_ROW_FP16
+    flags = _bwd_precision_bits(bool(pk.rnorm))
     if base_workspace:
         flags |= _lib.TRIPLET_BWD_BASE_WORKSPACE
     vi, vs, gi, gs = _set_view(im, im_len_t), _set_view(s, s_len_t), _grad_view(d_im), _grad_view(d_s)
