@@ -210,8 +210,8 @@ def rank_backward_block(im_all, il_all_t, s_local, s_len_t, dS_full, rank, g_glo
     from . import ops
     B = s_local.shape[0]
     dS_blk = dS_full[:, rank * B:(rank + 1) * B].contiguous()
-    packed = (g_glob, xm_all, xe_all, y) if rnorm is None else (g_glob, xm_all, xe_all, y, rnorm)
-    return ops._align_backward(im_all, s_local, il_all_t, s_len_t, dS_blk, gscale=gscale, packed=packed)
+    return ops._align_backward(im_all, s_local, il_all_t, s_len_t, dS_blk, gscale=gscale,
+                               packed=ops.Packed(g_glob, xm_all, xe_all, y, rnorm))
 
 
 class _PinnedPool:

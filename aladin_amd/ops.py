@@ -5,6 +5,7 @@ Every function requires float32 tensors on an AMD GPU ("cuda" device of PyTorch-
 otherwise; there is no CPU or eager-PyTorch fallback.
 """
 import ctypes as C
+from typing import NamedTuple
 
 import torch
 
@@ -78,11 +79,44 @@ def _bwd_precision_bits(have_rnorm):
     return _lib.BWD_PARTNERS_FP16 | (_lib.BWD_OWN_ROW_FP16 if _BWD_OWN_ROW_FP16[0] else 0)
 
 
+class Packed(NamedTuple):
+    """The fp16 MFMA operands of one problem as tensors, with its layout: what pack_sets / _align_forward return and the score
+    and backward functions take as `packed` (they also accept a plain tuple (geom, xm, xe, y[, rnorm]) and make this of it); an
+    operand that is not there is None."""
+    geom: object
+    xm: object
+    xe: object
+    y: object
+    rnorm: object = None        # inverse norms of the [xm | xe | y] rows: None without norms or with split operands
+
+    @classmethod
+    def from_buf(cls, buf, geom, offs):
+        """Tensor views of the one-allocation operand buffer of _triplet_forward (offs: byte offsets of xe, y, rnorm)."""
+        return cls(geom, buf[:geom.xm_bytes].view(torch.float16),
+                   buf[offs[0]:offs[0] + max(int(geom.xe_bytes), 16)].view(torch.float16),
+                   buf[offs[1]:offs[1] + geom.y_bytes].view(torch.float16),
+                   buf[offs[2]:offs[2] + geom.rnorm_bytes].view(torch.float32))
+
+    def operands(self):
+        return self.xm, self.xe, self.y, self.rnorm
+
+    def struct(self):
+        """struct aladin_packed of the operands that are there."""
+        return _lib.Packed(*(t.data_ptr() if t is not None else None for t in self.operands()))
+
+    def at_hand(self):
+        """Do the forward's operands reach the backward (or does it recompute them in fp32)?"""
+        return self.xm is not None
+
+    def fp16_rows(self):
+        """Can the backward's row step take its unit vectors from these operands?  Only with their inverse norms."""
+        return self.xm is not None and self.y is not None and self.rnorm is not None and not self.geom.split
+
+
 def _bwd_flags(packed):
     """flags word of the backward entry points for this problem: ALADIN_BWD_PARTNERS_FP16 when the setting asks for it and the
-    forward's packed operands WITH their inverse norms are at hand (a 5-tuple from _align_forward / pack_sets)."""
-    return _bwd_precision_bits(packed is not None and len(packed) > 4 and packed[1] is not None and packed[3] is not None
-                               and packed[4] is not None and not packed[0].split)
+    forward's packed operands WITH their inverse norms are at hand."""
+    return _bwd_precision_bits(packed is not None and Packed(*packed).fp16_rows())
 
 
 def _precision_code(precision):
@@ -93,18 +127,26 @@ def _precision_code(precision):
     raise ValueError("aladin_amd: precision must be 'fp16' or 'split', got %r" % (precision,))
 
 
-def align_geometry(Bi, Bc, R, T, D, x_tail=0, y_tail=2, precision=None):
-    """Packed layout for a (max-side set Bi x R) x (sum-side set Bc x T) problem; the tails are the
-    trailing positions each set drops (images 0, captions 2 -- reference alad/loss.py:87-90)."""
+def _geometry(long, Bi, Bc, R, T, D, x_tail, y_tail, precision):
+    """The cached struct aladin_align_geom of a problem, from aladin_align_geometry or (long) aladin_align_long_geometry."""
     prec = _precision_code(precision)
     key = (Bi, Bc, R, T, D, x_tail, y_tail, prec)
+    if long:
+        key = ('long',) + key
     g = _GEOM_CACHE.get(key)
     if g is None:
-        g = _lib.AlignGeom()
-        _lib.check(_lib.load().aladin_align_geometry(Bi, Bc, R, T, D, x_tail, y_tail, prec, C.byref(g)), 'align_geometry')
+        g = LongGeom() if long else _lib.AlignGeom()
+        name = 'align_long_geometry' if long else 'align_geometry'
+        _lib.check(getattr(_lib.load(), 'aladin_' + name)(Bi, Bc, R, T, D, x_tail, y_tail, prec, C.byref(g)), name)
         if len(_GEOM_CACHE) < 1024:
             _GEOM_CACHE[key] = g
     return g
+
+
+def align_geometry(Bi, Bc, R, T, D, x_tail=0, y_tail=2, precision=None):
+    """Packed layout for a (max-side set Bi x R) x (sum-side set Bc x T) problem; the tails are the
+    trailing positions each set drops (images 0, captions 2 -- reference alad/loss.py:87-90)."""
+    return _geometry(False, Bi, Bc, R, T, D, x_tail, y_tail, precision)
 
 
 # Long sets: past the tile classes of aladin_align_geometry (more than 96 scored positions on either side) the packed layout,
@@ -126,15 +168,7 @@ def is_long(R, T, x_tail=0, y_tail=2):
 
 def long_geometry(Bi, Bc, R, T, D, x_tail=0, y_tail=2, precision=None):
     """Packed layout of the long-set kernels (aladin_align_long_geometry) for up to LONG_POSITIONS positions per set."""
-    prec = _precision_code(precision)
-    key = ('long', Bi, Bc, R, T, D, x_tail, y_tail, prec)
-    g = _GEOM_CACHE.get(key)
-    if g is None:
-        g = LongGeom()
-        _lib.check(_lib.load().aladin_align_long_geometry(Bi, Bc, R, T, D, x_tail, y_tail, prec, C.byref(g)), 'align_long_geometry')
-        if len(_GEOM_CACHE) < 1024:
-            _GEOM_CACHE[key] = g
-    return g
+    return _geometry(True, Bi, Bc, R, T, D, x_tail, y_tail, precision)
 
 
 def _scoring_geometry(Bi, Bc, R, T, D, x_tail, y_tail, precision=None):
@@ -156,17 +190,6 @@ def _grad_view(t):
     return _lib.GradView(t.data_ptr(), t.stride(0), t.stride(1))
 
 
-def _packed_struct(xm, xe, y, rnorm=None):
-    return _lib.Packed(xm.data_ptr() if xm is not None else None, xe.data_ptr() if xe is not None else None,
-                       y.data_ptr() if y is not None else None, rnorm.data_ptr() if rnorm is not None else None)
-
-
-def _rnorm_views(rnorm, geom):
-    """(image part, caption part) of the inverse-norm buffer [xm rows | xe rows | y rows]."""
-    n_img = int(geom.xm_rows + geom.xe_rows)
-    return rnorm[:n_img], rnorm[n_img:]
-
-
 def pack_images(im, im_len_t, geom, rnorm=None, out=None):
     """(xm, xe): L2-normalised, sliced, length-masked fp16 MFMA operands of the image sets.  rnorm (optional float32 tensor of
     geom.rnorm_bytes / 4 elements): receives the image rows' inverse norms in its [xm | xe] part.  out = (xm, xe): write into
@@ -178,7 +201,7 @@ def pack_images(im, im_len_t, geom, rnorm=None, out=None):
     else:
         xm = torch.empty(geom.xm_bytes // 2, dtype=torch.float16, device=im.device)
         xe = torch.empty(max(geom.xe_bytes // 2, 8), dtype=torch.float16, device=im.device)
-    v, pk = _set_view(im, im_len_t), _packed_struct(xm, xe, None, rnorm)
+    v, pk = _set_view(im, im_len_t), Packed(geom, xm, xe, None, rnorm).struct()
     _lib.check(lib.aladin_align_pack(C.byref(v), None, C.byref(geom), C.byref(pk), _stream()), 'align_pack(images)')
     return xm, xe
 
@@ -187,7 +210,7 @@ def pack_captions(s, s_len_t, geom, rnorm=None):
     lib = _lib.load()
     s = _rows_inner_contig(s)
     y = torch.empty(geom.y_bytes // 2, dtype=torch.float16, device=s.device)
-    v, pk = _set_view(s, s_len_t), _packed_struct(None, None, y, rnorm)
+    v, pk = _set_view(s, s_len_t), Packed(geom, None, None, y, rnorm).struct()
     _lib.check(lib.aladin_align_pack(None, C.byref(v), C.byref(geom), C.byref(pk), _stream()), 'align_pack(captions)')
     return y
 
@@ -195,7 +218,7 @@ def pack_captions(s, s_len_t, geom, rnorm=None):
 def scores_from_packed(xm, xe, y, geom, out=None, e_scratch=None, reuse_side=False):
     lib = _lib.load()
     S = out if out is not None else torch.empty((geom.Bi, geom.Bc), dtype=torch.float32, device=xm.device)
-    pk = _packed_struct(xm, xe, y)
+    pk = Packed(geom, xm, xe, y).struct()
     if isinstance(geom, LongGeom):
         _lib.check(lib.aladin_align_long_scores(C.byref(pk), C.byref(geom), _ptr(S), S.stride(0), _stream()), 'align_long_scores')
         return S
@@ -231,28 +254,29 @@ def _check_backward_supported(im, s, x_tail, y_tail):
 
 
 def pack_sets(im, s, im_len_t, s_len_t, geom, norms=True):
-    """Both sets in one launch -> (geom, xm, xe, y, rnorm): the `packed` tuple the score and backward functions take
+    """Both sets in one launch -> Packed(geom, xm, xe, y, rnorm), the `packed` the score and backward functions take
     (rnorm None when norms=False or the operands are split)."""
     dev = im.device
     xm = torch.empty(geom.xm_bytes // 2, dtype=torch.float16, device=dev)
     xe = torch.empty(max(geom.xe_bytes // 2, 8), dtype=torch.float16, device=dev)
     y = torch.empty(geom.y_bytes // 2, dtype=torch.float16, device=dev)
     rnorm = torch.empty(geom.rnorm_bytes // 4, dtype=torch.float32, device=dev) if norms and not geom.split else None
-    vi, vs, pk = _set_view(im, im_len_t), _set_view(s, s_len_t), _packed_struct(xm, xe, y, rnorm)
+    packed = Packed(geom, xm, xe, y, rnorm)
+    vi, vs, pk = _set_view(im, im_len_t), _set_view(s, s_len_t), packed.struct()
     _lib.check(_lib.load().aladin_align_pack(C.byref(vi), C.byref(vs), C.byref(geom), C.byref(pk), _stream()), 'align_pack')
-    return geom, xm, xe, y, rnorm
+    return packed
 
 
 def _align_forward(im, s, im_len_t, s_len_t, x_tail=0, y_tail=2, precision=None, norms=True):
-    """-> (S, packed) where packed = (geom, xm, xe, y, rnorm) is kept for the backward pass.
+    """-> (S, packed) where packed = Packed(geom, xm, xe, y, rnorm) is kept for the backward pass.
     `im` is the max-side set, `s` the sum-side set (images / captions for 'MrSw')."""
     Bi, R, D = im.shape
     Bc, T, D2 = s.shape
     if D != D2:
         raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (D, D2))
     geom = _scoring_geometry(Bi, Bc, R, T, D, x_tail, y_tail, precision)
-    packed = pack_sets(_rows_inner_contig(im), _rows_inner_contig(s), im_len_t, s_len_t, geom, norms=norms)
-    return scores_from_packed(packed[1], packed[2], packed[3], geom), packed
+    packed = Packed(*pack_sets(_rows_inner_contig(im), _rows_inner_contig(s), im_len_t, s_len_t, geom, norms=norms))
+    return scores_from_packed(packed.xm, packed.xe, packed.y, geom), packed
 
 
 def _grad_like(x):
@@ -344,11 +368,10 @@ def _gemm_rows_pay(fill, Rq):
     return fill >= min(0.7, max(0.35, 0.42 + 0.08 * (Rq - 33) / 17.0))
 
 
-_FILL_HINT = [None]          # set by the wrappers just before .apply(), read by the node's forward (same thread, same call)
-
-
 def _align_backward(im, s, im_len_t, s_len_t, dS, gscale=None, packed=None, pairs=None, x_tails=(0, 2), dense=False, fill=None):
-    """aladin_align_bwd.  packed: (geom, xm, xe, y[, rnorm]) of the forward (None: the exact fp32 recompute).
+    """aladin_align_bwd, or for a long-set problem aladin_align_long_bwd (the pair-list path for any dS, a dense one included).
+    packed: Packed / (geom, xm, xe, y[, rnorm]) of the forward (None: the exact fp32 recompute); with its operands at hand the row
+    step's unit vectors are as set_backward_precision() says.
     dense: the caller knows that (almost) every pair carries a gradient (sum-of-violations hinge, a gradient on S):
     ALADIN_BWD_DENSE -- the arg-max table of all pairs from the split-precision tile kernel instead of one workgroup per pair."""
     lib = _lib.load()
@@ -358,46 +381,32 @@ def _align_backward(im, s, im_len_t, s_len_t, dS, gscale=None, packed=None, pair
     ld_dS = dS.shape[1]            # (not stride(0): a contiguous (1, n) view may report any leading stride)
     Bi, R, D = im.shape
     Bc, T, _ = s.shape
-    if isinstance(packed[0] if packed is not None else None, LongGeom) or (packed is None and is_long(R, T, *x_tails)):
-        return _align_backward_long(im, s, im_len_t, s_len_t, dS, ld_dS, gscale, packed, x_tails)
-    d_im, d_s = _grad_like(im), _grad_like(s)
-    have = packed is not None and packed[1] is not None
-    dense_flag = _lib.BWD_DENSE if (dense and DENSE_BACKWARD and have and Bi * Bc >= DENSE_MIN_PAIRS) else 0
-    if dense_flag and not (DENSE_ROWS_GEMM and _gemm_rows_pay(fill, R - 1 - packed[0].x_tail)):
+    packed = Packed(*packed) if packed is not None else None
+    have = packed is not None and packed.at_hand()
+    long = isinstance(packed.geom, LongGeom) if packed is not None else is_long(R, T, *x_tails)
+    if packed is not None:
+        geom = packed.geom
+    elif not long and x_tails != (0, 2):
+        raise NotImplementedError('aladin_amd: the stand-alone backward entry point is the image/caption form')
+    else:
+        geom = _geometry(long, Bi, Bc, R, T, D, *x_tails, None)
+    dense_flag = _lib.BWD_DENSE if (dense and not long and DENSE_BACKWARD and have and Bi * Bc >= DENSE_MIN_PAIRS) else 0
+    if dense_flag and not (DENSE_ROWS_GEMM and _gemm_rows_pay(fill, R - 1 - geom.x_tail)):
         dense_flag |= _lib.BWD_DENSE_GATHER
     _LAST_BWD_FLAGS[0] = dense_flag                      # which path the last backward took (tests)
-    if packed is None:
-        if x_tails != (0, 2):
-            raise NotImplementedError('aladin_amd: the stand-alone backward entry point is the image/caption form')
-        geom, pk = align_geometry(Bi, Bc, R, T, D), None
-    else:
-        geom = packed[0]
-        pk = _packed_struct(packed[1], packed[2], packed[3], packed[4] if len(packed) > 4 else None) if have else None
-    flags = (_bwd_flags(packed) if have else 0) | dense_flag
-    ws = _workspace(lib.aladin_align_bwd_workspace_bytes(C.byref(geom), dense_flag), im.device)
-    vi, vs, gi, gs = _set_view(im, im_len_t), _set_view(s, s_len_t), _grad_view(d_im), _grad_view(d_s)
-    _lib.check(lib.aladin_align_bwd(C.byref(vi), C.byref(vs), C.byref(geom), C.byref(pk) if pk is not None else None, _ptr(dS), ld_dS,
-                                    _ptr(gscale), _ptr(pairs[0] if pairs else None), _ptr(pairs[1] if pairs else None),
-                                    C.byref(gi), C.byref(gs), _ptr(ws), flags, _stream()), 'align_bwd')
-    return d_im, d_s
-
-
-def _align_backward_long(im, s, im_len_t, s_len_t, dS, ld_dS, gscale, packed, x_tails):
-    """aladin_align_long_bwd: the pair-list path for any dS (a dense one included), the row step's unit vectors as
-    set_backward_precision() says when the forward's packed operands are at hand."""
-    lib = _lib.load()
-    Bi, R, D = im.shape
-    Bc, T, _ = s.shape
     d_im, d_s = _grad_like(im), _grad_like(s)
-    have = packed is not None and packed[1] is not None
-    geom = packed[0] if packed is not None else long_geometry(Bi, Bc, R, T, D, *x_tails)
-    pk = _packed_struct(packed[1], packed[2], packed[3], packed[4] if len(packed) > 4 else None) if have else None
-    flags = _bwd_flags(packed) if have else 0
-    _LAST_BWD_FLAGS[0] = 0
-    ws = _workspace(lib.aladin_align_long_bwd_workspace_bytes(C.byref(geom)), im.device)
+    pk = C.byref(packed.struct()) if have else None
+    flags = (_bwd_flags(packed) if have else 0) | dense_flag
     vi, vs, gi, gs = _set_view(im, im_len_t), _set_view(s, s_len_t), _grad_view(d_im), _grad_view(d_s)
-    _lib.check(lib.aladin_align_long_bwd(C.byref(vi), C.byref(vs), C.byref(geom), C.byref(pk) if pk is not None else None, _ptr(dS), ld_dS,
-                                         _ptr(gscale), C.byref(gi), C.byref(gs), _ptr(ws), flags, _stream()), 'align_long_bwd')
+    if long:
+        ws = _workspace(lib.aladin_align_long_bwd_workspace_bytes(C.byref(geom)), im.device)
+        _lib.check(lib.aladin_align_long_bwd(C.byref(vi), C.byref(vs), C.byref(geom), pk, _ptr(dS), ld_dS, _ptr(gscale), C.byref(gi),
+                                             C.byref(gs), _ptr(ws), flags, _stream()), 'align_long_bwd')
+    else:
+        ws = _workspace(lib.aladin_align_bwd_workspace_bytes(C.byref(geom), dense_flag), im.device)
+        _lib.check(lib.aladin_align_bwd(C.byref(vi), C.byref(vs), C.byref(geom), pk, _ptr(dS), ld_dS, _ptr(gscale),
+                                        _ptr(pairs[0] if pairs else None), _ptr(pairs[1] if pairs else None),
+                                        C.byref(gi), C.byref(gs), _ptr(ws), flags, _stream()), 'align_bwd')
     return d_im, d_s
 
 
@@ -411,9 +420,9 @@ def _triplet_fused_ok(geom):
 
 def _triplet_forward(im, s, im_len_t, s_len_t, margin, loss_out=None):
     """aladin_align_triplet_fwd: pack + side GEMM + scores + hinge statistics + [pair arg-max | hinge element-wise] in ONE C call.
-    -> (loss, S, saved) with saved = (im, s, geom, buf, dS, ws): `buf` is ONE allocation holding xm | xe | y | rnorm, `ws` the node's
-    workspace (side scratch, statistics, arg-max table, dS^T) -- both untouched until _triplet_backward.  None when the shape is not
-    covered (the caller composes the generic calls)."""
+    -> (loss, S, AlignSaved): the operands xm | xe | y | rnorm are ONE allocation, the node's workspace (side scratch, statistics,
+    arg-max table, dS^T) another -- both untouched until the backward.  None when the shape is not covered (the caller composes
+    the generic calls)."""
     Bi, R, D = im.shape
     Bc, T, _ = s.shape
     if is_long(R, T):
@@ -431,24 +440,23 @@ def _triplet_forward(im, s, im_len_t, s_len_t, margin, loss_out=None):
         o_xe = up(geom.xm_bytes)
         o_y = o_xe + up(max(geom.xe_bytes, 16))
         o_rn = o_y + up(geom.y_bytes)
-        lay = (o_xe, o_y, o_rn, o_rn + up(geom.rnorm_bytes), int(lib.aladin_align_triplet_workspace_bytes(C.byref(geom))))
+        lay = ((o_xe, o_y, o_rn), o_rn + up(geom.rnorm_bytes), int(lib.aladin_align_triplet_workspace_bytes(C.byref(geom))))
         if len(_TRIPLET_WS) < 256:
             _TRIPLET_WS[key] = lay
-    o_xe, o_y, o_rn, n_buf, n_ws = lay
+    offs, n_buf, n_ws = lay
     buf = torch.empty(n_buf, dtype=torch.uint8, device=dev)
     ws = torch.empty(n_ws, dtype=torch.uint8, device=dev)
     S = torch.empty((Bi, Bc), dtype=torch.float32, device=dev)
     dS = torch.empty((Bi, Bc), dtype=torch.float32, device=dev)
     loss = loss_out if loss_out is not None else torch.empty((), dtype=torch.float32, device=dev)
-    base = buf.data_ptr()
-    pk = _lib.Packed(base, base + o_xe, base + o_y, base + o_rn)
-    vi, vs = _set_view(im, im_len_t), _set_view(s, s_len_t)
+    vi, vs, pk = _set_view(im, im_len_t), _set_view(s, s_len_t), _packed_from_buf(buf, offs)
     _lib.check(lib.aladin_align_triplet_fwd(C.byref(vi), C.byref(vs), C.byref(geom), float(margin), C.byref(pk), _ptr(S), S.stride(0),
                                             _ptr(loss), _ptr(dS), _ptr(ws), _stream()), 'align_triplet_fwd')
-    return loss, S, (im, s, geom, buf, dS, ws, (o_xe, o_y, o_rn))
+    return loss, S, AlignSaved(geom, im, s, dS, ws, (buf,), offs=offs, table=True)
 
 
 def _packed_from_buf(buf, offs):
+    """struct aladin_packed of the one-allocation operand buffer, without a tensor view (the fused step is host-bound)."""
     base = buf.data_ptr()
     return _lib.Packed(base, base + offs[0], base + offs[1], base + offs[2])
 
@@ -467,6 +475,67 @@ def _triplet_backward(im, s, im_len_t, s_len_t, geom, pk, dS, ws, gscale, base_w
     return d_im, d_s
 
 
+class AlignSaved:
+    """What the forward of an alignment head leaves for its backward.  Producers: _triplet_forward (the fused call),
+    _align_head_forward (the composed calls), _SmallHeads (the small-batch heads' launch); one consumer: backward().
+    The tensors go through the node's save_for_backward (tensors(), handed out once); the rest stays here, on the node's ctx:
+      offs            byte offsets of xe, y, rnorm in the ONE operand buffer of the fused call; None: xm, xe, y, rnorm are four tensors
+      table, base_ws  the arg-max table of dS's pairs is already in the saved workspace [which is laid out as aladin_align_bwd's]
+      pairs, dense, fill   without a table, for _align_backward: the hinge's pair list, the density probe's answer, the captions' fill
+      live            a dS was produced: there is something to back-propagate"""
+    __slots__ = ('geom', 'offs', 'table', 'base_ws', 'pairs', 'dense', 'fill', 'live', '_tensors')
+
+    def __init__(self, geom, im, s, dS, ws, operands, offs=None, table=False, base_ws=False, pairs=None, dense=False, fill=None):
+        self.geom, self.offs, self.table, self.base_ws = geom, offs, table, base_ws
+        self.pairs, self.dense, self.fill, self.live = pairs, dense, fill, dS is not None
+        self._tensors = [im, s, dS, ws, *operands]
+
+    def tensors(self):
+        """[im, s (in the row layout the kernels were given), dS, workspace, operands...] for save_for_backward."""
+        out, self._tensors = self._tensors, None
+        return out
+
+    def backward(self, saved, im_len_t, s_len_t, gscale, g_scores=None):
+        """-> (d_im, d_s).  saved: tensors() as the node's ctx.saved_tensors returns them; gscale: the upstream gradient of the
+        loss as a device scalar (None: none arrived); g_scores: a gradient on the returned score matrix."""
+        im, s, dS, ws, *operands = saved
+        if self.table and g_scores is None:
+            # the training path: the table is already there (forward), only the row kernel is left; dloss/dS never leaves the
+            # device and the upstream scalar goes to the kernels as a pointer
+            pk = _packed_from_buf(operands[0], self.offs) if self.offs is not None else Packed(self.geom, *operands).struct()
+            return _triplet_backward(im, s, im_len_t, s_len_t, self.geom, pk, dS, ws, gscale, base_workspace=self.base_ws)
+        packed = Packed.from_buf(operands[0], self.geom, self.offs) if self.offs is not None else Packed(self.geom, *operands)
+        if g_scores is None:
+            return _align_backward(im, s, im_len_t, s_len_t, dS, gscale=gscale, packed=packed, pairs=self.pairs, dense=self.dense,
+                                   fill=self.fill)
+        # the returned score matrix was used too (the reference's S carries grad, alad/loss.py:151-159):
+        # total dS = g_loss * dloss/dS + g_scores, generally dense
+        total = g_scores.to(torch.float32)
+        if gscale is not None:
+            total = total + dS * gscale
+        return _align_backward(im, s, im_len_t, s_len_t, total.contiguous(), packed=packed, dense=True, fill=self.fill)
+
+
+def _align_head_forward(im, s, im_len_t, s_len_t, margin, max_violation, need, fill=None, hinge=True, loss_out=None):
+    """Alignment scores [+ their hinge] -> (loss or None, S, AlignSaved).  need: the sets take a gradient.  With the
+    hardest-negative hinge on the fp16 pair kernel's shapes -- every training config -- ONE call into the library
+    (_triplet_forward); otherwise pack + scores, the hinge, and for the sum of violations the density probe."""
+    if need and hinge:
+        _check_backward_supported(im, s, 0, 2)
+    fused = _triplet_forward(im, s, im_len_t, s_len_t, margin, loss_out) if (hinge and need and max_violation) else None
+    if fused is not None:
+        return fused
+    S, packed = _align_forward(im, s, im_len_t, s_len_t, norms=need)
+    loss = dS = pairs = None
+    dense = False
+    if hinge:
+        loss, dS, pairs = _hinge_raw(S, margin, max_violation, need, want_pairs=True, loss_out=loss_out)
+        # sum of violations: dloss/dS is dense while most pairs violate the margin (the previous steps' pair counts say)
+        if need and not max_violation:
+            dense = _density_probe.step(pairs[1], S.shape[0] * S.shape[1])
+    return loss, S, AlignSaved(packed.geom, im, s, dS, None, packed.operands(), pairs=pairs, dense=dense, fill=fill)
+
+
 class _AlignScores(torch.autograd.Function):
     @staticmethod
     def forward(ctx, im, s, im_len_t, s_len_t, x_tail, y_tail):
@@ -475,28 +544,19 @@ class _AlignScores(torch.autograd.Function):
             _check_backward_supported(im, s, x_tail, y_tail)
         S, packed = _align_forward(im, s, im_len_t, s_len_t, x_tail, y_tail, norms=need)
         if need:
-            ctx.save_for_backward(im, s, im_len_t, s_len_t, *packed[1:])
-            ctx.geom = packed[0]
+            ctx.save_for_backward(im, s, im_len_t, s_len_t, *packed.operands())
+            ctx.geom = packed.geom
         return S
 
     @staticmethod
     def backward(ctx, dS):
-        im, s, im_len_t, s_len_t, xm, xe, y, rnorm = ctx.saved_tensors
+        im, s, im_len_t, s_len_t, *operands = ctx.saved_tensors
         dense = False
         if DENSE_BACKWARD and dS.numel() >= DENSE_MIN_PAIRS and not torch.cuda.is_current_stream_capturing():
             probe = _generic_probes.setdefault((tuple(dS.shape), ctx.geom.x_tail, ctx.geom.y_tail), _DensityProbe(unknown=False))
             dense = probe.step(torch.count_nonzero(dS), dS.numel())
-        d_im, d_s = _align_backward(im, s, im_len_t, s_len_t, dS, packed=(ctx.geom, xm, xe, y, rnorm), dense=dense)
+        d_im, d_s = _align_backward(im, s, im_len_t, s_len_t, dS, packed=Packed(ctx.geom, *operands), dense=dense)
         return d_im, d_s, None, None, None, None
-
-
-def _buf_views(buf, geom, offs):
-    """(geom, xm, xe, y, rnorm) tensor views of the one-allocation operand buffer of _triplet_forward."""
-    xm = buf[:geom.xm_bytes].view(torch.float16)
-    xe = buf[offs[0]:offs[0] + max(int(geom.xe_bytes), 16)].view(torch.float16)
-    y = buf[offs[1]:offs[1] + geom.y_bytes].view(torch.float16)
-    rnorm = buf[offs[2]:offs[2] + geom.rnorm_bytes].view(torch.float32)
-    return geom, xm, xe, y, rnorm
 
 
 class _AlignTriplet(torch.autograd.Function):
@@ -507,60 +567,23 @@ class _AlignTriplet(torch.autograd.Function):
     (aladin_align_triplet_fwd / _bwd; rounds 1-4: six ctypes calls and nine allocations per step)."""
 
     @staticmethod
-    def forward(ctx, im, s, im_len_t, s_len_t, margin, max_violation):
+    def forward(ctx, im, s, im_len_t, s_len_t, margin, max_violation, fill):
         need = any(ctx.needs_input_grad[:2])
-        ctx.fill, _FILL_HINT[0] = _FILL_HINT[0], None
+        loss, S, saved = _align_head_forward(im, s, im_len_t, s_len_t, margin, max_violation, need, fill)
         if need:
-            _check_backward_supported(im, s, 0, 2)
-        ctx.fused = False
-        fused = _triplet_forward(im, s, im_len_t, s_len_t, margin) if need and max_violation else None
-        if fused is not None:
-            loss, S, (im_c, s_c, geom, buf, dS, ws, offs) = fused
-            ctx.save_for_backward(im_c, s_c, im_len_t, s_len_t, buf, dS, ws)
-            ctx.geom, ctx.offs, ctx.fused, ctx.pairs, ctx.dense = geom, offs, True, None, False
-            ctx.set_materialize_grads(False)
-            return loss, S
-        S, packed = _align_forward(im, s, im_len_t, s_len_t, norms=need)
-        loss, dS, pairs = _hinge_raw(S, margin, max_violation, need, want_pairs=True)
-        if need:
-            ctx.save_for_backward(im, s, im_len_t, s_len_t, dS, *packed[1:])
-            ctx.geom = packed[0]
-            ctx.pairs = pairs
-        # sum of violations: dloss/dS is dense while most pairs violate the margin (the previous steps' pair counts say)
-        ctx.dense = False
-        if need and not max_violation:
-            ctx.dense = _density_probe.step(pairs[1], S.shape[0] * S.shape[1])
+            ctx.align = saved
+            ctx.save_for_backward(im_len_t, s_len_t, *saved.tensors())
         ctx.set_materialize_grads(False)
         return loss, S
 
     @staticmethod
     def backward(ctx, g_loss, g_scores):
         if g_loss is None and g_scores is None:
-            return None, None, None, None, None, None
-        if ctx.fused:
-            im, s, im_len_t, s_len_t, buf, dS, ws = ctx.saved_tensors
-            if g_scores is None:
-                # the argmax table is already there (forward): only the row kernel is left
-                d_im, d_s = _triplet_backward(im, s, im_len_t, s_len_t, ctx.geom, _packed_from_buf(buf, ctx.offs), dS, ws,
-                                              g_loss.to(torch.float32).contiguous())
-                return d_im, d_s, None, None, None, None
-            packed = _buf_views(buf, ctx.geom, ctx.offs)
-        else:
-            im, s, im_len_t, s_len_t, dS, xm, xe, y, rnorm = ctx.saved_tensors
-            packed = (ctx.geom, xm, xe, y, rnorm)
-        if g_scores is None:
-            # the training path: only the loss is differentiated; dloss/dS (<= 3B non-zeros with the hardest-negative
-            # hinge) never leaves the device and the upstream scalar goes to the kernels as a pointer
-            g = g_loss.to(torch.float32).contiguous()
-            d_im, d_s = _align_backward(im, s, im_len_t, s_len_t, dS, gscale=g, packed=packed, pairs=ctx.pairs, dense=ctx.dense, fill=ctx.fill)
-        else:
-            # the returned score matrix was used too (the reference's S carries grad, alad/loss.py:151-159):
-            # total dS = g_loss * dloss/dS + g_scores, generally dense
-            total = g_scores.to(torch.float32)
-            if g_loss is not None:
-                total = total + dS * g_loss.to(torch.float32)
-            d_im, d_s = _align_backward(im, s, im_len_t, s_len_t, total.contiguous(), packed=packed, dense=True, fill=ctx.fill)
-        return d_im, d_s, None, None, None, None
+            return None, None, None, None, None, None, None
+        im_len_t, s_len_t, *saved = ctx.saved_tensors
+        g = g_loss.to(torch.float32).contiguous() if g_loss is not None else None
+        d_im, d_s = ctx.align.backward(saved, im_len_t, s_len_t, g, g_scores)
+        return d_im, d_s, None, None, None, None, None
 
 
 def _check_sets(im_set, s_seq, im_len, s_len):
@@ -583,8 +606,8 @@ def alignment_triplet_loss(im_set, s_seq, im_len, s_len, margin, max_violation):
                          '(the reference fails in diag/expand_as, alad/loss.py:43-45)' % (im_set.shape[0], s_seq.shape[0]))
     if torch.is_grad_enabled() and (im_set.requires_grad or s_seq.requires_grad):
         im_set, s_seq = _pad_features(im_set, s_seq)
-    _FILL_HINT[0] = None if max_violation else _caption_fill(s_len, s_seq.shape[1])
-    return _AlignTriplet.apply(im_set, s_seq, im_len_t, s_len_t, margin, max_violation)
+    fill = None if max_violation else _caption_fill(s_len, s_seq.shape[1])
+    return _AlignTriplet.apply(im_set, s_seq, im_len_t, s_len_t, margin, max_violation, fill)
 
 
 def _host_lengths(lens):

@@ -6,10 +6,9 @@ import ctypes as C
 import torch
 
 from . import _lib
-from . import ops as _al
-from ._ops_common import _RAW_STREAM, _stream, _ptr, _require_gpu, _rows_inner_contig, _LEN_CACHE, lengths_tensor, _ld, _workspace
-from .ops import (_FILL_HINT, _align_backward, _align_forward, _caption_fill, _check_backward_supported, _check_sets, _density_probe,
-                  _packed_from_buf, _packed_struct, _pair_kernel_covers, _set_view, _triplet_backward, _triplet_forward, is_long)
+from ._ops_common import _stream, _ptr, _require_gpu, _rows_inner_contig, _ld, _workspace
+from .ops import (AlignSaved, _align_forward, _align_head_forward, _caption_fill, _check_backward_supported, _check_sets,
+                  _pad_features, _pair_kernel_covers, _set_view, is_long)
 from .ops_losses import _hinge_raw, _sgemm, dot_scores
 
 
@@ -40,15 +39,15 @@ def _heads_small_fwd(im, s, S, margin, max_violation, flags, temperature, eps, w
     out['dMl'] = torch.empty((B, B), **f32) if (want_grads and flags & HEAD_LISTNET and weights[2] != 0) else None
     out['dS'] = torch.empty((B, B), **f32) if (want_grads and flags & HEAD_ALIGN_HINGE) else None
     out['pairs'] = out['table_ws'] = out['sets'] = None
-    if (align is not None and out['dS'] is not None and max_violation and _pair_kernel_covers(align[4][0])
-            and not align[4][0].split):
-        im_set, s_seq, im_len_t, s_len_t, packed = align
-        geom = packed[0]
+    im_set, s_seq, im_len_t, s_len_t, packed = align if align is not None else (None,) * 5
+    if (packed is not None and out['dS'] is not None and max_violation and _pair_kernel_covers(packed.geom)
+            and not packed.geom.split):
+        geom = packed.geom
         im_c, s_c = _rows_inner_contig(im_set), _rows_inner_contig(s_seq)
         out['table_ws'] = torch.empty(lib.aladin_align_bwd_workspace_bytes(C.byref(geom), 0), dtype=torch.uint8, device=dev)
         out['sets'] = (im_c, s_c)
         ws = _workspace(lib.aladin_heads_small_workspace_bytes(B), dev)
-        vi, vs, pk = _set_view(im_c, im_len_t), _set_view(s_c, s_len_t), _packed_struct(*packed[1:5])
+        vi, vs, pk = _set_view(im_c, im_len_t), _set_view(s_c, s_len_t), packed.struct()
         _lib.check(lib.aladin_heads_small_fwd_argmax(_ptr(im), _ld(im) if im is not None else 0, _ptr(s), _ld(s) if s is not None else 0,
                                                      _ptr(S), _ld(S), D, float(margin), int(flags), float(temperature), float(eps),
                                                      float(weights[0]), float(weights[1]), float(weights[2]), _ptr(out['M']),
@@ -129,11 +128,10 @@ class _SmallHeads(torch.autograd.Function):
         o = _heads_small_fwd(a, b, S, margin, max_violation, flags, temperature, eps, weights, need_sets or need_embs, True, align)
         if o['sets'] is not None:
             im, s = o['sets']
-        ctx.flags, ctx.weights = flags, weights
-        ctx.geom = packed[0] if packed is not None else None
-        ctx.pairs = o['pairs']
-        pk = packed[1:] if packed is not None else (None, None, None, None)
-        ctx.save_for_backward(a, b, im, s, im_len_t, s_len_t, pk[0], pk[1], pk[2], pk[3], o['dMh'], o['dMl'], o['dS'], o['table_ws'])
+        ctx.weights = weights
+        ctx.align = saved = None if packed is None else AlignSaved(
+            packed.geom, im, s, o['dS'], o['table_ws'], packed.operands(), table=o['table_ws'] is not None, base_ws=True, pairs=o['pairs'])
+        ctx.save_for_backward(a, b, im_len_t, s_len_t, o['dMh'], o['dMl'], *(saved.tensors() if saved else ()))
         ctx.set_materialize_grads(False)
         terms = o['terms']
         ctx.mark_non_differentiable(*[t for t in (terms, S, o['M']) if t is not None])       # one call: it replaces the set
@@ -143,11 +141,12 @@ class _SmallHeads(torch.autograd.Function):
     def backward(ctx, g_total, _g_terms, _g_S, _g_M):
         if g_total is None:
             return (None,) * 12
-        a, b, im, s, im_len_t, s_len_t, xm, xe, y, rnorm, dMh, dMl, dS, table_ws = ctx.saved_tensors
-        flags, w = ctx.flags, ctx.weights
+        a, b, im_len_t, s_len_t, dMh, dMl, *saved = ctx.saved_tensors
+        w = ctx.weights
         g = g_total.to(torch.float32).contiguous()
         d_a = d_b = d_im = d_s = None
-        scale = torch.empty(1, dtype=torch.float32, device=g.device) if dS is not None else None
+        want_a = ctx.align is not None and ctx.align.live
+        scale = torch.empty(1, dtype=torch.float32, device=g.device) if want_a else None
         if a is not None:
             B, D = a.shape
             d_a = torch.empty((B, D), dtype=torch.float32, device=a.device) if ctx.needs_input_grad[0] else None
@@ -157,12 +156,8 @@ class _SmallHeads(torch.autograd.Function):
                                                           _ptr(scale), _ptr(d_a), _ptr(d_b), _stream()), 'heads_small_bwd')
         elif scale is not None:
             scale = g * float(w[1])
-        if dS is not None and any(ctx.needs_input_grad[2:4]):
-            if table_ws is not None:
-                d_im, d_s = _triplet_backward(im, s, im_len_t, s_len_t, ctx.geom, _packed_struct(xm, xe, y, rnorm), dS, table_ws, scale,
-                                              base_workspace=True)
-            else:
-                d_im, d_s = _align_backward(im, s, im_len_t, s_len_t, dS, gscale=scale, packed=(ctx.geom, xm, xe, y, rnorm), pairs=ctx.pairs)
+        if want_a and any(ctx.needs_input_grad[2:4]):
+            d_im, d_s = ctx.align.backward(saved, im_len_t, s_len_t, scale)
         return d_a, d_b, d_im, d_s, None, None, None, None, None, None, None, None
 
 
@@ -173,31 +168,17 @@ class _BigHeads(torch.autograd.Function):
     alignment backward.  No element-wise torch kernels."""
 
     @staticmethod
-    def forward(ctx, img_emb, cap_emb, im, s, im_len_t, s_len_t, margin, max_violation, flags, weights, temperature, eps):
+    def forward(ctx, img_emb, cap_emb, im, s, im_len_t, s_len_t, margin, max_violation, flags, weights, temperature, eps, fill):
         lib = _lib.load()
         need_sets = any(ctx.needs_input_grad[2:4])
         need_embs = any(ctx.needs_input_grad[0:2])
         dev = img_emb.device
         B = img_emb.shape[0]
         terms = torch.empty(3, dtype=torch.float32, device=dev)          # slots of absent heads are never read
-        S = packed = dS = pairs = table_ws = buf = None
-        dense = False
-        ctx.fill, _FILL_HINT[0] = _FILL_HINT[0], None
-        ctx.offs = None
+        S = saved = None
         if flags & (HEAD_ALIGN_HINGE | HEAD_LISTNET):
-            if need_sets and flags & HEAD_ALIGN_HINGE:
-                _check_backward_supported(im, s, 0, 2)
-            fused = (_triplet_forward(im, s, im_len_t, s_len_t, margin, loss_out=terms[1:2])
-                     if (flags & HEAD_ALIGN_HINGE) and need_sets and max_violation else None)
-            if fused is not None:                    # the alignment head's whole forward in one library call
-                _, S, (im, s, geom_f, buf, dS, table_ws, ctx.offs) = fused
-                packed = (geom_f, None, None, None, None)
-            else:
-                S, packed = _align_forward(im, s, im_len_t, s_len_t, norms=need_sets)
-                if flags & HEAD_ALIGN_HINGE:
-                    _, dS, pairs = _hinge_raw(S, margin, max_violation, need_sets, want_pairs=True, loss_out=terms[1:2])
-                    if need_sets and not max_violation:                 # sum of violations: the dense backward while dS is dense
-                        dense = _density_probe.step(pairs[1], B * B)
+            _, S, saved = _align_head_forward(im, s, im_len_t, s_len_t, margin, max_violation, need_sets, fill,
+                                              hinge=bool(flags & HEAD_ALIGN_HINGE), loss_out=terms[1:2])
         a = b = M = dMh = dMl = None
         if flags & (HEAD_MATCH_HINGE | HEAD_LISTNET):
             a = img_emb if img_emb.stride(1) == 1 else img_emb.contiguous()
@@ -218,12 +199,8 @@ class _BigHeads(torch.autograd.Function):
                                          C.c_void_p(tp + 4) if flags & HEAD_ALIGN_HINGE else C.c_void_p(0), float(weights[1]),
                                          C.c_void_p(tp + 8) if flags & HEAD_LISTNET else C.c_void_p(0), float(weights[2]),
                                          _ptr(total), _stream()), 'loss_total')
-        ctx.flags, ctx.weights = flags, weights
-        ctx.geom = packed[0] if packed is not None else None
-        ctx.pairs = pairs
-        ctx.dense = dense
-        pk = packed[1:] if packed is not None else (None, None, None, None)
-        ctx.save_for_backward(a, b, im, s, im_len_t, s_len_t, pk[0], pk[1], pk[2], pk[3], dMh, dMl, dS, table_ws, buf)
+        ctx.weights, ctx.align = weights, saved
+        ctx.save_for_backward(a, b, im_len_t, s_len_t, dMh, dMl, *(saved.tensors() if saved else ()))
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(*[t for t in (terms, S, M) if t is not None])
         return total, terms, S, M
@@ -231,15 +208,15 @@ class _BigHeads(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_total, _g_terms, _g_S, _g_M):
         if g_total is None:
-            return (None,) * 12
+            return (None,) * 13
         lib = _lib.load()
-        a, b, im, s, im_len_t, s_len_t, xm, xe, y, rnorm, dMh, dMl, dS, table_ws, buf = ctx.saved_tensors
+        a, b, im_len_t, s_len_t, dMh, dMl, *saved = ctx.saved_tensors
         w = ctx.weights
         g = g_total.to(torch.float32).contiguous()
         dev = g.device
         d_a = d_b = d_im = d_s = None
         want_m = (dMh is not None or dMl is not None) and any(ctx.needs_input_grad[0:2])
-        want_a = dS is not None and any(ctx.needs_input_grad[2:4])
+        want_a = ctx.align is not None and ctx.align.live and any(ctx.needs_input_grad[2:4])
         C_tot = torch.empty_like(dMh if dMh is not None else dMl) if want_m else None
         scale = torch.empty(1, dtype=torch.float32, device=dev) if want_a else None
         if want_m or want_a:
@@ -254,12 +231,9 @@ class _BigHeads(torch.autograd.Function):
             if ctx.needs_input_grad[1]:
                 d_b = torch.empty((B, D), dtype=torch.float32, device=dev)
                 _sgemm(B, D, B, C_tot, 1, C_tot.stride(0), a, a.stride(0), a.stride(1), d_b)          # C.T @ img
-        if want_a and buf is not None:
-            d_im, d_s = _triplet_backward(im, s, im_len_t, s_len_t, ctx.geom, _packed_from_buf(buf, ctx.offs), dS, table_ws, scale)
-        elif want_a:
-            d_im, d_s = _align_backward(im, s, im_len_t, s_len_t, dS, gscale=scale, packed=(ctx.geom, xm, xe, y, rnorm), pairs=ctx.pairs,
-                                        dense=ctx.dense, fill=ctx.fill)
-        return d_a, d_b, d_im, d_s, None, None, None, None, None, None, None, None
+        if want_a:
+            d_im, d_s = ctx.align.backward(saved, im_len_t, s_len_t, scale)
+        return d_a, d_b, d_im, d_s, None, None, None, None, None, None, None, None, None
 
 
 def small_batch_loss_heads(img_emb, cap_emb, im_set, s_seq, im_len, s_len, margin, max_violation, heads, weights,
@@ -279,15 +253,16 @@ def small_batch_loss_heads(img_emb, cap_emb, im_set, s_seq, im_len, s_len, margi
         if not (im_set.shape[0] == s_seq.shape[0] == img_emb.shape[0]):
             raise ValueError('aladin_amd: the loss heads need one image set, one caption and one embedding pair per sample')
         if torch.is_grad_enabled() and (im_set.requires_grad or s_seq.requires_grad):
-            from .ops import _pad_features
             im_set, s_seq = _pad_features(im_set, s_seq)          # D % 4 != 0: zero features, dropped again by autograd
     w = (float(weights.get('matching', 0.0)), float(weights.get('alignment', 0.0)), float(weights.get('distillation', 0.0)))
     # long sets never reach the small-batch kernels (their tile classes stop at 96 scored positions): the general node
     long_sets = im_set is not None and s_seq is not None and flags & (HEAD_ALIGN_HINGE | HEAD_LISTNET) and \
         is_long(im_set.shape[1], s_seq.shape[1])
     node = _SmallHeads if img_emb.shape[0] <= SMALL_BATCH_MAX and not long_sets else _BigHeads
-    _FILL_HINT[0] = _caption_fill(s_len, s_seq.shape[1]) if (node is _BigHeads and not max_violation and flags & HEAD_ALIGN_HINGE) else None
-    return node.apply(img_emb, cap_emb, im_set, s_seq, im_len_t, s_len_t, margin, max_violation, flags, w, temperature, eps)
+    args = (img_emb, cap_emb, im_set, s_seq, im_len_t, s_len_t, margin, max_violation, flags, w, temperature, eps)
+    if node is _SmallHeads:
+        return _SmallHeads.apply(*args)
+    return _BigHeads.apply(*args, _caption_fill(s_len, s_seq.shape[1]) if (not max_violation and flags & HEAD_ALIGN_HINGE) else None)
 
 
 loss_heads = small_batch_loss_heads            # the single-node step at any batch size

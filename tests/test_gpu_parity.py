@@ -1262,6 +1262,49 @@ def test_dense_row_step_follows_the_caption_fill():
         ops._density_probe.__init__()
 
 
+def test_caption_fill_reaches_the_big_heads():
+    """The same choice through ops.loss_heads at B > 64 (ops._BigHeads, sum of violations): the captions' fill is an argument
+    of the node, and full captions take the GEMM row step, short ones the gather."""
+    from aladin_amd import _lib, ops, synth
+    B, D = 128, 64                          # the smallest batch with B * B >= DENSE_MIN_PAIRS
+    im, s, il, _ = synth.alignment_batch(B, 34, 50, D, seed=59, ragged=False)
+    gi, gc = synth.global_embeddings(B, D, seed=60)
+    ops._density_probe.__init__()
+    old_f, ops.DENSE_MIN_FRACTION = ops.DENSE_MIN_FRACTION, 0.0
+    try:
+        for sl, gather in (([50] * B, False), ([13] * B, True)):
+            x, y, a, b = (T(v).requires_grad_(True) for v in (gi, gc, im, s))
+            total = ops.loss_heads(x, y, a, b, il, sl, 0.2, False, ('matching', 'alignment'), {'matching': 1.0, 'alignment': 1.0})[0]
+            total.backward()
+            assert ops._LAST_BWD_FLAGS[0] & _lib.BWD_DENSE
+            assert bool(ops._LAST_BWD_FLAGS[0] & _lib.BWD_DENSE_GATHER) == gather
+    finally:
+        ops.DENSE_MIN_FRACTION = old_f
+        ops._density_probe.__init__()
+
+
+def test_table_and_score_gradient_backward_agree():
+    """One node, both ways through its backward: only the loss differentiated (the forward's arg-max table + the row step) against
+    a (zero) gradient on the returned S as well (total dS through the general backward, operands as views of the forward's one
+    buffer).  Same gradients to 1e-5 of the largest entry (the bar of the dense-against-list tests), finite, zero on padding."""
+    from aladin_amd import ops, synth
+    B, R, Tn, D = 8, 34, 20, 64
+    im, s, il, sl = synth.alignment_batch(B, R, Tn, D, seed=61, ragged=True)
+    grads = []
+    for through_scores in (False, True):
+        a, b = T(im).requires_grad_(True), T(s).requires_grad_(True)
+        loss, S = ops.alignment_triplet_loss(a, b, il, sl, 0.2, True)
+        (loss + 0.0 * S.sum() if through_scores else loss).backward()
+        grads.append((a.grad.clone(), b.grad.clone()))
+    for k, lens in ((0, il), (1, sl)):
+        g0, g1 = grads[0][k], grads[1][k]
+        assert torch.isfinite(g0).all() and torch.isfinite(g1).all()
+        assert g0.abs().max() > 0
+        assert (g0 - g1).abs().max() <= 1e-5 * g0.abs().max()
+        for i, n in enumerate(lens):
+            assert not g0[i, n:].any() and not g1[i, n:].any()
+
+
 def test_dense_backward_through_the_score_matrix():
     """The other dense caller: a gradient arriving on the returned S (listnet on top of the alignment scores)."""
     from aladin_amd import ops, synth

@@ -55,19 +55,19 @@ B = 256
 im, s, il, sl = synth.alignment_batch(B, 34, 50, 768, seed=1234, ragged=False)
 a, b = T(im), T(s)
 ilt, slt = ops.lengths_tensor(il, dev), ops.lengths_tensor(sl, dev)
-loss, S, (im_c, s_c, geom, buf, dS, ws, offs) = ops._triplet_forward(a, b, ilt, slt, 0.2)
+loss, S, align = ops._triplet_forward(a, b, ilt, slt, 0.2)
+saved = align.tensors()
 one = torch.ones((), device=dev)
 
 
 def rows_us(iters=200):
-    pk = ops._packed_from_buf(buf, offs)
     for _ in range(20):
-        ops._triplet_backward(im_c, s_c, ilt, slt, geom, pk, dS, ws, one)
+        align.backward(saved, ilt, slt, one)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(iters):
-        ops._triplet_backward(im_c, s_c, ilt, slt, geom, pk, dS, ws, one)
+        align.backward(saved, ilt, slt, one)
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / iters * 1e3
