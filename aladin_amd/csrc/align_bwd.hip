@@ -25,7 +25,8 @@
 //   launched, and one small function per stage does the work.  The exported entry points compose the stages:
 //     aladin_align_bwd               check -> (table of all pairs | the caller's list | list from dS) -> table from the list
 //                                    -> (rows by GEMM, align_bwd_dense.hip | rows by gather)
-//     aladin_align_triplet_fwd       check -> pack -> scores -> table from the hinge statistics
+//     aladin_align_triplet_fwd       check -> pack -> scores -> table from the hinge statistics (with side rows: pack [xe | y] ->
+//                                    side GEMM + pack xm in one launch -> scores)
 //     aladin_align_triplet_bwd       check -> rows by gather
 //     aladin_heads_small_fwd_argmax  check -> statistics -> table from the statistics
 #include "../../include/aladin_hip.h"
@@ -978,8 +979,15 @@ extern "C" int aladin_align_triplet_fwd(const aladin_set* im, const aladin_set* 
   triplet_ws_layout(g, (char*)workspace, &w);
   const BwdProblem pr = bwd_problem(im, s, g, p, stream);
   if (int rc = hinge_table_check(pr, S, ldS, loss, dS, w.hinge, w.bwd, false)) return rc;
-  if (int rc = aladin_internal_pack(im, s, g, p, pr.st)) return rc;
-  if (int rc = aladin_internal_scores(p->xm, p->xe, p->y, g, w.e, S, ldS, 0, stream)) return rc;
+  if (aladin_internal_side_packs_main(im, g)) {
+    // side rows: [xe | y] first, then the side GEMM with the main rows packed beside it
+    if (int rc = aladin_internal_pack_side_operands(im, s, g, p, pr.st)) return rc;
+    if (int rc = aladin_internal_side_with_main_pack(im, s, g, p, (float*)w.e, pr.st)) return rc;
+    if (int rc = aladin_internal_scores(p->xm, p->xe, p->y, g, w.e, S, ldS, ALADIN_SCORES_REUSE_SIDE, stream)) return rc;
+  } else {
+    if (int rc = aladin_internal_pack(im, s, g, p, pr.st)) return rc;
+    if (int rc = aladin_internal_scores(p->xm, p->xe, p->y, g, w.e, S, ldS, 0, stream)) return rc;
+  }
   return table_from_hinge(pr, S, ldS, margin, loss, dS, w.hinge, bwd_ws(pr, w.bwd));
 }
 

@@ -324,13 +324,13 @@ extern "C" int aladin_align_pack(const aladin_set* im, const aladin_set* s, cons
 // ------------------------------------------------------------------------------------------------
 // side GEMM: E[i][col] = <last region of image i, word col>   (fp32, xe_rows x y_rows)
 // ------------------------------------------------------------------------------------------------
+// one workgroup tile of E (tile index bid); shared by align_side_gemm_kernel and align_side_pack_kernel (end of the file)
 template <int NT, int SWM, int NS>
-__global__ __launch_bounds__(256) void align_side_gemm_kernel(const half_t* __restrict__ xe, const half_t* __restrict__ y,
-                                                              float* __restrict__ E, int64_t ldE, int64_t ldk,
-                                                              int ktiles, int n_nblk) {
+__device__ __forceinline__ void side_gemm_tile(const half_t* __restrict__ xe, const half_t* __restrict__ y, float* __restrict__ E,
+                                               int64_t ldE, int64_t ldk, int ktiles, int n_nblk, unsigned bid) {
   using Cfg = GemmCfg<2, 2, SWM, NT>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int mb = blockIdx.x / n_nblk, nb = blockIdx.x % n_nblk;
+  const int mb = bid / n_nblk, nb = bid % n_nblk;
   f32x16 acc[SWM][NT];
 #pragma unroll
   for (int m = 0; m < SWM; ++m)
@@ -350,6 +350,13 @@ __global__ __launch_bounds__(256) void align_side_gemm_kernel(const half_t* __re
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         E[(row0 + m * 32 + (r & 3) + 8 * (r >> 2)) * ldE + col0 + n * 32] = acc[m][n][r];
+}
+
+template <int NT, int SWM, int NS>
+__global__ __launch_bounds__(256) void align_side_gemm_kernel(const half_t* __restrict__ xe, const half_t* __restrict__ y,
+                                                              float* __restrict__ E, int64_t ldE, int64_t ldk,
+                                                              int ktiles, int n_nblk) {
+  side_gemm_tile<NT, SWM, NS>(xe, y, E, ldE, ldk, ktiles, n_nblk, blockIdx.x);
 }
 
 // Diagnostic build only (the PROBE instantiation of align_scores16_kernel): per-workgroup shader-clock and 100 MHz real-time
@@ -1239,6 +1246,19 @@ static SideCfg select_side(const aladin_align_geom* g) {
   return c;
 }
 
+// The triplet forward's prologue (aladin_align_triplet_fwd): pack [xe | y], then ONE launch of [side tiles | blocks that pack xm]
+// (align_side_pack_kernel, end of the file) instead of pack everything, then the side GEMM.  xm is first read by the score kernel,
+// so nothing orders its packing before the side GEMM; the side tiles are bound by their L2 -> LDS fill, the packing by HBM.
+// Every class with side rows takes it: 32 and 48 main rows (65 regions = 64 + 1 is not a class of the pair kernel), rem 1..8, all
+// caption classes -- the side tile is select_side's, whatever it is.  Kept in the old order: problems without side rows (there
+// is no launch to pack beside), split precision, and image views that float4 loads cannot address (the batched packer has only
+// pack_row's whole-row-in-registers path: D % 4 == 0, D <= 1024, 16-byte aligned rows).
+static const int MAIN_PACK_ROWS = 8;        // rows a wave of a pack block has in flight
+static bool side_packs_main(const aladin_set* im, const aladin_align_geom* g) {
+  return g->rem > 0 && !g->split && g->D <= 1024 && is_vec4_ok(im->data, im->stride_b, im->stride_r, g->D) &&
+         g->mrows % MAIN_PACK_ROWS == 0;      // a batch of rows never leaves its image
+}
+
 // f(std::integral_constant<int, v>...) for run-time values v, each drawn from its Set: every combination of the sets is compiled,
 // so the callers instantiate kernels only under `if constexpr` rules (the configurations the selection above can return).
 template <int... Vs> struct Set {};
@@ -1264,9 +1284,9 @@ template <class Cfg> static constexpr Tiles tiles_of(int lds = Cfg::LDS_BYTES, i
 }
 
 // The one launch path of this file: tile check, dynamic LDS reserved once per device, launch, launch check.
-// args(n_nblk, n_blocks) returns the kernel's arguments as a tuple.
+// args(n_nblk, n_blocks) returns the kernel's arguments as a tuple.  extra_blocks: blocks behind the n_blocks tiles of the grid.
 template <auto KERN, class Args>
-static int launch_tiles(const char* what, Tiles t, int64_t m_rows, int64_t n_rows, hipStream_t stream, Args args) {
+static int launch_tiles(const char* what, Tiles t, int64_t m_rows, int64_t n_rows, hipStream_t stream, Args args, int extra_blocks = 0) {
   const int64_t n_mblk = (m_rows + t.bm - 1) / t.bm, n_nblk = n_rows / t.bn;
   if (m_rows % t.m_unit != 0 || n_nblk * t.bn != n_rows) {
     aladin_set_error("%s: packed rows (%lld, %lld) do not tile by (%d, %d)", what, (long long)m_rows, (long long)n_rows, t.bm, t.bn);
@@ -1275,7 +1295,7 @@ static int launch_tiles(const char* what, Tiles t, int64_t m_rows, int64_t n_row
   static unsigned long long lds_reserved = 0;
   if (int rc = aladin_reserve_lds((const void*)KERN, t.lds, &lds_reserved, what)) return rc;
   const int n_blocks = (int)(n_mblk * n_nblk);
-  std::apply([&](auto... a) { hipLaunchKernelGGL(KERN, dim3(n_blocks), dim3(t.threads), t.lds, stream, a...); }, args((int)n_nblk, n_blocks));
+  std::apply([&](auto... a) { hipLaunchKernelGGL(KERN, dim3(n_blocks + extra_blocks), dim3(t.threads), t.lds, stream, a...); }, args((int)n_nblk, n_blocks));
   return aladin_check_launch(what);
 }
 
@@ -1405,4 +1425,134 @@ extern "C" int aladin_align_scores(const aladin_packed* p, const aladin_align_ge
   if (!p) { aladin_set_error("align_scores: null argument"); return ALADIN_ERR_ARG; }
   if (flags & ~ALADIN_SCORES_REUSE_SIDE) { aladin_set_error("align_scores: unknown flags %d", flags); return ALADIN_ERR_ARG; }
   return aladin_internal_scores(p->xm, p->xe, p->y, g, e_scratch, S, ldS, flags, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// triplet forward prologue: [side GEMM tiles | blocks that pack the main image rows] in one launch (side_packs_main)
+// ------------------------------------------------------------------------------------------------
+struct MainPack {
+  const float* im; int64_t sb, sr; const int32_t* len;      // the raw image set
+  int Bi, Rq, x_tail, D, Dp, mrows;
+  int64_t xm_rows;
+  half_t* xm; float* rnorm;                                 // rnorm may be nullptr
+};
+
+// Rows [0, xm_rows) of the main operand, MAIN_PACK_ROWS at a time per wave: wave w of n_waves takes the batches w, w + n_waves, ...
+// pack_row's fp16 whole-row path for each row -- same loads, same sumsq4 chain over the four float4 of a lane, wave_sum,
+// 1 / max(sqrt, 1e-12), one rounding per element, zero rows and the tile-filling copies of region 0 as pack_both_kernel places
+// them -- but the loads of all the batch's rows are issued before the first row is reduced.
+__device__ __forceinline__ void pack_main_rows(const MainPack& m, int w, int n_waves) {
+  constexpr int RB = MAIN_PACK_ROWS;
+  const int lane = threadIdx.x & 63;
+  for (int64_t d0 = (int64_t)w * RB; d0 < m.xm_rows; d0 += (int64_t)n_waves * RB) {
+    const int i = (int)(d0 / m.mrows), rho0 = (int)(d0 % m.mrows);      // mrows % RB == 0: one image per batch
+    int L = 0;                                                          // regions of image i that count (alad/loss.py:89)
+    if (i < m.Bi) {
+      L = m.len[i] - 1 - m.x_tail;
+      L = L < 0 ? 0 : (L > m.Rq ? m.Rq : L);
+    }
+    float4 v[RB][4];
+#pragma unroll
+    for (int j = 0; j < RB; ++j) {
+      int rho = rho0 + j;
+      if (rho >= m.Rq) rho = 0;                                         // tile-filling copy of the first region
+      const float* src = m.im + i * m.sb + (int64_t)(rho + 1) * m.sr;   // region 0 dropped (alad/loss.py:87)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int c = lane * 4 + 256 * k;
+        // a row of an image of the batch exists in memory whether its length masks it or not
+        v[j][k] = (i < m.Bi && c < m.D) ? *reinterpret_cast<const float4*>(src + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < RB; ++j) {
+      int rho = rho0 + j;
+      if (rho >= m.Rq) rho = 0;
+      half_t* dst = m.xm + (d0 + j) * m.Dp;
+      if (rho >= L) {                                                   // masked region, or an image that pads the batch: a zero row
+        for (int c = lane * 8; c < m.Dp; c += 64 * 8) *reinterpret_cast<half8*>(dst + c) = half8{0, 0, 0, 0, 0, 0, 0, 0};
+        if (m.rnorm && lane == 0) m.rnorm[d0 + j] = 0.f;
+        continue;
+      }
+      float ss = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ss = sumsq4(ss, v[j][k]);
+      ss = wave_sum(ss);
+      const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+      if (m.rnorm && lane == 0) m.rnorm[d0 + j] = inv;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int c = lane * 4 + 256 * k;
+        if (c < m.Dp) *reinterpret_cast<half4*>(dst + c) = half4{(half_t)(v[j][k].x * inv), (half_t)(v[j][k].y * inv), (half_t)(v[j][k].z * inv), (half_t)(v[j][k].w * inv)};
+      }
+    }
+  }
+}
+
+// Grid [n_side side tiles | pack blocks].  No block reads what another block of the launch writes: the side tiles read xe and y
+// (packed by the launch before) and write E; the pack blocks read the raw images and write xm and its rnorm entries.
+// Whether the two overlap or merely run one after the other is decided by two things:
+//   * few, fat pack blocks.  Dynamic LDS is per launch, so a pack block reserves the side tile's 64-120 KB as well and at most two
+//     blocks share a CU; thousands of four-row blocks (pack_both_kernel's shape) would leave HBM a handful of waves per CU.  So:
+//     about one pack block per CU, each of its four waves with the loads of MAIN_PACK_ROWS rows in flight before it reduces any
+//     (8 rows x 3 float4 a lane at D = 768: 96 VGPRs, ~96 KB in flight per CU), looping over batches when there are more rows;
+//   * side tiles first in block order: they are dispatched first and set the length of the launch, and the pack blocks fill the
+//     second slot of each CU (or the CUs a small grid of three-stage tiles leaves empty).
+// Measured at B = 256, R = 34, T = 50, D = 768: the launch takes 15.2 us against the side GEMM's 11.8 alone, for
+// 5.3 us of packing taken out of the launch before.  Half as many pack blocks with two batches each, pack blocks first in block
+// order, four rows in flight, a raised wave priority for the side tiles, nontemporal loads and stores: none was faster.
+template <int NT, int SWM, int NS>
+__global__ __launch_bounds__(256) void align_side_pack_kernel(const half_t* __restrict__ xe, const half_t* __restrict__ y,
+                                                              float* __restrict__ E, int64_t ldE, int64_t ldk, int ktiles,
+                                                              int n_nblk, int n_side, MainPack mp) {
+  if ((int)blockIdx.x < n_side) {
+    side_gemm_tile<NT, SWM, NS>(xe, y, E, ldE, ldk, ktiles, n_nblk, blockIdx.x);
+    return;
+  }
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  pack_main_rows(mp, ((int)blockIdx.x - n_side) * 4 + wave, ((int)gridDim.x - n_side) * 4);
+}
+
+static const int MAIN_PACK_BLOCKS = 256;      // one per CU of the MI355X
+
+static int check_prologue(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out) {
+  if (!g || !out || !set_ok(im) || !set_ok(s) || !out->xm || !out->xe || !out->y) { aladin_set_error("align_pack: null argument"); return ALADIN_ERR_ARG; }
+  if (!side_packs_main(im, g)) { aladin_set_error("align_pack: not a problem whose side launch packs the main rows"); return ALADIN_ERR_UNSUPPORTED; }
+  return ALADIN_OK;
+}
+
+bool aladin_internal_side_packs_main(const aladin_set* im, const aladin_align_geom* g) { return set_ok(im) && g && side_packs_main(im, g); }
+
+// rows [xm_rows, xm_rows + xe_rows + y_rows) of the [xm | xe | y] row space: pack_both_kernel on the same problem without its
+// main rows (row 0 of the launch is the first side row), so xe, y and their rnorm entries get the bits aladin_internal_pack gives
+int aladin_internal_pack_side_operands(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out,
+                                       hipStream_t st) {
+  if (int rc = check_prologue(im, s, g, out)) return rc;
+  const int64_t total = g->xe_rows + g->y_rows;
+  hipLaunchKernelGGL(pack_both_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, st, im->data, im->stride_b, im->stride_r, im->len,
+                     s->data, s->stride_b, s->stride_r, s->len, g->Bi, g->Bc, g->Rq, g->Tq, g->x_tail, g->y_tail, g->D, g->Dp, g->mrows, g->rem,
+                     (int64_t)0, g->xe_rows, total, g->trows, (half_t*)out->xm, (half_t*)out->xe, (half_t*)out->y,
+                     is_vec4_ok(im->data, im->stride_b, im->stride_r, g->D), is_vec4_ok(s->data, s->stride_b, s->stride_r, g->D), 0,
+                     out->rnorm ? out->rnorm + g->xm_rows : nullptr);
+  return aladin_check_launch("pack_both_kernel");
+}
+
+// the side GEMM of packed xe and y into E, with the main rows of `im` packed by the blocks behind its tiles
+int aladin_internal_side_with_main_pack(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out,
+                                        float* E, hipStream_t st) {
+  if (int rc = check_prologue(im, s, g, out)) return rc;
+  if (!E) { aladin_set_error("align_side_pack: null side scratch"); return ALADIN_ERR_ARG; }
+  const MainPack mp = {im->data, im->stride_b, im->stride_r, im->len, g->Bi, g->Rq, g->x_tail, g->D, g->Dp, g->mrows, g->xm_rows,
+                       (half_t*)out->xm, out->rnorm};
+  const int64_t wave_batches = (g->xm_rows / MAIN_PACK_ROWS + 3) / 4;
+  const int n_pack = (int)(wave_batches < MAIN_PACK_BLOCKS ? wave_batches : MAIN_PACK_BLOCKS);
+  const SideCfg c = select_side(g);
+  return with_values([&](auto nt, auto big, auto two) {
+    constexpr int SWM = big ? 2 : 1, NS = two ? 2 : 3;
+    using Cfg = GemmCfg<2, 2, SWM, nt>;
+    return launch_tiles<align_side_pack_kernel<nt, SWM, NS>>("align_side_pack_kernel", tiles_of<Cfg>(NS * Cfg::STAGE_BYTES), g->xe_rows,
+                                                            g->y_rows, st, [&](int n_nblk, int n_blocks) {
+      return std::make_tuple((const half_t*)out->xe, (const half_t*)out->y, E, (int64_t)g->y_rows, (int64_t)g->Dp, g->Dp / 64, n_nblk, n_blocks, mp);
+    }, n_pack);
+  }, Set<1, 2, 3>(), c.nt, Set<0, 1>(), c.big, Set<0, 1>(), c.two);
 }

@@ -30,6 +30,11 @@ struct aladin_packed;
 int aladin_internal_pack(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out, hipStream_t st);
 int aladin_internal_scores(const void* xm, const void* xe, const void* y, const aladin_align_geom* g, void* e_scratch, float* S,
                            int64_t ldS, int flags, void* stream);
+// align_fwd.hip: the triplet forward's prologue where the side GEMM launch also packs the main image rows (side_packs_main there)
+bool aladin_internal_side_packs_main(const aladin_set* im, const aladin_align_geom* g);
+int aladin_internal_pack_side_operands(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out, hipStream_t st);
+int aladin_internal_side_with_main_pack(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out, float* E,
+                                        hipStream_t st);
 int aladin_internal_align_argmax(const aladin_align_geom* g, const void* xm, const void* xe, const void* y, float* E,
                                  const int32_t* im_len, const int32_t* s_len, uint8_t* table, int tstride, uint8_t* flags, hipStream_t stream);
 
