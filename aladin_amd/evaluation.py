@@ -5,6 +5,8 @@
                                              the alignment_sim_fn closures train.py:495-498 / test.py:260-263
     recall / recall_test / compute_recall    <- alad/recall_auxiliary.py:8-149
     i2t / t2i                                <- alad/evaluation.py:158-327
+    search_topk                              new: the k best gallery items of every query from matching-head embeddings,
+                                             without the score matrix (ops.search_topk)
     AverageMeter / LogCollector              <- alad/evaluation.py:22-77 (host bookkeeping)
 
 The per-query Python loops, per-iteration host->device copies and numpy argsort of the reference
@@ -177,6 +179,25 @@ def compute_sim_matrix(img, cap, img_len=None, cap_len=None, mode='matching', pr
                 raise ValueError("compute_sim_matrix(mode='alignment') needs img_len and cap_len")
             return ops.alignment_scores(img, cap, list(img_len), list(cap_len), 'MrSw', precision=precision)
     raise ValueError("mode must be 'matching' or 'alignment'")
+
+
+def search_topk(images, captions, k=50, direction='i2t'):
+    """The k best gallery items of every query from matching-head embeddings, best first: (indices, scores) as an (n_q, k) int32
+    and an (n_q, k) float32 device tensor.  direction='i2t': the (n_img, D) images query the (n_cap, D) captions; 't2i': the
+    captions query the images.  The same entries as the first k of a stable descending sort of compute_sim_matrix(images,
+    captions) along the gallery axis (ties -> lower index; -1 / -inf past the gallery size), without the score matrix:
+    ops.search_topk, up to 589824 gallery items."""
+    if direction not in ('i2t', 't2i'):
+        raise ValueError("direction must be 'i2t' or 't2i'")
+    dev = _device()
+    if _is_packed_store(images) != _is_packed_store(captions):
+        raise ValueError('search_topk: pass two stores or two tensors')
+    if _is_packed_store(images):
+        images, captions = images.glob, captions.glob
+    img = torch.as_tensor(images).to(dev, torch.float32)
+    cap = torch.as_tensor(captions).to(dev, torch.float32)
+    with torch.no_grad():
+        return ops.search_topk(img, cap, k, dim=1 if direction == 'i2t' else 0, return_scores=True)
 
 
 def _metrics(ranks):

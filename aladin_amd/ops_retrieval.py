@@ -96,3 +96,38 @@ def topk_indices(scores, k, dim=1):
     _lib.check(_lib.load().aladin_topk(_ptr(sc), q_stride, c_stride, n_q, n_c, int(k), _ptr(out), _ptr(None), _stream()),
                'topk')
     return out
+
+
+SEARCH_MAX_K = 256
+SEARCH_MAX_GALLERY = 36864 * 16      # groups of 16 gallery items, at most topk's 36864 candidates of them
+
+
+def search_topk(img, cap, k, dim=1, return_scores=False):
+    """(n_q, k) int32 indices of each query's k best gallery items straight from the (n_img, D) / (n_cap, D) embeddings:
+    sim_matrix + topk_indices fused, the (n_img, n_cap) score matrix is never written and the gallery may hold up to
+    589824 items.  dim=1: images query the captions; dim=0: captions query the images (the operands keep their roles, as in
+    topk_indices(sim_matrix(img, cap), k, dim)).  Best first, ties -> lower index, -1 past the gallery size; the same ints as
+    the two-step path.  return_scores=True: (indices, scores), the scores bit-equal to sim_matrix's entries (-inf past the
+    gallery size)."""
+    if img.dim() != 2 or cap.dim() != 2 or img.shape[1] != cap.shape[1] or dim not in (0, 1):
+        raise ValueError('aladin_amd: search_topk expects (n_img,D) and (n_cap,D) embeddings and dim 0 or 1')
+    k = int(k)
+    if not 1 <= k <= SEARCH_MAX_K:
+        raise ValueError('aladin_amd: search_topk needs 1 <= k <= %d (got %d)' % (SEARCH_MAX_K, k))
+    n_img, n_cap, D = img.shape[0], cap.shape[0], img.shape[1]
+    n_q, n_g = (n_img, n_cap) if dim == 1 else (n_cap, n_img)
+    if n_g > SEARCH_MAX_GALLERY:
+        raise ValueError('aladin_amd: search_topk searches at most %d gallery items (got %d)' % (SEARCH_MAX_GALLERY, n_g))
+    if n_img < 1 or n_cap < 1 or D < 1:
+        raise ValueError('aladin_amd: search_topk needs non-empty embeddings')
+    _require_gpu(img, cap)                               # after the limits: they hold whatever the device
+    lib = _lib.load()
+    img = img if img.stride(1) == 1 else img.contiguous()
+    cap = cap if cap.stride(1) == 1 else cap.contiguous()
+    dev = img.device
+    idx = torch.empty((n_q, k), dtype=torch.int32, device=dev)
+    val = torch.empty((n_q, k), dtype=torch.float32, device=dev) if return_scores else None
+    ws = _workspace(lib.aladin_search_workspace_bytes(n_img, n_cap, D, k, dim), dev)
+    _lib.check(lib.aladin_search_topk(_ptr(img), _ld(img), _ptr(cap), _ld(cap), n_img, n_cap, D, k, dim, _ptr(idx), _ptr(val),
+                                      _ptr(ws), _stream()), 'search_topk')
+    return (idx, val) if return_scores else idx

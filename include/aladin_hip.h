@@ -464,6 +464,22 @@ ALADIN_API int aladin_retrieval_ranks_exact(const float* img, int64_t img_row_st
                            int n_cap, int D, int caps_per_img, int32_t* rank_i2t, int32_t* top1_i2t, int32_t* rank_t2i,
                            int32_t* top1_t2i, void* workspace, void* stream);
 
+/* Top-k gallery search straight from the embeddings: what aladin_sim_matrix + aladin_topk(..., out_val) give, bit for bit,
+ * without writing the (n_img x n_cap) score matrix and without aladin_topk's limit on the candidates of a query.
+ *   dim = 1: the n_img images are the queries, the captions the gallery;  dim = 0: the n_cap captions query the images
+ *   (the operands keep their roles, as in aladin_topk on sim with q_stride = 1).
+ *   out_idx (n_q x k int32): the k best gallery indices, best first, ties -> lower index, -1 past the gallery size;
+ *   out_val (n_q x k fp32, may be NULL): their scores, the bits aladin_sim_matrix would store, -inf past the gallery size.
+ *   NaN scores sort last.
+ * The gallery is cut into groups of 16 neighbours; one pass of the three-product GEMM leaves every group's maximum, the k
+ * best groups of a query hold its k best scores, a second pass collects them (csrc/search.hip).  No atomics: deterministic.
+ * Limits: 1 <= k <= 256; at most 36864 groups = 589824 gallery items (ALADIN_ERR_UNSUPPORTED above).
+ * workspace: aladin_search_workspace_bytes(n_img, n_cap, D, k, dim) (0 for arguments the call refuses): the packed operands
+ * of aladin_sim_workspace_bytes + 6 bytes per (query, group) + 72 per (query, selected group). */
+ALADIN_API size_t aladin_search_workspace_bytes(int n_img, int n_cap, int D, int k, int dim);
+ALADIN_API int aladin_search_topk(const float* img, int64_t img_row_stride, const float* cap, int64_t cap_row_stride, int n_img,
+                       int n_cap, int D, int k, int dim, int32_t* out_idx, float* out_val, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
