@@ -1,0 +1,269 @@
+// Alignment-head re-scoring of shortlists (aladin_align_rescore, aladin_rerank_order): the MrSw score (max over regions, sum
+// over words; reference alad/loss.py:80-125) of LISTED (image, caption) pairs, straight from two embedding stores (store.hip).
+// Work and memory are proportional to n_q * k: no operand is repacked, nothing of the size of the (n_q x gallery) grid exists.
+//
+// cand is an (n_q x k) table of gallery positions (the output of aladin_search_topk, -1 = no candidate).  dim = 1: query q is
+// image q, its candidates are captions; dim = 0: query q is caption q, its candidates are images.  The image is always the max
+// side and the MFMA's A operand (rows of the accumulator), the caption the sum side and the B operand (columns), so a pair's
+// accumulators -- and every bit of its score -- are the same whichever side was the query.
+//
+// Workgroup = one query x a chunk of NW candidates (NW = 8 waves, 4 where the LDS does not hold 8 panels), one wave per pair.
+// A sample's rows are contiguous in its store, so its operand panel is rows + offsets[id] * ldk: per 64-deep K step the query's
+// panel (read ONCE per workgroup) and the NW candidate panels go global -> LDS by LDS-DMA in the 8-row pieces and with the
+// XOR swizzle of gemm_core.hpp, double buffered, and come back as ds_read_b128 fragments (lds_frag16) of v_mfma_f32_16x16x32_f16.
+// Split rows [hi | lo] walk the chain hi.hi, lo.hi, hi.lo in one fp32 accumulator (KMapSplit, a = image, b = caption).
+//
+// Rows past a sample's count belong to the NEXT sample -- or lie past the end of the allocation for the last one: a piece's
+// per-lane source row is clamped to the sample's last row (gemm_stage_k's a_avail, per lane), pieces wholly past the count are
+// not fetched at all, and the epilogue SELECTS by count (rows >= count are left out of the max, words >= count add 0.0): what
+// an unfetched LDS row holds only reaches accumulator rows / columns that are never looked at.
+//
+// Epilogue, all in registers: word w of tile ct is column lane & 15; the max over the image's regions runs over the wave's row
+// tiles, the 4 registers and the 4 lane groups (exact, any order), starts from 0 for an image shorter than the padded set (the
+// zero fill of alad/loss.py:116,124) and from -inf for one that fills it; the sum over words is row16_sum per tile, tiles added
+// in ascending order.  One lane writes the pair's score once: no atomics, and nothing depends on the slot, the chunk, k or n_q.
+#include "../../include/aladin_hip.h"
+
+#include "sim_common.hpp"
+
+constexpr int RESCORE_MAX_K = 256;
+constexpr int RESCORE_MAX_COUNT = 96;                     // the tile classes' limit: six 16-row tiles per side
+constexpr int RESCORE_TILES = RESCORE_MAX_COUNT / 16;
+constexpr int RESCORE_LDS_LIMIT = 160 * 1024;
+constexpr float RESCORE_SPLIT_UNSCALE = 1.0f / (16384.0f * 16384.0f);      // split rows carry 2^14 each (store.hip, align_fwd.hip)
+
+struct RescoreSide {
+  const half_t* rows;
+  const int64_t* offsets;
+  const int32_t* counts;
+  const int32_t* ids;      // view position -> sample, or nullptr
+  int n;                   // samples in the view
+  int cmax;                // host-known bound of the counts (<= 96): counts are clamped to it
+  int prows;               // LDS rows of one panel: round_up(cmax, 16)
+};
+
+// field by field: selecting whole kernel-argument structs by a run-time value would send them through scratch memory
+__device__ __forceinline__ RescoreSide rescore_pick(bool first, const RescoreSide& a, const RescoreSide& b) {
+  return RescoreSide{first ? a.rows : b.rows, first ? a.offsets : b.offsets, first ? a.counts : b.counts, first ? a.ids : b.ids,
+                     first ? a.n : b.n, first ? a.cmax : b.cmax, first ? a.prows : b.prows};
+}
+
+// One 64-deep K step of a sample's panel -> LDS rows [lds_row0, lds_row0 + 8 * ceil(cnt / 8)), pieces p0, p0 + pstep, ...
+// lds_row0 is a multiple of 16, so piece p's swizzle parity is p & 1 (stage_lane_offset, gemm_core.hpp).
+__device__ __forceinline__ void rescore_stage(const half_t* __restrict__ panel, int cnt, int64_t ldk, int64_t k_off, char* stage, int lds_row0,
+                                              int p0, int pstep, int lane) {
+  const int r = lane >> 3;
+  const int npieces = (cnt + 7) >> 3;
+  for (int p = p0; p < npieces; p += pstep) {                                  // wave-uniform
+    const int row = min(8 * p + r, cnt - 1);                                   // never past the sample's last row
+    const int logical = (lane & 7) ^ (((r >> 1) ^ ((p & 1) << 2)) & 7);
+    const half_t* src = panel + (int64_t)row * ldk + k_off + logical * 8;
+    __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src), LDS_PTR(stage + (lds_row0 + 8 * p) * 128), 16, 0, 0);
+  }
+}
+
+__global__ __launch_bounds__(512) void rescore_kernel(RescoreSide x, RescoreSide y, const int32_t* __restrict__ cand, int k, int dim,
+                                                      int x_full, int64_t ldk, int kps, int split, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int nw = blockDim.x >> 6;
+  const int nchunk = (k + nw - 1) / nw;
+  const int q = blockIdx.x / nchunk;
+  const int slot = (blockIdx.x - q * nchunk) * nw + wave;
+  const RescoreSide sh = rescore_pick(dim == 1, x, y);     // the query's side, shared by the workgroup
+  const RescoreSide ga = rescore_pick(dim == 1, y, x);     // the candidates' side, one panel per wave
+  const int stage_bytes = (sh.prows + nw * ga.prows) * 128;
+  const int g_row0 = sh.prows + wave * ga.prows;
+
+  const int sq = sh.ids ? sh.ids[q] : q;
+  const int cnt_s = min(max(sh.counts[sq], 0), sh.cmax);
+  const half_t* pan_s = sh.rows + sh.offsets[sq] * ldk;
+  const int c = __builtin_amdgcn_readfirstlane(slot < k ? cand[(int64_t)q * k + slot] : -1);      // one pair per wave: uniform
+  const bool live = c >= 0 && c < ga.n;
+  int cnt_g = 0;
+  const half_t* pan_g = ga.rows;
+  if (live) {
+    const int sg = ga.ids ? ga.ids[c] : c;
+    cnt_g = min(max(ga.counts[sg], 0), ga.cmax);
+    pan_g = ga.rows + ga.offsets[sg] * ldk;
+  }
+  cnt_g = __builtin_amdgcn_readfirstlane(cnt_g);
+  const int cnt_x = dim == 1 ? cnt_s : cnt_g, cnt_y = dim == 1 ? cnt_g : cnt_s;
+  const int nrt = live ? (cnt_x + 15) >> 4 : 0, nct = live ? (cnt_y + 15) >> 4 : 0;      // 16-row tiles of this pair
+  const int a_row0 = (dim == 1 ? 0 : g_row0) + (lane & 15), b_row0 = (dim == 1 ? g_row0 : 0) + (lane & 15);
+
+  f32x4 acc[RESCORE_TILES][RESCORE_TILES];
+#pragma unroll
+  for (int rt = 0; rt < RESCORE_TILES; ++rt)
+#pragma unroll
+    for (int ct = 0; ct < RESCORE_TILES; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const KMapSplit km{kps, 0};
+  const int ktiles = split ? 3 * kps : kps;
+  // K offsets of the image (a) and caption (b) rows; the shared / gathered panels take the one of their side
+  auto k_sh = [&](int kt) { return split ? (dim == 1 ? km.a(kt) : km.b(kt)) : (int64_t)kt * 64; };
+  auto k_ga = [&](int kt) { return split ? (dim == 1 ? km.b(kt) : km.a(kt)) : (int64_t)kt * 64; };
+  rescore_stage(pan_s, cnt_s, ldk, k_sh(0), smem, 0, wave, nw, lane);
+  rescore_stage(pan_g, cnt_g, ldk, k_ga(0), smem, g_row0, 0, 1, lane);
+  for (int kt = 0; kt < ktiles; ++kt) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                          // step kt is in LDS for every wave; every wave is done with step kt - 1
+    const char* cur = smem + (kt & 1) * stage_bytes;
+    if (kt + 1 < ktiles) {
+      char* nxt = smem + ((kt + 1) & 1) * stage_bytes;
+      rescore_stage(pan_s, cnt_s, ldk, k_sh(kt + 1), nxt, 0, wave, nw, lane);
+      rescore_stage(pan_g, cnt_g, ldk, k_ga(kt + 1), nxt, g_row0, 0, 1, lane);
+    }
+#pragma unroll
+    for (int k32 = 0; k32 < 2; ++k32) {
+      half8 a[RESCORE_TILES], b[RESCORE_TILES];
+#pragma unroll
+      for (int t = 0; t < RESCORE_TILES; ++t) {
+        a[t] = half8{0, 0, 0, 0, 0, 0, 0, 0};
+        b[t] = half8{0, 0, 0, 0, 0, 0, 0, 0};
+        if (t < nrt) a[t] = lds_frag16(cur, a_row0 + t * 16, k32, lane);
+        if (t < nct) b[t] = lds_frag16(cur, b_row0 + t * 16, k32, lane);
+      }
+#pragma unroll
+      for (int rt = 0; rt < RESCORE_TILES; ++rt) {
+        if (rt >= nrt) continue;
+#pragma unroll
+        for (int ct = 0; ct < RESCORE_TILES; ++ct)
+          if (ct < nct) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[rt], b[ct], acc[rt][ct], 0, 0, 0);
+      }
+    }
+  }
+
+  if (slot >= k) return;
+  float total = -INFINITY;
+  if (live) {
+    total = 0.0f;
+    const float floor_ = cnt_x < x_full ? 0.0f : -INFINITY;                    // the zero fill of an image shorter than the padded set
+    const int row0 = 4 * (lane >> 4);
+#pragma unroll
+    for (int ct = 0; ct < RESCORE_TILES; ++ct) {
+      if (ct >= nct) continue;
+      float m = floor_;
+#pragma unroll
+      for (int rt = 0; rt < RESCORE_TILES; ++rt) {
+        if (rt >= nrt) continue;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const float v = rt * 16 + row0 + reg < cnt_x ? acc[rt][ct][reg] : -INFINITY;      // selected, never multiplied
+          m = fmax_nc(m, v);
+        }
+      }
+      m = fmax_nc(m, lane_xor16(m));
+      m = fmax_nc(m, lane_xor32(m));
+      const float wv = ct * 16 + (lane & 15) < cnt_y ? m : 0.0f;
+      total += row16_sum(wv);
+    }
+    if (split) total *= RESCORE_SPLIT_UNSCALE;                                 // exact: a power of two
+  }
+  if (lane == 0) out[(int64_t)q * k + slot] = total;
+}
+
+// ------------------------------------------------------------------------------------------------
+// One workgroup per query: the stable descending order of its re-scored shortlist.  Entry t goes to position
+// #{j : j precedes t}, j precedes t when it is a candidate and t is none, or both are alike and score_j > score_t, or the
+// scores are equal and j < t (the earlier shortlist slot: the matching head breaks ties).  NaN counts as -inf.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rerank_order_kernel(const int32_t* __restrict__ cand, const float* __restrict__ scores, int k,
+                                                           int32_t* __restrict__ out_idx, float* __restrict__ out_val) {
+  __shared__ float val[RESCORE_MAX_K];
+  __shared__ int idx[RESCORE_MAX_K];
+  const int q = blockIdx.x, t = threadIdx.x;
+  if (t < k) {
+    const int c = cand[(int64_t)q * k + t];
+    float v = scores[(int64_t)q * k + t];
+    if (!(v == v) || c < 0) v = -INFINITY;
+    val[t] = v;
+    idx[t] = c < 0 ? -1 : c;
+  }
+  __syncthreads();
+  if (t < k) {
+    const float v = val[t];
+    const bool none = idx[t] < 0;
+    int rank = 0;
+    for (int j = 0; j < k; ++j) {
+      const bool jnone = idx[j] < 0;
+      const bool before = jnone != none ? none : (val[j] > v || (val[j] == v && j < t));
+      rank += before;
+    }
+    out_idx[(int64_t)q * k + rank] = idx[t];
+    out_val[(int64_t)q * k + rank] = v;
+  }
+}
+
+static int rescore_waves(int sh_rows, int ga_rows) {
+  for (int nw = 8; nw >= 4; nw >>= 1)
+    if (2 * (sh_rows + nw * ga_rows) * 128 <= RESCORE_LDS_LIMIT) return nw;
+  return 0;
+}
+
+extern "C" int aladin_align_rescore(const void* x_rows, const int64_t* x_offsets, const int32_t* x_counts, const int32_t* x_ids, int n_x,
+                                    int x_max_count, const void* y_rows, const int64_t* y_offsets, const int32_t* y_counts,
+                                    const int32_t* y_ids, int n_y, int y_max_count, int D, int precision, int dim, int x_full,
+                                    const int32_t* cand, int k, float* out, void* stream) {
+  if (!x_rows || !x_offsets || !x_counts || !y_rows || !y_offsets || !y_counts || !cand || !out || n_x < 1 || n_y < 1 || D < 1 ||
+      (dim != 0 && dim != 1) || (precision != ALADIN_PRECISION_FP16 && precision != ALADIN_PRECISION_SPLIT) || x_full < 1 ||
+      x_max_count < 0 || y_max_count < 0) {
+    aladin_set_error("align_rescore: bad argument (n_x=%d n_y=%d D=%d precision=%d dim=%d x_full=%d; null table or output, dim 0 or 1)", n_x,
+                     n_y, D, precision, dim, x_full);
+    return ALADIN_ERR_ARG;
+  }
+  if (k < 1 || k > RESCORE_MAX_K) {
+    aladin_set_error("align_rescore: 1 <= k <= %d candidates per query, got %d", RESCORE_MAX_K, k);
+    return ALADIN_ERR_UNSUPPORTED;
+  }
+  if (x_max_count > RESCORE_MAX_COUNT || y_max_count > RESCORE_MAX_COUNT) {
+    aladin_set_error("align_rescore: at most %d scored positions per set, got %d regions / %d words", RESCORE_MAX_COUNT, x_max_count,
+                     y_max_count);
+    return ALADIN_ERR_UNSUPPORTED;
+  }
+  const int width = aladin_store_row_width(D, precision);
+  if (width < D) {
+    aladin_set_error("align_rescore: feature size %d is not one a store holds", D);
+    return ALADIN_ERR_UNSUPPORTED;
+  }
+  const int split = precision == ALADIN_PRECISION_SPLIT;
+  const int Dp = split ? width / 2 : width;
+  if (Dp % 64) {
+    aladin_set_error("align_rescore: store rows of %d halfs are not whole 64-deep K steps", Dp);
+    return ALADIN_ERR_UNSUPPORTED;
+  }
+  RescoreSide x{(const half_t*)x_rows, x_offsets, x_counts, x_ids, n_x, x_max_count, round_up(x_max_count > 0 ? x_max_count : 1, 16)};
+  RescoreSide y{(const half_t*)y_rows, y_offsets, y_counts, y_ids, n_y, y_max_count, round_up(y_max_count > 0 ? y_max_count : 1, 16)};
+  const int sh_rows = dim == 1 ? x.prows : y.prows, ga_rows = dim == 1 ? y.prows : x.prows;
+  const int nw = rescore_waves(sh_rows, ga_rows);
+  if (!nw) {
+    aladin_set_error("align_rescore: no chunk of %d + n x %d rows fits the LDS", sh_rows, ga_rows);
+    return ALADIN_ERR_UNSUPPORTED;
+  }
+  static unsigned long long lds_reserved = 0;
+  if (int rc = aladin_reserve_lds((const void*)rescore_kernel, RESCORE_LDS_LIMIT, &lds_reserved, "rescore_kernel")) return rc;
+  const int n_q = dim == 1 ? n_x : n_y;
+  const int64_t blocks = (int64_t)n_q * cdiv(k, nw);
+  if (blocks > 0x7fffffff) {
+    aladin_set_error("align_rescore: %d queries x %d candidates are more workgroups than one launch takes", n_q, k);
+    return ALADIN_ERR_UNSUPPORTED;
+  }
+  hipLaunchKernelGGL(rescore_kernel, dim3((unsigned)blocks), dim3(nw * 64), 2 * (sh_rows + nw * ga_rows) * 128, (hipStream_t)stream, x, y,
+                     cand, k, dim, x_full, (int64_t)width, Dp / 64, split, out);
+  return aladin_check_launch("rescore_kernel");
+}
+
+extern "C" int aladin_rerank_order(const int32_t* cand, const float* scores, int n_q, int k, int32_t* out_idx, float* out_val,
+                                   void* stream) {
+  if (!cand || !scores || !out_idx || !out_val || n_q < 1) {
+    aladin_set_error("rerank_order: bad argument (n_q=%d; null table or output)", n_q);
+    return ALADIN_ERR_ARG;
+  }
+  if (k < 1 || k > RESCORE_MAX_K) {
+    aladin_set_error("rerank_order: 1 <= k <= %d candidates per query, got %d", RESCORE_MAX_K, k);
+    return ALADIN_ERR_UNSUPPORTED;
+  }
+  hipLaunchKernelGGL(rerank_order_kernel, dim3(n_q), dim3(256), 0, (hipStream_t)stream, cand, scores, k, out_idx, out_val);
+  return aladin_check_launch("rerank_order_kernel");
+}

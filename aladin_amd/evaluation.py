@@ -200,6 +200,24 @@ def search_topk(images, captions, k=50, direction='i2t'):
         return ops.search_topk(img, cap, k, dim=1 if direction == 'i2t' else 0, return_scores=True)
 
 
+def search_rerank(images, captions, k=50, direction='i2t', shortlist=None):
+    """Two-stage retrieval over two PackedSetStore / StoreView objects: (indices, scores) as an (n_q, k) int32 and an (n_q, k)
+    float32 device tensor, best first by the ALIGNMENT head.  The shortlist of every query is search_topk(images, captions, k,
+    direction) on the stores' matching-head embeddings (shortlist=None) or the caller's (n_q, k) int32 table of gallery
+    positions (-1 = none); its pairs are scored straight from the stores (store.alignment_scores_for_pairs) and ordered by
+    score, ties -> the earlier shortlist slot, -1 / -inf last.  Nothing of the size of the (n_q, gallery) grid is computed."""
+    if direction not in ('i2t', 't2i'):
+        raise ValueError("direction must be 'i2t' or 't2i'")
+    if not (_is_packed_store(images) and _is_packed_store(captions)):
+        raise ValueError('search_rerank: pass two stores / views (encode_data_packed), not tensors')
+    from .store import alignment_scores_for_pairs
+    with torch.no_grad():
+        if shortlist is None:
+            shortlist, _ = search_topk(images, captions, k, direction)
+        scores = alignment_scores_for_pairs(images, captions, shortlist, direction)
+        return ops.rerank_order(shortlist, scores)
+
+
 def _metrics(ranks):
     ranks = np.asarray(ranks, dtype=np.float64)
     r1 = 100.0 * len(np.where(ranks < 1)[0]) / len(ranks)

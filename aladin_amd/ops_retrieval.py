@@ -131,3 +131,61 @@ def search_topk(img, cap, k, dim=1, return_scores=False):
     _lib.check(lib.aladin_search_topk(_ptr(img), _ld(img), _ptr(cap), _ld(cap), n_img, n_cap, D, k, dim, _ptr(idx), _ptr(val),
                                       _ptr(ws), _stream()), 'search_topk')
     return (idx, val) if return_scores else idx
+
+
+RESCORE_MAX_K = 256
+RESCORE_MAX_COUNT = 96               # scored positions per set: the tile classes' limit
+
+
+def _check_shortlist(cand, n_q=None):
+    if not isinstance(cand, torch.Tensor) or cand.dim() != 2 or cand.dtype != torch.int32:
+        raise ValueError('aladin_amd: the shortlist must be an (n_q, k) int32 tensor')
+    if n_q is not None and cand.shape[0] != n_q:
+        raise ValueError('aladin_amd: the shortlist has %d rows for %d queries' % (cand.shape[0], n_q))
+    if not 1 <= cand.shape[1] <= RESCORE_MAX_K:
+        raise ValueError('aladin_amd: a shortlist holds 1 <= k <= %d candidates per query (got %d)' % (RESCORE_MAX_K, cand.shape[1]))
+
+
+def align_rescore(x, y, cand, dim, D, precision, x_full, out=None):
+    """(n_q, k) float32 alignment-head (MrSw) scores of the listed pairs straight from two embedding stores -- no repacking,
+    nothing of the size of the (n_q, gallery) grid.  x / y: the image / caption side as (rows, offsets, counts, ids or None,
+    samples in the view, largest count); cand: (n_q, k) int32 gallery-view positions, -1 = none (-inf in the output);
+    dim=1: images query captions, dim=0: captions query images.  out: a preallocated result (graph capture).
+    aladin_amd.store.alignment_scores_for_pairs is the front end."""
+    if dim not in (0, 1):
+        raise ValueError('aladin_amd: align_rescore takes dim 0 or 1')
+    n_q = x[4] if dim == 1 else y[4]
+    _check_shortlist(cand, n_q)
+    if x[5] > RESCORE_MAX_COUNT or y[5] > RESCORE_MAX_COUNT:
+        raise ValueError('aladin_amd: align_rescore scores sets of at most %d positions (got %d regions, %d words)'
+                         % (RESCORE_MAX_COUNT, x[5], y[5]))
+    if not cand.is_cuda:
+        raise RuntimeError('aladin_amd: the shortlist must live on the GPU (no CPU fallback exists)')
+    cand = cand.contiguous()
+    if out is None:
+        out = torch.empty(cand.shape, dtype=torch.float32, device=cand.device)
+    elif out.shape != cand.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError('aladin_amd: align_rescore needs a contiguous float32 output of the shortlist\'s shape')
+    from .ops import _precision_code
+    _lib.check(_lib.load().aladin_align_rescore(_ptr(x[0]), _ptr(x[1]), _ptr(x[2]), _ptr(x[3]), int(x[4]), int(x[5]),
+                                                _ptr(y[0]), _ptr(y[1]), _ptr(y[2]), _ptr(y[3]), int(y[4]), int(y[5]),
+                                                int(D), _precision_code(precision), int(dim), int(x_full), _ptr(cand),
+                                                cand.shape[1], _ptr(out), _stream()), 'align_rescore')
+    return out
+
+
+def rerank_order(cand, scores, out_idx=None, out_val=None):
+    """(indices, scores): every row of the shortlist `cand` and of its scores in descending score order -- a stable sort, ties go
+    to the earlier shortlist slot; -1 entries last, as -1 / -inf.  out_idx / out_val: preallocated results (graph capture)."""
+    _check_shortlist(cand)
+    if not isinstance(scores, torch.Tensor) or scores.shape != cand.shape or scores.dtype != torch.float32:
+        raise ValueError('aladin_amd: rerank_order needs float32 scores of the shortlist\'s shape')
+    _require_gpu(scores)
+    cand, scores = cand.contiguous(), scores.contiguous()
+    if out_idx is None:
+        out_idx = torch.empty_like(cand)
+    if out_val is None:
+        out_val = torch.empty_like(scores)
+    _lib.check(_lib.load().aladin_rerank_order(_ptr(cand), _ptr(scores), cand.shape[0], cand.shape[1], _ptr(out_idx), _ptr(out_val),
+                                               _stream()), 'rerank_order')
+    return out_idx, out_val

@@ -231,3 +231,30 @@ def _store_scores_block(img, cap):
                                                  ops._ptr(y), ops._stream()), 'align_pack_store_y')
         ops.scores_from_packed(xm, xe, y, g, out=S[:, j0:j1])
     return S
+
+
+def alignment_scores_for_pairs(img, cap, cand, direction='i2t'):
+    """(n_q, k) float32 'MrSw' scores of LISTED pairs between two stores / views: direction='i2t' scores image q against the
+    captions cand[q, :], 't2i' caption q against the images cand[q, :].  cand: (n_q, k) int32 device tensor of positions in the
+    gallery view (a search_topk shortlist), -1 = no candidate (-inf in the result).  The rows are read where they lie in the
+    stores (ops.align_rescore): work and memory follow n_q * k, not the grid, and a pair's bits do not depend on where it is
+    listed.  Semantics are those of _store_scores_block (zero fill for images shorter than the padded set included)."""
+    from .evaluation import _is_packed_store
+    if not (_is_packed_store(img) and _is_packed_store(cap)):
+        raise ValueError('aladin_amd: alignment_scores_for_pairs takes two stores / views, not tensors')
+    if direction not in ('i2t', 't2i'):
+        raise ValueError("direction must be 'i2t' or 't2i'")
+    si, ids_i, idt_i = _unwrap(img)
+    sc, ids_c, idt_c = _unwrap(cap)
+    if si.D != sc.D:
+        raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (si.D, sc.D))
+    if si.precision != sc.precision:
+        raise ValueError('aladin_amd: the two stores hold different precisions (%s vs %s)' % (si.precision, sc.precision))
+    if len(img) < 1 or len(cap) < 1:
+        raise ValueError('aladin_amd: empty store')
+    ops._check_shortlist(cand, len(img) if direction == 'i2t' else len(cap))
+    oi, ci = si._tables()
+    oc, cc = sc._tables()
+    x = (si.rows, oi, ci, idt_i, len(img), si.max_count(ids_i))
+    y = (sc.rows, oc, cc, idt_c, len(cap), sc.max_count(ids_c))
+    return ops.align_rescore(x, y, cand, 1 if direction == 'i2t' else 0, si.D, si.precision, si.padded_len - 1 - si.tail)

@@ -480,6 +480,30 @@ ALADIN_API size_t aladin_search_workspace_bytes(int n_img, int n_cap, int D, int
 ALADIN_API int aladin_search_topk(const float* img, int64_t img_row_stride, const float* cap, int64_t cap_row_stride, int n_img,
                        int n_cap, int D, int k, int dim, int32_t* out_idx, float* out_val, void* workspace, void* stream);
 
+/* Two-stage retrieval: alignment-head (MrSw) scores of LISTED pairs straight from two embedding stores, and the order of
+ * every query's re-scored shortlist (csrc/rescore.hip).  Work and memory are proportional to n_q * k; no operand is repacked.
+ *   x_* / y_*: the image / caption store as aladin_align_pack_store_x / _y take it (rows, offsets, counts, ids: view position
+ *   -> sample, may be NULL), n_x / n_y the samples in the view, x_max_count / y_max_count a bound of their counts known to
+ *   the host (the kernel clamps to it), D and precision those of BOTH stores.
+ *   dim = 1: the n_x images are the queries and cand holds caption positions; dim = 0: the n_y captions query the images.
+ *   cand (n_q x k int32): positions in the gallery view, -1 (or anything outside the view) = no candidate.
+ *   x_full: the count at which an image fills the padded set (padded_len - 1 - tail); a shorter image takes the zero fill
+ *   into every max over its regions (alad/loss.py:116,124).
+ *   out (n_q x k fp32): the score of image q and caption cand[q][s] (dim = 1) / of image cand[q][s] and caption q (dim = 0);
+ *   -inf where there is no candidate; exactly 0.0 for a caption without scored words.
+ * A pair's bits depend on the pair alone: not on its slot, the other candidates, k, the number of queries or dim.
+ * Limits (ALADIN_ERR_UNSUPPORTED past them, checked before any launch): 1 <= k <= 256, counts <= 96 on both sides, D one
+ * that aladin_store_row_width accepts.  No allocation, no synchronisation, no atomics: graph-capturable.
+ *
+ * aladin_rerank_order: out_idx / out_val (n_q x k) = cand / scores of every query in descending score order, ties -> the
+ * earlier shortlist slot (a stable sort), entries without a candidate last as -1 / -inf; NaN counts as -inf. */
+ALADIN_API int aladin_align_rescore(const void* x_rows, const int64_t* x_offsets, const int32_t* x_counts, const int32_t* x_ids, int n_x,
+                         int x_max_count, const void* y_rows, const int64_t* y_offsets, const int32_t* y_counts,
+                         const int32_t* y_ids, int n_y, int y_max_count, int D, int precision, int dim, int x_full,
+                         const int32_t* cand, int k, float* out, void* stream);
+ALADIN_API int aladin_rerank_order(const int32_t* cand, const float* scores, int n_q, int k, int32_t* out_idx, float* out_val,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
