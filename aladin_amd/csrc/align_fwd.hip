@@ -10,16 +10,21 @@
 //                  * rows that exist only to fill a 32-row MFMA tile are COPIES of the image's
 //                    first region (max is idempotent), never zeros: a zero would wrongly clamp
 //                    the max of an image without padded regions.
-// score kernel   one (8 images x 4 captions)-class tile per workgroup: LDS-staged fp16 MFMA GEMM
-//                (gemm_core.hpp) with regions on the MFMA row axis and words on the lane axis, so
-//                max-over-regions is an in-lane max over the 16 accumulator registers plus one
-//                half-wave exchange, and sum-over-words is a 32-lane shuffle reduction.  The
-//                B x B x R' x T' tensor of the reference never exists.
-//                Variants of the 16x16x32 body on the same 256 x 384 workgroup tile and LDS image (scores are
-//                bit-identical across them: same MFMA shape, K order and epilogue arithmetic):
-//                  align_scores16_tall_kernel   8 waves of 128 x 96 (headline class: 14 LDS fragment reads per 32-deep step)
-//                  align_scores16_kernel<4,2,2> 8 waves of 64 x 192 (16 reads; classes whose captions do not tile 96 columns)
-//                  align_scores16_kernel<2,1,3> 128 x 192 tile, two waves, three-stage ring: grids of <= 64 big tiles (B <= 64)
+// score kernel   one tile of whole images x whole captions per workgroup: LDS-staged fp16 MFMA GEMM (gemm_core.hpp) with regions
+//                on the MFMA row axis and words on the lane axis, so max-over-regions is an in-lane max over the accumulator
+//                registers plus one or two lane exchanges, and sum-over-words is a 16-lane reduction.  The B x B x R' x T'
+//                tensor of the reference never exists.
+//                Bodies (select_scores picks one from the class table of aladin_align_geometry and the grid size).  The
+//                16x16x32 ones share one LDS image, one K order and one epilogue arithmetic (scores16_epilogue; the r48 body's own
+//                scores16_epilogue_r48 does the same operations in the same order), so a score is bit-identical whichever computed it:
+//                  align_scores16_tall_kernel   128 x 96 wave tiles, 2 x 4 waves = 256 x 384 (headline class: 14 LDS fragment
+//                                               reads per 32-deep step); 128 x 80 for 40-word captions, 1 x 2 waves on their small grids
+//                  align_scores16_kernel        64 x 192 wave tiles: 4 x 2 waves (16 reads; captions that do not tile 96 columns),
+//                                               or 2 x 1 waves with a three-stage ring on grids of <= 64 big tiles (B <= 64)
+//                  align_scores16_r48_kernel    the 48-row region class: 96 x 96 (96 x 80) wave tiles, 2 x 4 or 1 x 2 waves
+//                  align_scores16_r48x3_kernel  48 rows x 40 words on large grids: 144 x 80 wave tiles, 288 x 320 per workgroup
+//                  align_scores_kernel          v_mfma_f32_32x32x16_f16, the 96-row region class (an epilogue of its own)
+//                align_argmax16_{tall,r48}_kernel: the same tiles and main loop, recording WHICH region won (argmax16_epilogue).
 // side GEMM      R' = 33 = 32 + 1: the 33rd region of every image is gathered into one extra
 //                operand (one row per image) whose plain GEMM against the captions (E) is folded
 //                into the max by the score kernel -- 33/32 of the MFMA work instead of 64/32.
@@ -380,8 +385,8 @@ ALADIN_DIAG_API int aladin_debug_read_clock_probe(unsigned long long* host_out, 
 #endif  // ALADIN_DIAG
 
 // ------------------------------------------------------------------------------------------------
-// score kernel, v_mfma_f32_32x32x16_f16 body (the 96-row region class: R' 66..96)
-//   WM   M-tiles (32 rows) per wave;  Q  M-tiles per image;  images per wave = WM / Q  (2 or 1)
+// score kernel, v_mfma_f32_32x32x16_f16 body (the 96-row region class: R' 66..96, no side rows)
+//   WM   M-tiles (32 rows) per wave = Q, the M-tiles per image: a wave's rows are ONE image
 //   TP16 padded words per caption / 16;  a wave's column strip holds CPS = 1 or 2 whole captions
 // ------------------------------------------------------------------------------------------------
 template <int WM, int Q, int TP16, bool HAS_E>
@@ -389,12 +394,10 @@ __global__ __launch_bounds__(512) void align_scores_kernel(const half_t* __restr
                                                            const float* __restrict__ E, int64_t ldE,
                                                            float* __restrict__ S, int64_t ldS, int Bi, int Bc,
                                                            int64_t ldk, int ktiles, int n_nblk, int n_blocks) {
+  static_assert(WM == Q && !HAS_E, "one image per wave and no side rows: the one class this body serves (E and ldE are not read)");
   constexpr int WGM = 4;
   constexpr int NT = (TP16 & 1) ? TP16 : TP16 / 2;
   constexpr int CPS = (TP16 & 1) ? 2 : 1;
-  constexpr int IPW = WM / Q;
-  static_assert(IPW == 1 || IPW % 2 == 0, "one image or pairs of images per wave");
-  constexpr int NPAIR = IPW == 1 ? 1 : IPW / 2;
   using Cfg = GemmCfg<WGM, 2, WM, NT>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -415,39 +418,20 @@ __global__ __launch_bounds__(512) void align_scores_kernel(const half_t* __restr
 
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int wm = wave / 2, wn = wave % 2;
-  const int half = lane >> 5, l5 = lane & 31;
+  const int l5 = lane & 31;
 
-  // max over regions: 16 accumulator rows per lane, then the other half-wave's 16 rows.  Images are
-  // handled in pairs: one v_permlane32_swap leaves image 2p in lanes 0-31 and image 2p+1 in lanes 32-63.
+  // max over regions: 16 accumulator rows per lane and M-tile, then the other half-wave's
+  float m[NT];
 #pragma unroll
-  for (int pr = 0; pr < NPAIR; ++pr) {
-    float m[NT];
-    if constexpr (IPW >= 2) {
+  for (int n = 0; n < NT; ++n) {
+    float p = acc[0][n][0];
 #pragma unroll
-      for (int n = 0; n < NT; ++n) {
-        float p0 = acc[2 * pr][n][0], p1 = acc[2 * pr + 1][n][0];
+    for (int a = 0; a < WM; ++a)
 #pragma unroll
-        for (int r = 1; r < 16; ++r) { p0 = fmaxf(p0, acc[2 * pr][n][r]); p1 = fmaxf(p1, acc[2 * pr + 1][n][r]); }
-        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-        m[n] = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-      }
-    } else {
-#pragma unroll
-      for (int n = 0; n < NT; ++n) {
-        float p = acc[0][n][0];
-#pragma unroll
-        for (int a = 0; a < WM; ++a)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) p = fmaxf(p, acc[a][n][r]);
-        m[n] = fmaxf(p, __shfl_xor(p, 32, 64));
-      }
-    }
-    const int img = (mb * WGM + wm) * IPW + (IPW >= 2 ? 2 * pr + half : 0);
-    if constexpr (HAS_E) {
-      const float* e = E + (int64_t)img * ldE + (int64_t)nb * Cfg::BN + wn * NT * 32 + l5;
-#pragma unroll
-      for (int n = 0; n < NT; ++n) m[n] = fmaxf(m[n], e[n * 32]);
-    }
+      for (int r = 0; r < 16; ++r) p = fmaxf(p, acc[a][n][r]);
+    m[n] = fmaxf(p, __shfl_xor(p, 32, 64));
+  }
+  const int img = mb * WGM + wm;
 
   // sum over words: 16-lane groups map to captions at compile time
   float v[CPS];
@@ -463,8 +447,7 @@ __global__ __launch_bounds__(512) void align_scores_kernel(const half_t* __restr
 #pragma unroll
   for (int c = 0; c < CPS; ++c) {
     const float t = half_wave_sum(v[c]);
-    if (l5 == 0 && (IPW >= 2 || half == 0) && img < Bi && cap + c < Bc) S[(int64_t)img * ldS + cap + c] = t;
-  }
+    if (lane == 0 && img < Bi && cap + c < Bc) S[(int64_t)img * ldS + cap + c] = t;
   }
 }
 
@@ -483,13 +466,14 @@ __device__ __forceinline__ float max_xor32(float m) {
   return vmax(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
 }
 
-// max of the eight values a lane holds of one image and one column (two 16-row tiles x four registers), written as a chain
-// so that the compiler emits v_max3_f32 (4 instructions instead of 7; max is exact in any order)
-__device__ __forceinline__ float max8(const f32x4& a, const f32x4& b) {
-  float t = vmax(vmax(a[0], a[1]), a[2]);
-  t = vmax(vmax(t, a[3]), b[0]);
-  t = vmax(vmax(t, b[1]), b[2]);
-  return vmax(t, b[3]);
+// max of the values a lane holds of one image and one column -- TPI 16-row tiles from t0 on, four registers each -- written as
+// one chain so that the compiler emits v_max3_f32 (4 instructions for 8 values instead of 7; max is exact in any order)
+template <int TPI, int RT, int CT>
+__device__ __forceinline__ float image_max(const f32x4 (&acc)[RT][CT], int t0, int ct) {
+  float t = acc[t0][ct][0];
+#pragma unroll
+  for (int i = 1; i < 4 * TPI; ++i) t = vmax(t, acc[t0 + i / 4][ct][i % 4]);
+  return t;
 }
 
 // Word sums of the "half" caption classes (8, 24 and 40 words: trows = 16 TP16 - 8): two captions share 2 TP16 - 1 column tiles,
@@ -508,118 +492,90 @@ __device__ __forceinline__ void caption_add(float (&v)[NC], int ct, int l4, floa
 }
 
 // ------------------------------------------------------------------------------------------------
-// score kernel, v_mfma_f32_16x16x32_f16 body, for every class with one or two 32-row region tiles per image
-// (R' <= 64, plus the side row: Q = 1 -> a wave's 64 rows are two images, Q = 2 -> one) and captions of TP16 = 1, 2, 3, 4 or 6 sixteen-word tiles (headline: 3 = 48 words):
-// 256 x 384 workgroup tile (8 waves: 4 x 2; wave = 2 images x 12/TP16 captions = 4 x 12 accumulator
-// tiles of 16 x 16).
-//   max over regions : in-lane over 2 row tiles x 4 registers, v_permlane32_swap pairs the wave's two
-//                      images into the two half-waves, one 16-lane exchange finishes the 32 rows
-//   sum over words   : a caption is exactly TP16 column tiles -> in-lane adds, then a 16-lane reduction
+// score kernels, v_mfma_f32_16x16x32_f16 bodies: the epilogue of all of them.  A wave holds Cfg::RT16 x Cfg::CT16 accumulator
+// tiles of 16 x 16: RT16 / TPI images of TPI row tiles each (TPI = 2: 32 main rows, 3: 48, 4: 64) x whole captions.
+//   max over regions : in-lane over an image's TPI row tiles x 4 registers (image_max).  Images are finished in pairs:
+//                      v_permlane32_swap gathers the first into lanes 0-31 and the second into lanes 32-63; an odd last image
+//                      is finished by both half-waves.  One 16-lane exchange completes the rows; the side rows join from E.
+//   sum over words   : a caption's column tiles in ascending order, in-lane (caption_add), then a 16-lane reduction
+// Every body calls this one function, so a score gets the same operations in the same order -- and the same bits -- whichever
+// computed it (the order of a max is free; that of the word sum is not).
+//   REMC     side rows per image known at compile time (1, or 2 -- VinVL's 50 regions = 48 + 2; a run-time trip count costs
+//            the headline kernel ~10 %, the 48-row one several per cent); 0: `rem` of them, up to 8, a run-time count
+//   OVERHANG the workgroup's last row tile may hang over the operand's end: E is read at the last of the n_img images that exist
+//            instead (such an image's scores are not stored); n_img is not looked at otherwise
 // ------------------------------------------------------------------------------------------------
-template <bool HAS_E, int TP16, int Q, int REMC, int WGM = 4, int WGN = 2, bool HALF = false>
-__device__ __forceinline__ void scores16_epilogue(f32x4 (&acc)[4][12], int mb, int nb, const float* __restrict__ E,
-                                                  int64_t ldE, int rem, float* __restrict__ S, int64_t ldS, int Bi, int Bc) {
-  using Cfg = GemmCfg<WGM, WGN, 2, 6>;
-  constexpr int CT = 12;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int wm = wave / WGN, wn = wave % WGN;
-  const int half = lane >> 5, l4 = lane & 15;
-  static_assert(Q == 1 || Q == 2, "one or two 32-row region tiles per image");
-  // Q == 1: the wave's 64 rows are two images (lanes 0-31 finish image 0, lanes 32-63 image 1);
-  // Q == 2: they are ONE image (R' in 34..64, or 65 with the side row)
-  const int img = (Q == 1) ? (mb * WGM + wm) * 2 + half : mb * WGM + wm;
-  // REMC == 1: exactly one side row per image, known at compile time (the headline class: a run-time trip
-  // count here costs the whole kernel ~10 %); REMC == 0: `rem` side rows, run-time loop
-  if constexpr (REMC == 1) rem = 1;
-  const float* e = HAS_E ? E + (int64_t)img * rem * ldE + (int64_t)nb * Cfg::BN + wn * 192 + l4 : nullptr;
-  constexpr int NC = HALF ? 24 / (2 * TP16 - 1) : 12 / TP16;       // captions of the wave's 192-row strip
-  static_assert(HALF ? (TP16 <= 2) : (12 % TP16 == 0), "a caption must be a whole number of 16-word column tiles of the strip (or 8 / 24 words)");
-  float v[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) v[c] = 0.f;
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct) {
-    const float p0 = max8(acc[0][ct], acc[1][ct]);
-    const float p1 = max8(acc[2][ct], acc[3][ct]);
-    float m;
-    if constexpr (Q == 1) {
-      // rows are spread over the four 16-lane quarters; gather image 0 into lanes 0-31, image 1 into 32-63
-      auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-      m = vmax(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-      m = max_xor16(m);
-    } else {
-      m = vmax(p0, p1);                                           // all 64 rows belong to the image
-      m = max_xor16(m);
-      m = max_xor32(m);
-    }
-    if constexpr (HAS_E && REMC == 1) m = vmax(m, e[ct * 16]);
-    if constexpr (HAS_E && REMC != 1) {
-      // branch-free: max is idempotent, so rows past the last side row re-read it (k clamped to rem - 1)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) m = vmax(m, e[(int64_t)(k < rem ? k : rem - 1) * ldE + ct * 16]);
-    }
-    caption_add<TP16, HALF, NC>(v, ct, l4, m);
-  }
-  const int cap = (nb * WGN + wn) * NC;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const float t = row16_sum(v[c]);
-    if ((lane & (Q == 1 ? 31 : 63)) == 0 && img < Bi && cap + c < Bc) S[(int64_t)img * ldS + cap + c] = t;
-  }
-}
-
-// Epilogue of the TALL wave tile (128 x 96 per wave: four images x 96 / (16 TP16) captions; 2 x 4 waves per workgroup).
-// The same operations in the same order per score as scores16_epilogue -- in-lane max over an image's 2 row tiles x 4
-// registers, permlane32_swap pairing two images into the half-waves, one 16-lane exchange; in-lane adds over a caption's
-// column tiles, then the 16-lane sum -- so the scores are bit-identical.
-template <bool HAS_E, int TP16, int REMC, int Q = 1, bool HALF = false, int CT = 6, int WGM = 2, int WGN = 4>
-__device__ __forceinline__ void scores16_epilogue_tall(f32x4 (&acc)[8][CT], int mb, int nb, const float* __restrict__ E,
-                                                       int64_t ldE, int rem, float* __restrict__ S, int64_t ldS, int Bi, int Bc) {
-  using Cfg = GemmCfg<WGM, WGN, 4, 3, CT>;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int wm = wave / WGN, wn = wave % WGN;
-  const int half = lane >> 5, l4 = lane & 15;
-  if constexpr (REMC == 1) rem = 1;
-  constexpr int NC = HALF ? 2 * CT / (2 * TP16 - 1) : CT / TP16;
+template <class Cfg, int TPI, bool HAS_E, int TP16, int REMC, bool HALF, bool OVERHANG = false>
+__device__ __forceinline__ void scores16_epilogue(f32x4 (&acc)[Cfg::RT16][Cfg::CT16], int mb, int nb, const float* __restrict__ E,
+                                                  int64_t ldE, int rem, float* __restrict__ S, int64_t ldS, int Bi, int Bc, int n_img = 0) {
+  constexpr int CT = Cfg::CT16, NI = Cfg::RT16 / TPI;
+  static_assert(Cfg::RT16 % TPI == 0, "whole images per wave");
+  constexpr int NC = HALF ? 2 * CT / (2 * TP16 - 1) : CT / TP16;     // captions of the wave's column strip
   static_assert(HALF ? (CT % (2 * TP16 - 1) == 0) : (CT % TP16 == 0), "a caption must be a whole number of 16-word column tiles of the strip, or two captions 2 TP16 - 1 tiles");
-  const int cap = (nb * WGN + wn) * NC;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wm = wave / Cfg::WGN, wn = wave % Cfg::WGN;
+  const int half = lane >> 5, l4 = lane & 15;
+  if constexpr (REMC >= 1) rem = REMC;
+  const int cap = (nb * Cfg::WGN + wn) * NC;
 #pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    // Q == 1: the pair's 64 rows are two images (lanes 0-31 finish the first, 32-63 the second); Q == 2: one image
-    const int img = (Q == 1) ? (mb * WGM + wm) * 4 + 2 * p + half : (mb * WGM + wm) * 2 + p;
-    const float* e = HAS_E ? E + (int64_t)img * rem * ldE + (int64_t)nb * Cfg::BN + wn * Cfg::WCOLS + l4 : nullptr;
+  for (int i0 = 0; i0 < NI; i0 += 2) {
+    const bool pair = i0 + 1 < NI;                                   // compile-time once unrolled
+    const int img = (mb * Cfg::WGM + wm) * NI + i0 + (pair ? half : 0);
+    int img_e = img;
+    if constexpr (OVERHANG) img_e = img < n_img ? img : n_img - 1;
+    const float* e = HAS_E ? E + (int64_t)img_e * rem * ldE + (int64_t)nb * Cfg::BN + wn * Cfg::WCOLS + l4 : nullptr;
     float v[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) v[c] = 0.f;
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
-      const float p0 = max8(acc[4 * p][ct], acc[4 * p + 1][ct]);
-      const float p1 = max8(acc[4 * p + 2][ct], acc[4 * p + 3][ct]);
-      float m;
-      if constexpr (Q == 1) {
-        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+      // rows are spread over the four 16-lane quarters
+      float m = image_max<TPI>(acc, i0 * TPI, ct);
+      if (pair) {
+        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(image_max<TPI>(acc, (i0 + 1) * TPI, ct)), false, false);
         m = vmax(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-        m = max_xor16(m);
       } else {
-        m = vmax(p0, p1);
-        m = max_xor16(m);
         m = max_xor32(m);
       }
-      if constexpr (HAS_E && REMC == 1) m = vmax(m, e[ct * 16]);
-      if constexpr (HAS_E && REMC != 1) {
+      m = max_xor16(m);
+      if constexpr (HAS_E) {
+        // REMC == 0 is branch-free: max is idempotent, so rows past the last side row re-read it (k clamped to rem - 1)
 #pragma unroll
-        for (int k = 0; k < 8; ++k) m = vmax(m, e[(int64_t)(k < rem ? k : rem - 1) * ldE + ct * 16]);
+        for (int k = 0; k < (REMC ? REMC : 8); ++k) m = vmax(m, e[(int64_t)(REMC || k < rem ? k : rem - 1) * ldE + ct * 16]);
       }
       caption_add<TP16, HALF, NC>(v, ct, l4, m);
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       const float t = row16_sum(v[c]);
-      if ((lane & (Q == 1 ? 31 : 63)) == 0 && img < Bi && cap + c < Bc) S[(int64_t)img * ldS + cap + c] = t;
+      if ((lane & (pair ? 31 : 63)) == 0 && img < Bi && cap + c < Bc) S[(int64_t)img * ldS + cap + c] = t;
     }
   }
 }
 
+// The epilogue's side-row values were written by the side GEMM on OTHER XCDs: pull this wave's -- RT16 / TPI images x REMC rows x
+// WCOLS columns, in lines of 32 floats -- into this XCD's L2 before the main loop, so that the epilogue's loads do not pay an HBM /
+// fabric round trip 25 us from here.  An 80-column strip is not line aligned: up to four lines, touched at floats 0, 32, 64, 79.
+// The data itself is dropped: one LDS-DMA dword per lane into the piece of stage 1 that this same wave overwrites with its own
+// (later, in-order) refill.  OVERHANG / n_img: as in scores16_epilogue.
+template <class Cfg, int TPI, int REMC, bool OVERHANG = false>
+__device__ __forceinline__ void side_prefetch(const float* __restrict__ E, int64_t ldE, int mb, int nb, char* smem, int n_img = 0) {
+  constexpr int NI = Cfg::RT16 / TPI;
+  constexpr int LPR = Cfg::WCOLS % 32 ? Cfg::WCOLS / 32 + 2 : Cfg::WCOLS / 32;      // lines per row
+  constexpr int LINES = NI * REMC * LPR;
+  static_assert(REMC >= 1 && LINES <= 64, "one line per lane");
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int q = (threadIdx.x & 63) % LINES;
+  int img = (mb * Cfg::WGM + wave / Cfg::WGN) * NI + q / (LPR * REMC);
+  if constexpr (OVERHANG) img = img < n_img ? img : n_img - 1;
+  const int k = (q / LPR) % REMC;
+  const int off = (q % LPR) * 32 < Cfg::WCOLS ? (q % LPR) * 32 : Cfg::WCOLS - 1;
+  const float* src = E + ((int64_t)img * REMC + k) * ldE + (int64_t)nb * Cfg::BN + (wave % Cfg::WGN) * Cfg::WCOLS + off;
+  __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src), LDS_PTR(smem + Cfg::STAGE_BYTES + wave * 1024), 4, 0, 0);
+}
+
+// The TALL wave tile: 128 x 96 per wave = four images (two at Q = 2) x 96 / (16 TP16) captions; 2 x 4 waves per workgroup, 14 LDS
+// fragment reads per 32-deep step against the WIDE tile's 16.
 // HALF / CT: the 24- and 40-word caption classes (CT = 5: an 80-column strip = two captions of 40).  WGM x WGN = 1 x 2: the
 // two-wave 128 x 160 tile the small grids of the 40-word class use (the other classes' small grids run align_scores16_kernel).
 template <bool HAS_E, int TP16, int REMC, int Q = 1, bool HALF = false, int CT = 6, int WGM = 2, int WGN = 4>
@@ -636,21 +592,9 @@ __global__ __launch_bounds__(WGM * WGN * 64) void align_scores16_tall_kernel(con
   for (int rt = 0; rt < 8; ++rt)
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if constexpr (HAS_E && REMC == 1 && Q == 1 && WGM == 2 && WGN == 4) {
-    // pull this tile's side-row values into this XCD's L2 now (see align_scores16_kernel): per wave 4 images x 96 columns
-    // = 12 lines of 32 floats (80 columns: not line aligned, touched at floats 0, 32, 64, 79); dropped into the piece of stage 1
-    // this wave's own refill overwrites later
-    const int wave_u = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane_p = threadIdx.x & 63;
-    constexpr int LPR = CT == 5 ? 4 : 3;
-    const int q = lane_p % (4 * LPR);
-    const int img_p = (mb * 2 + wave_u / 4) * 4 + q / LPR;
-    const int off_p = (q % LPR) * 32 < Cfg::WCOLS ? (q % LPR) * 32 : Cfg::WCOLS - 1;
-    const float* src = E + (int64_t)img_p * ldE + (int64_t)nb * Cfg::BN + (wave_u % 4) * Cfg::WCOLS + off_p;
-    __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src), LDS_PTR(smem + Cfg::STAGE_BYTES + wave_u * 1024), 4, 0, 0);
-  }
+  if constexpr (HAS_E && REMC == 1 && Q == 1 && WGM == 2 && WGN == 4) side_prefetch<Cfg, 2, 1>(E, ldE, mb, nb, smem);
   gemm_mainloop16_tall<Cfg, true>(xm + (int64_t)mb * Cfg::BM * ldk, y + (int64_t)nb * Cfg::BN * ldk, ldk, ktiles, smem, acc);
-  scores16_epilogue_tall<HAS_E, TP16, REMC, Q, HALF, CT, WGM, WGN>(acc, mb, nb, E, ldE, rem, S, ldS, Bi, Bc);
+  scores16_epilogue<Cfg, 2 * Q, HAS_E, TP16, REMC, HALF>(acc, mb, nb, E, ldE, rem, S, ldS, Bi, Bc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -658,11 +602,11 @@ __global__ __launch_bounds__(WGM * WGN * 64) void align_scores16_tall_kernel(con
 // shape of every shipped YAML -- used to pay for two 32-row tiles (64 rows, 22 % of the MFMA rows padding).  Wave tile
 // 96 x 96 = two images x 96 / (16 TP16) captions (6 x 6 accumulator tiles: 144 registers), workgroup 2 x 4 waves = 192 x 384
 // (4 images x 8 captions at 48 padded words), same LDS image and main loop (gemm_mainloop16_tall with six row tiles: 12
-// fragment reads per 36 MFMAs).  Epilogue: in-lane max over an image's 3 row tiles x 4 registers, v_permlane32_swap pairs
-// the wave's two images into the half-waves, one 16-lane exchange; the side rows join from E; in-lane adds over a caption's
-// column tiles, then the 16-lane sum.  WGM x WGN = 1 x 2 (96 x 192, two waves) is the small-grid variant: same operations
-// in the same order per score, so a score is bit-identical whichever variant computed it.
+// fragment reads per 36 MFMAs).  WGM x WGN = 1 x 2 (96 x 192, two waves) is the small-grid variant.
+// HALF: the 24- / 40-word caption classes (caption_add); CT = 5: the wave's 80 columns are two captions of 40 words.
 // ------------------------------------------------------------------------------------------------
+// This body keeps an epilogue of its own: on scores16_epilogue<Cfg, 3, ...> -- the same operations in the same order per score, the same
+// bits -- the shipped shape's 192 x 320 tile measured 0.16 % slower than before in all of five alternations.
 __device__ __forceinline__ float max12(const f32x4& a, const f32x4& b, const f32x4& c) {
   float t = vmax(vmax(a[0], a[1]), a[2]);
   t = vmax(vmax(t, a[3]), b[0]);
@@ -730,22 +674,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void align_scores16_r48_kernel(cons
   for (int rt = 0; rt < 6; ++rt)
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if constexpr (HAS_E && REMC >= 1 && REMC <= 2 && WGM == 2 && WGN == 4) {
-    // pull this tile's side-row values into this XCD's L2 now (they were written by the side GEMM on other XCDs; see
-    // align_scores16_kernel): per wave 2 images x REMC rows x 96 columns = 6 REMC lines of 32 floats (80 columns: not line
-    // aligned, up to four lines -- touched at floats 0, 32, 64, 79); dropped into the piece of stage 1 this wave's own refill
-    // overwrites later
-    const int wave_u = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane_p = threadIdx.x & 63;
-    constexpr int LPR = CT == 5 ? 4 : 3;
-    constexpr int LINES = 2 * LPR * REMC;
-    const int q = lane_p % LINES;
-    const int img_p = (mb * WGM + wave_u / WGN) * 2 + q / (LPR * REMC);
-    const int k_p = (q / LPR) % REMC;
-    const int off_p = (q % LPR) * 32 < Cfg::WCOLS ? (q % LPR) * 32 : Cfg::WCOLS - 1;
-    const float* src = E + ((int64_t)img_p * REMC + k_p) * ldE + (int64_t)nb * Cfg::BN + (wave_u % WGN) * Cfg::WCOLS + off_p;
-    __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src), LDS_PTR(smem + Cfg::STAGE_BYTES + wave_u * 1024), 4, 0, 0);
-  }
+  if constexpr (HAS_E && REMC >= 1 && REMC <= 2 && WGM == 2 && WGN == 4) side_prefetch<Cfg, 3, REMC>(E, ldE, mb, nb, smem);
   gemm_mainloop16_tall<Cfg, true>(xm + (int64_t)mb * Cfg::BM * ldk, y + (int64_t)nb * Cfg::BN * ldk, ldk, ktiles, smem, acc);
   scores16_epilogue_r48<HAS_E, TP16, REMC, WGM, WGN, CT, HALF>(acc, mb, nb, E, ldE, rem, S, ldS, Bi, Bc);
 }
@@ -757,8 +686,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void align_scores16_r48_kernel(cons
 // 2400 LDS cycles under 2880 of matrix pipe).  Only the 80-column strip fits: two stages of 608 rows are 152 KB (96-column strips
 // would need 168).  The packed operands keep the class's 4-image unit (xm_rows is a multiple of 192, so the sharded path's
 // operands still concatenate): the last row tile may hang over the end and re-reads the operand's last 8-row piece for the rows
-// that do not exist (gemm_stage_k a_avail); their scores are not stored.
-// Epilogue: images 0 and 1 of the wave as in the 96-row tile (each finished by one half-wave), image 2 by both halves.
+// that do not exist (gemm_stage_k a_avail); their scores are not stored, and E is read at the last image that exists (OVERHANG).
 // ------------------------------------------------------------------------------------------------
 using CfgR48x3 = GemmCfg<2, 4, 3, 3, 5, 9>;
 template <bool HAS_E, int REMC>
@@ -776,63 +704,11 @@ __global__ __launch_bounds__(512) void align_scores16_r48x3_kernel(const half_t*
   for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int wave_u = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if constexpr (HAS_E && REMC >= 1 && REMC <= 2) {
-    // side-row values of this tile into this XCD's L2 (see align_scores16_r48_kernel): per wave 3 images x REMC rows x 80 columns
-    const int lane_p = threadIdx.x & 63;
-    constexpr int LINES = 12 * REMC;
-    const int q = lane_p % LINES;
-    int img_p = (mb * 2 + wave_u / 4) * 3 + q / (4 * REMC);
-    if (img_p * 48 >= xm_rows) img_p = xm_rows / 48 - 1;       // the overhanging tile
-    const int k_p = (q / 4) % REMC;
-    const int off_p = (q % 4) * 32 < 80 ? (q % 4) * 32 : 79;
-    const float* src = E + ((int64_t)img_p * REMC + k_p) * ldE + (int64_t)nb * Cfg::BN + (wave_u % 4) * 80 + off_p;
-    __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src), LDS_PTR(smem + Cfg::STAGE_BYTES + wave_u * 1024), 4, 0, 0);
-  }
+  const int n_img = xm_rows / 48;                                  // images that exist in the operands (>= Bi)
+  if constexpr (HAS_E && REMC >= 1 && REMC <= 2) side_prefetch<Cfg, 3, REMC, true>(E, ldE, mb, nb, smem, n_img);
   gemm_mainloop16_tall<Cfg, true>(xm + (int64_t)mb * Cfg::BM * ldk, y + (int64_t)nb * Cfg::BN * ldk, ldk, ktiles, smem, acc, KMapLinear(),
                                   xm_rows - mb * Cfg::BM);
-  // ---- epilogue
-  const int lane = threadIdx.x & 63;
-  const int wm = wave_u / 4, wn = wave_u % 4;
-  const int half = lane >> 5, l4 = lane & 15;
-  if constexpr (REMC >= 1) rem = REMC;
-  const int cap = (nb * 4 + wn) * 2;
-  const int img0 = (mb * 2 + wm) * 3;
-  const int imgA = img0 + half, imgC = img0 + 2;
-  const int n_img = xm_rows / 48;                                  // images that exist in the operands (>= Bi)
-  const int64_t ecol = (int64_t)nb * Cfg::BN + wn * 80 + l4;
-  const float* eA = HAS_E ? E + (int64_t)(imgA < n_img ? imgA : n_img - 1) * rem * ldE + ecol : nullptr;
-  const float* eC = HAS_E ? E + (int64_t)(imgC < n_img ? imgC : n_img - 1) * rem * ldE + ecol : nullptr;
-  float vA[2] = {0.f, 0.f}, vC[2] = {0.f, 0.f};
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct) {
-    const float p0 = max12(acc[0][ct], acc[1][ct], acc[2][ct]);
-    const float p1 = max12(acc[3][ct], acc[4][ct], acc[5][ct]);
-    const float p2 = max12(acc[6][ct], acc[7][ct], acc[8][ct]);
-    auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-    float mA = max_xor16(vmax(__uint_as_float(sw[0]), __uint_as_float(sw[1])));
-    float mC = max_xor16(max_xor32(p2));
-    if constexpr (HAS_E && REMC >= 1) {
-#pragma unroll
-      for (int k = 0; k < REMC; ++k) { mA = vmax(mA, eA[(int64_t)k * ldE + ct * 16]); mC = vmax(mC, eC[(int64_t)k * ldE + ct * 16]); }
-    }
-    if constexpr (HAS_E && REMC == 0) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int64_t o = (int64_t)(k < rem ? k : rem - 1) * ldE + ct * 16;
-        mA = vmax(mA, eA[o]); mC = vmax(mC, eC[o]);
-      }
-    }
-    if (ct < 2) { vA[0] += mA; vC[0] += mC; }
-    else if (ct > 2) { vA[1] += mA; vC[1] += mC; }
-    else { vA[0] += l4 < 8 ? mA : 0.f; vA[1] += l4 < 8 ? 0.f : mA; vC[0] += l4 < 8 ? mC : 0.f; vC[1] += l4 < 8 ? 0.f : mC; }
-  }
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const float tA = row16_sum(vA[c]), tC = row16_sum(vC[c]);
-    if ((lane & 31) == 0 && imgA < Bi && cap + c < Bc) S[(int64_t)imgA * ldS + cap + c] = tA;
-    if (lane == 0 && imgC < Bi && cap + c < Bc) S[(int64_t)imgC * ldS + cap + c] = tC;
-  }
+  scores16_epilogue<Cfg, 3, HAS_E, 3, REMC, true, true>(acc, mb, nb, E, ldE, rem, S, ldS, Bi, Bc, n_img);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -865,27 +741,22 @@ __device__ __forceinline__ float xchg16(float v) {          // the value of lane
   return (threadIdx.x & 16) ? a : b;
 }
 
-__device__ __forceinline__ float xchg32(float v) {          // the value of lane ^ 32
-  auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  const float a = __uint_as_float(sw[0]), b = __uint_as_float(sw[1]);
-  return (threadIdx.x & 32) ? a : b;
-}
-
-// Q == 1: an image is 32 rows (+ one side row from E): two images per 64-row pair, finished in the two half-waves.
-// Q == 2: an image is all 64 rows of the pair (R' 34..64, no side rows): one more exchange, one result per wave.
-template <bool HAS_E, int TP16, int Q>
-__device__ __forceinline__ void argmax16_epilogue_tall(f32x4 (&acc)[8][6], int mb, int nb, const float* __restrict__ E, int64_t ldE, int rem,
-                                                       const int32_t* __restrict__ im_len, int x_tail, int Rq,
-                                                       const int32_t* __restrict__ s_len, int y_tail, int Tq,
-                                                       uint8_t* __restrict__ table, int tstride, uint8_t* __restrict__ flags,
-                                                       int Bi, int Bc) {
-  using Cfg = GemmCfg<2, 4, 4, 3>;
-  static_assert(Q == 1 || !HAS_E, "two row tiles per image: classes without side rows only");
-  constexpr int CT = 6, NC = CT / TP16;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int wm = wave / 4, wn = wave % 4;
+// The arg-max epilogue of both kernels below.  A wave's Cfg::RT16 row tiles are RT16 / TPI images of TPI tiles each (TPI = 2: 32
+// main rows, 3: 48, both with up to 8 side rows from E -- regions 16 TPI .. 16 TPI + rem - 1; 4: 64 rows, none), finished in
+// pairs as in scores16_epilogue: lanes 0-31 finish the pair's first image, lanes 32-63 the second.
+template <class Cfg, int TPI, bool HAS_E, int TP16>
+__device__ __forceinline__ void argmax16_epilogue(f32x4 (&acc)[Cfg::RT16][Cfg::CT16], int mb, int nb, const float* __restrict__ E, int64_t ldE, int rem,
+                                                  const int32_t* __restrict__ im_len, int x_tail, int Rq,
+                                                  const int32_t* __restrict__ s_len, int y_tail, int Tq,
+                                                  uint8_t* __restrict__ table, int tstride, uint8_t* __restrict__ flags,
+                                                  int Bi, int Bc) {
+  constexpr int CT = Cfg::CT16, NC = CT / TP16, NI = Cfg::RT16 / TPI, R0 = 16 * TPI;
+  static_assert(Cfg::RT16 % (2 * TPI) == 0, "whole pairs of images per wave");
+  static_assert(!HAS_E || R0 + 8 <= 63, "the side rows' region indices must fit the 6 mantissa bits below the zero-fill candidate 63");
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int wm = wave / Cfg::WGN, wn = wave % Cfg::WGN;
   const int half = lane >> 5, l4 = lane & 15, q4 = lane >> 4;
-  const int cap0 = (nb * 4 + wn) * NC;
+  const int cap0 = (nb * Cfg::WGN + wn) * NC;
   const float NEG = -3.0e38f;
   // words past the caption's length are zero columns: all their candidates tie at 0 -- they neither count nor flag
   int Lc[NC];
@@ -895,70 +766,50 @@ __device__ __forceinline__ void argmax16_epilogue_tall(f32x4 (&acc)[8][6], int m
     if (cap0 + c < Bc) { int l = s_len[cap0 + c] - 1 - y_tail; Lc[c] = l < 0 ? 0 : (l > Tq ? Tq : l); }
   }
 #pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    // as in scores16_epilogue_tall: Q == 1: the pair's 64 rows are two images, lanes 0-31 finish the first, 32-63 the second
-    const int img = (Q == 1) ? (mb * 2 + wm) * 4 + 2 * p + half : (mb * 2 + wm) * 2 + p;
-    int Li = 0;
-    if (img < Bi) { Li = im_len[img] - 1 - x_tail; Li = Li < 0 ? 0 : (Li > Rq ? Rq : Li); }
-    const int Li_a = Q == 1 ? __shfl(Li, lane & 31, 64) : Li, Li_b = Q == 1 ? __shfl(Li, (lane & 31) + 32, 64) : Li;
-    const float* e = HAS_E ? E + (int64_t)img * rem * ldE + (int64_t)nb * Cfg::BN + wn * 96 + l4 : nullptr;
+  for (int i0 = 0; i0 < NI; i0 += 2) {
+    // regions that count of the pair's images A and B (wave-uniform), and of the one this lane finishes
+    const int img_a = (mb * Cfg::WGM + wm) * NI + i0;
+    int Li_a = 0, Li_b = 0;
+    if (img_a < Bi) { Li_a = im_len[img_a] - 1 - x_tail; Li_a = Li_a < 0 ? 0 : (Li_a > Rq ? Rq : Li_a); }
+    if (img_a + 1 < Bi) { Li_b = im_len[img_a + 1] - 1 - x_tail; Li_b = Li_b < 0 ? 0 : (Li_b > Rq ? Rq : Li_b); }
+    const int img = img_a + half, Li = half ? Li_b : Li_a;
+    const float* e = HAS_E ? E + (int64_t)img * rem * ldE + (int64_t)nb * Cfg::BN + wn * Cfg::WCOLS + l4 : nullptr;
+    // region r with accumulator or side value v, of an image with L valid regions, as a candidate
+    auto candidate = [&](float v, int r, int L) {
+      unsigned bits = (__float_as_uint(v) & ~63u) | (unsigned)r;
+      if (r >= L) bits = 63u;                                      // every masked region is the one zero-fill candidate
+      return (r >= Rq) ? NEG : __uint_as_float(bits);              // rows past R' only fill the tile
+    };
     bool pair_flag[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) pair_flag[c] = false;
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
-      // Q == 1: this lane's 8 values of image A (row tiles 4p, 4p+1) and of image B (4p+2, 4p+3): regions 16 t + 4 q4 + reg
-      // Q == 2: 16 values of the one image: regions 16 t + 4 q4 + reg over the four row tiles
+      // this lane's 4 TPI values of image A (row tiles from i0 TPI on) and of image B (the next TPI): regions 16 t + 4 q4 + reg
       float a1 = NEG, a2 = NEG, b1 = NEG, b2 = NEG;
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < TPI; ++t)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
           const int r = 16 * t + 4 * q4 + reg;
-          {
-            float v = acc[4 * p + t][ct][reg];
-            unsigned bits = (__float_as_uint(v) & ~63u) | (unsigned)r;
-            if (r >= Li_a) bits = 63u;                               // every masked region is the one zero-fill candidate
-            v = (r >= Rq) ? NEG : __uint_as_float(bits);               // rows past R' only fill the tile
-            top2_merge(a1, a2, v, NEG);
-          }
-          {
-            const int rb = Q == 1 ? r : r + 32;
-            float v = acc[4 * p + 2 + t][ct][reg];
-            unsigned bits = (__float_as_uint(v) & ~63u) | (unsigned)rb;
-            if (rb >= Li_b) bits = 63u;
-            v = (rb >= Rq) ? NEG : __uint_as_float(bits);
-            top2_merge(b1, b2, v, NEG);
-          }
+          top2_merge(a1, a2, candidate(acc[i0 * TPI + t][ct][reg], r, Li_a), NEG);
+          top2_merge(b1, b2, candidate(acc[(i0 + 1) * TPI + t][ct][reg], r, Li_b), NEG);
         }
-      float t1, t2;
-      if constexpr (Q == 1) {
-        // lanes 0-31 take image A's partials of lane + 32, lanes 32-63 image B's of lane - 32
-        auto s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a1), __float_as_uint(b1), false, false);
-        auto s2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a2), __float_as_uint(b2), false, false);
-        t1 = __uint_as_float(s1[0]); t2 = __uint_as_float(s2[0]);
-        top2_merge(t1, t2, __uint_as_float(s1[1]), __uint_as_float(s2[1]));
-        { const float o1 = xchg16(t1), o2 = xchg16(t2); top2_merge(t1, t2, o1, o2); }
-      } else {
-        t1 = a1; t2 = a2;
-        top2_merge(t1, t2, b1, b2);
-        { const float o1 = xchg16(t1), o2 = xchg16(t2); top2_merge(t1, t2, o1, o2); }
-        { const float o1 = xchg32(t1), o2 = xchg32(t2); top2_merge(t1, t2, o1, o2); }
-      }
+      // lanes 0-31 take image A's partials of lane + 32, lanes 32-63 image B's of lane - 32
+      auto s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a1), __float_as_uint(b1), false, false);
+      auto s2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a2), __float_as_uint(b2), false, false);
+      float t1 = __uint_as_float(s1[0]), t2 = __uint_as_float(s2[0]);
+      top2_merge(t1, t2, __uint_as_float(s1[1]), __uint_as_float(s2[1]));
+      { const float o1 = xchg16(t1), o2 = xchg16(t2); top2_merge(t1, t2, o1, o2); }
       if constexpr (HAS_E) {
-        if (rem == 1) {                                                 // the headline class: one side row (region 32)
-          const float ev = e[ct * 16];
-          const float ep = (Rq > 32) ? __uint_as_float((32 >= Li ? 63u : ((__float_as_uint(ev) & ~63u) | 32u))) : NEG;
-          top2_merge(t1, t2, ep, NEG);
+        if (rem == 1) {                                                 // the headline class: one side row
+          top2_merge(t1, t2, candidate(e[ct * 16], R0, Li), NEG);
         } else {
-          // up to 8 side rows (regions 32 .. 32 + rem - 1); rows past the last repeat it -- the same candidate, merged as one
+          // up to 8 side rows; rows past the last repeat it -- the same candidate, merged as one
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
             const int kk = k < rem ? k : rem - 1;
-            const unsigned idx = 32u + (unsigned)kk;
-            const float ev = e[(int64_t)kk * ldE + ct * 16];
-            const float ep = ((int)idx < Rq) ? __uint_as_float(((int)idx >= Li ? 63u : ((__float_as_uint(ev) & ~63u) | idx))) : NEG;
-            top2_merge(t1, t2, ep, NEG);
+            top2_merge(t1, t2, candidate(e[(int64_t)kk * ldE + ct * 16], R0 + kk, Li), NEG);
           }
         }
       }
@@ -967,18 +818,19 @@ __device__ __forceinline__ void argmax16_epilogue_tall(f32x4 (&acc)[8][6], int m
       // NO_GRAD: the zero fill won, or the word is padding (its raw row is not zero: bwd_rows_kernel must skip it)
       const uint8_t res = (idx >= (unsigned)Li || w >= Lc[c]) ? (uint8_t)255 : (uint8_t)idx;
       const bool close = (t1 - t2) < ARGMAX_TAU_ACC;                   // t2 == NEG when there is one candidate only
-      if ((lane & (Q == 1 ? 16 : 48)) == 0 && img < Bi && cap0 + c < Bc && w < tstride) table[((int64_t)img * Bc + cap0 + c) * tstride + w] = res;
+      if ((lane & 16) == 0 && img < Bi && cap0 + c < Bc && w < tstride) table[((int64_t)img * Bc + cap0 + c) * tstride + w] = res;
       pair_flag[c] = pair_flag[c] || (close && w < Lc[c]);
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-      const unsigned long long mask = Q == 1 ? (half ? 0xffffffff00000000ull : 0x00000000ffffffffull) : ~0ull;
+      const unsigned long long mask = half ? 0xffffffff00000000ull : 0x00000000ffffffffull;
       const bool any = (__ballot(pair_flag[c] && img < Bi && cap0 + c < Bc) & mask) != 0;
-      if ((lane & (Q == 1 ? 31 : 63)) == 0 && any) flags[(int64_t)img * Bc + cap0 + c] = 1;
+      if ((lane & 31) == 0 && any) flags[(int64_t)img * Bc + cap0 + c] = 1;
     }
   }
 }
 
+// 32 main rows per image (Q = 1: R' <= 40 with the side rows) or 64 (Q = 2: R' 57..64, none)
 template <bool HAS_E, int TP16, int Q>
 __global__ __launch_bounds__(512) void align_argmax16_tall_kernel(const half_t* __restrict__ xm, const half_t* __restrict__ y,
                                                                   const float* __restrict__ E, int64_t ldE, int rem,
@@ -996,93 +848,10 @@ __global__ __launch_bounds__(512) void align_argmax16_tall_kernel(const half_t* 
 #pragma unroll
     for (int ct = 0; ct < 6; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
   gemm_mainloop16_tall<Cfg, true>(xm + (int64_t)mb * Cfg::BM * ldk, y + (int64_t)nb * Cfg::BN * ldk, ldk, ktiles, smem, acc);
-  argmax16_epilogue_tall<HAS_E, TP16, Q>(acc, mb, nb, E, ldE, rem, im_len, x_tail, Rq, s_len, y_tail, Tq, table, tstride, flags, Bi, Bc);
+  argmax16_epilogue<Cfg, 2 * Q, HAS_E, TP16>(acc, mb, nb, E, ldE, rem, im_len, x_tail, Rq, s_len, y_tail, Tq, table, tstride, flags, Bi, Bc);
 }
 
-// The 48-row region class (see align_scores16_r48_kernel): a wave's 96 rows are two images of three row tiles each; side rows
-// (regions 48 .. 48 + rem - 1) join from E.  Same packing of the region index into the 6 low mantissa bits (regions < 56).
-template <bool HAS_E, int TP16>
-__device__ __forceinline__ void argmax16_epilogue_r48(f32x4 (&acc)[6][6], int mb, int nb, const float* __restrict__ E, int64_t ldE, int rem,
-                                                      const int32_t* __restrict__ im_len, int x_tail, int Rq,
-                                                      const int32_t* __restrict__ s_len, int y_tail, int Tq,
-                                                      uint8_t* __restrict__ table, int tstride, uint8_t* __restrict__ flags,
-                                                      int Bi, int Bc) {
-  using Cfg = GemmCfg<2, 4, 3, 3>;
-  constexpr int CT = 6, NC = CT / TP16;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int wm = wave / 4, wn = wave % 4;
-  const int half = lane >> 5, l4 = lane & 15, q4 = lane >> 4;
-  const int cap0 = (nb * 4 + wn) * NC;
-  const float NEG = -3.0e38f;
-  int Lc[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    Lc[c] = 0;
-    if (cap0 + c < Bc) { int l = s_len[cap0 + c] - 1 - y_tail; Lc[c] = l < 0 ? 0 : (l > Tq ? Tq : l); }
-  }
-  const int img = (mb * 2 + wm) * 2 + half;
-  int Li = 0;
-  if (img < Bi) { Li = im_len[img] - 1 - x_tail; Li = Li < 0 ? 0 : (Li > Rq ? Rq : Li); }
-  const int Li_a = __shfl(Li, lane & 31, 64), Li_b = __shfl(Li, (lane & 31) + 32, 64);
-  const float* e = HAS_E ? E + (int64_t)img * rem * ldE + (int64_t)nb * Cfg::BN + wn * 96 + l4 : nullptr;
-  bool pair_flag[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) pair_flag[c] = false;
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct) {
-    float a1 = NEG, a2 = NEG, b1 = NEG, b2 = NEG;
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int r = 16 * t + 4 * q4 + reg;
-        {
-          float v = acc[t][ct][reg];
-          unsigned bits = (__float_as_uint(v) & ~63u) | (unsigned)r;
-          if (r >= Li_a) bits = 63u;                               // every masked region is the one zero-fill candidate
-          v = (r >= Rq) ? NEG : __uint_as_float(bits);               // rows past R' only fill the tile
-          top2_merge(a1, a2, v, NEG);
-        }
-        {
-          float v = acc[3 + t][ct][reg];
-          unsigned bits = (__float_as_uint(v) & ~63u) | (unsigned)r;
-          if (r >= Li_b) bits = 63u;
-          v = (r >= Rq) ? NEG : __uint_as_float(bits);
-          top2_merge(b1, b2, v, NEG);
-        }
-      }
-    // lanes 0-31 take the first image's partials of lane + 32, lanes 32-63 the second image's of lane - 32
-    auto s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a1), __float_as_uint(b1), false, false);
-    auto s2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a2), __float_as_uint(b2), false, false);
-    float t1 = __uint_as_float(s1[0]), t2 = __uint_as_float(s2[0]);
-    top2_merge(t1, t2, __uint_as_float(s1[1]), __uint_as_float(s2[1]));
-    { const float o1 = xchg16(t1), o2 = xchg16(t2); top2_merge(t1, t2, o1, o2); }
-    if constexpr (HAS_E) {
-      // up to 8 side rows (regions 48 .. 48 + rem - 1); rows past the last repeat it -- the same candidate, merged as one
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int kk = k < rem ? k : rem - 1;
-        const unsigned idx = 48u + (unsigned)kk;
-        const float ev = e[(int64_t)kk * ldE + ct * 16];
-        const float ep = ((int)idx < Rq) ? __uint_as_float(((int)idx >= Li ? 63u : ((__float_as_uint(ev) & ~63u) | idx))) : NEG;
-        top2_merge(t1, t2, ep, NEG);
-      }
-    }
-    const unsigned idx = __float_as_uint(t1) & 63u;
-    const int c = ct / TP16, w = (ct % TP16) * 16 + l4;
-    const uint8_t res = (idx >= (unsigned)Li || w >= Lc[c]) ? (uint8_t)255 : (uint8_t)idx;
-    const bool close = (t1 - t2) < ARGMAX_TAU_ACC;
-    if ((lane & 16) == 0 && img < Bi && cap0 + c < Bc && w < tstride) table[((int64_t)img * Bc + cap0 + c) * tstride + w] = res;
-    pair_flag[c] = pair_flag[c] || (close && w < Lc[c]);
-  }
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const unsigned long long mask = half ? 0xffffffff00000000ull : 0x00000000ffffffffull;
-    const bool any = (__ballot(pair_flag[c] && img < Bi && cap0 + c < Bc) & mask) != 0;
-    if ((lane & 31) == 0 && any) flags[(int64_t)img * Bc + cap0 + c] = 1;
-  }
-}
-
+// The 48-row region class (see align_scores16_r48_kernel): a wave's 96 rows are two images of three row tiles each
 template <bool HAS_E, int TP16>
 __global__ __launch_bounds__(512) void align_argmax16_r48_kernel(const half_t* __restrict__ xm, const half_t* __restrict__ y,
                                                                  const float* __restrict__ E, int64_t ldE, int rem,
@@ -1100,7 +869,7 @@ __global__ __launch_bounds__(512) void align_argmax16_r48_kernel(const half_t* _
 #pragma unroll
     for (int ct = 0; ct < 6; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
   gemm_mainloop16_tall<Cfg, true>(xm + (int64_t)mb * Cfg::BM * ldk, y + (int64_t)nb * Cfg::BN * ldk, ldk, ktiles, smem, acc);
-  argmax16_epilogue_r48<HAS_E, TP16>(acc, mb, nb, E, ldE, rem, im_len, x_tail, Rq, s_len, y_tail, Tq, table, tstride, flags, Bi, Bc);
+  argmax16_epilogue<Cfg, 3, HAS_E, TP16>(acc, mb, nb, E, ldE, rem, im_len, x_tail, Rq, s_len, y_tail, Tq, table, tstride, flags, Bi, Bc);
 }
 
 // WGM x WGN waves of 64 x 192 each: 4 x 2 with a double buffer is the kernel above; 2 x 1 (128 x 192, two waves) with a
@@ -1125,23 +894,13 @@ __global__ __launch_bounds__(WGM * WGN * 64) void align_scores16_kernel(const ha
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  if constexpr (HAS_E && REMC == 1 && Q == 1 && WGM == 4 && WGN == 2 && NS == 2) {
-    // The epilogue's side-row values E[img][cols] were written by the side GEMM on OTHER XCDs: pull this tile's 12
-    // lines per wave (2 images x 192 columns) into this XCD's L2 now, so that the epilogue's loads do not pay an HBM /
-    // fabric round trip 25 us from here.  The data itself is dropped: one LDS-DMA dword per lane into the piece of
-    // stage 1 that this same wave overwrites with its own (later, in-order) refill.
-    const int wave_u = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane_p = threadIdx.x & 63;
-    const int img_p = (mb * 4 + wave_u / 2) * 2 + ((lane_p % 12) / 6);
-    const float* src = E + (int64_t)img_p * ldE + (int64_t)nb * Cfg::BN + (wave_u % 2) * 192 + (lane_p % 6) * 32;
-    __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src), LDS_PTR(smem + Cfg::STAGE_BYTES + wave_u * 1024), 4, 0, 0);
-  }
+  if constexpr (HAS_E && REMC == 1 && Q == 1 && WGM == 4 && WGN == 2 && NS == 2) side_prefetch<Cfg, 2, 1>(E, ldE, mb, nb, smem);
   unsigned long long pt0 = 0, pr0 = 0, pt1 = 0, pr1 = 0;
   if constexpr (PROBE) { pt0 = __builtin_amdgcn_s_memtime(); pr0 = __builtin_amdgcn_s_memrealtime(); }
   gemm_mainloop16<Cfg, true, NS>(xm + (int64_t)mb * Cfg::BM * ldk, y + (int64_t)nb * Cfg::BN * ldk, ldk, ktiles, smem, acc);
   if constexpr (PROBE) { pt1 = __builtin_amdgcn_s_memtime(); pr1 = __builtin_amdgcn_s_memrealtime(); }
 
-  scores16_epilogue<HAS_E, TP16, Q, REMC, WGM, WGN, HALF>(acc, mb, nb, E, ldE, rem, S, ldS, Bi, Bc);
+  scores16_epilogue<Cfg, 2 * Q, HAS_E, TP16, REMC, HALF>(acc, mb, nb, E, ldE, rem, S, ldS, Bi, Bc);
 #ifdef ALADIN_DIAG
   if constexpr (PROBE) {
     __syncthreads();

@@ -1434,6 +1434,30 @@ def test_large_grid_half_caption_classes_are_bit_identical(Bi, Bc, R, Tn):
             assert torch.equal(S[ii, jj][keep_i, keep_j], part[keep_i, keep_j]), (i0, j0)
 
 
+@pytest.mark.parametrize('Bi,Bc,R,Tn,D', [(36, 64, 60, 50, 64), (40, 72, 66, 50, 64)])
+def test_large_grid_two_region_tile_classes_are_bit_identical(Bi, Bc, R, Tn, D):
+    """Two 32-row region tiles per image (R' 59, and 65 = 64 + the side row) with whole 16-word caption tiles on grids of more than
+    64 workgroup tiles: the eight-wave 128 x 96 wave tile, where a wave's 128 rows are one pair of images, against the matrix's own
+    32 x 32 blocks (small grids: the two-wave 128 x 192 tile, one image per wave) bit for bit, and against the oracle."""
+    from aladin_amd import ops, synth
+    im, s, il, sl = synth.alignment_batch(Bi, R, Tn, D, seed=7200 + R, ragged=True, Bc=Bc)
+    il[0], sl[0] = R, Tn
+    g = ops.align_geometry(Bi, Bc, R, Tn, D)
+    assert g.mrows == 64 and g.trows == 16 * g.tp16 and (g.xm_rows // 256) * (g.y_rows // 384) > 64
+    a, b = T(im), T(s)
+    S = ops.alignment_scores(a, b, il, sl)
+    assert_scores_close(S.cpu().numpy(), O.alignment_scores(im, s, il, sl))
+    for i0 in range(0, Bi, 32):
+        for j0 in range(0, Bc, 32):
+            ii, jj = slice(i0, min(Bi, i0 + 32)), slice(j0, min(Bc, j0 + 32))
+            il_b, sl_b = list(il[ii]), list(sl[jj])
+            il_b[0], sl_b[0] = R, Tn                                     # every block keeps the geometry of the whole
+            part = ops.alignment_scores(a[ii].clone(), b[jj].clone(), il_b, sl_b)
+            keep_i = slice(1 if il_b[0] != il[i0] else 0, None)          # the sample whose length was raised scores differently
+            keep_j = slice(1 if sl_b[0] != sl[j0] else 0, None)
+            assert torch.equal(S[ii, jj][keep_i, keep_j], part[keep_i, keep_j]), (i0, j0)
+
+
 @pytest.mark.parametrize('Bi,Bc,R,Tn', [(254, 270, 51, 38), (250, 258, 49, 43), (256, 256, 50, 36), (262, 272, 54, 40), (254, 270, 50, 38)])
 def test_large_grid_40_word_tile_is_bit_identical(Bi, Bc, R, Tn):
     """Large grids of the 48-row region class x 40-word caption class run the 288 x 320 workgroup tile (three images per wave; the
@@ -1449,7 +1473,7 @@ def test_large_grid_40_word_tile_is_bit_identical(Bi, Bc, R, Tn):
     g = ops.align_geometry(Bi, Bc, R, Tn, 256)
     assert g.mrows == 48 and g.trows == 40 and (g.xm_rows // 192) * (g.y_rows // 320) >= 512
     r192, r288 = -(-(g.xm_rows // 192) * (g.y_rows // 320) // 256), -(-(-(-g.xm_rows // 288)) * (g.y_rows // 320) // 256)
-    assert (1.37 * r288 < 0.97 * r192) == ((Bi, Bc) != (256, 256))          # which kernel the library picks (align_fwd.hip launch_scores16_r48)
+    assert (1.37 * r288 < 0.97 * r192) == ((Bi, Bc) != (256, 256))          # which kernel the library picks (align_fwd.hip select_scores)
     a, b = T(im), T(s)
     S = ops.alignment_scores(a, b, il, sl)
     assert_scores_close(S.cpu().numpy(), O.alignment_scores(im, s, il, sl))

@@ -6,7 +6,10 @@ builds (an old library built from another checkout against the new one):
     python tools/check_variant.py save new.pt
     python tools/check_variant.py cmp old.pt new.pt
 
-Scores: the bench batch (B = 256, full lengths) and a ragged batch.  Gradients (exact backward precision unless the name says
+Scores: the bench batch (B = 256, full lengths) and a ragged batch; one small ragged problem per body and epilogue variant of the
+score kernels (SCORE_CASES: the geometry and the grid rule that select the body are asserted), in fp16 and split precision.
+Arg-max table: the sum-of-violations step with the dense table forced, one problem per variant of the arg-max kernels
+(ARGMAX_CASES).  Gradients (exact backward precision unless the name says
 otherwise), one case per stage of the alignment backward: the fused triplet step in the three precision modes; the
 sum-of-violations step with the GEMM and with the gather row step; a sparse gradient on the score matrix (fp16 pair kernel at
 R = 65, fp32 fallback at R = 71); a long problem; the small-batch loss heads.
@@ -17,6 +20,92 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
+
+
+# (Bi, Bc, R, T, D) -> (mrows, rem, tp16, trows), body, small-grid variant: what csrc/align_fwd.hip's select_scores picks
+SCORE_CASES = (
+    ((6, 5, 34, 50, 64), (32, 1, 3, 48), 'WIDE', True),           # Q = 1, one side row
+    ((5, 9, 60, 50, 64), (64, 0, 3, 48), 'WIDE', True),           # Q = 2
+    ((4, 5, 66, 40, 64), (64, 1, 3, 40), 'TALL', True),           # Q = 2 + side row
+    ((5, 9, 34, 67, 64), (32, 1, 4, 64), 'WIDE', True),           # tp16 = 4
+    ((9, 21, 36, 27, 64), (32, 3, 2, 24), 'WIDE', True),          # half class, 3 side rows
+    ((6, 50, 34, 11, 64), (32, 1, 1, 8), 'WIDE', True),           # 8-word class
+    ((6, 18, 34, 43, 64), (32, 1, 3, 40), 'TALL', True),          # two-wave 128 x 160
+    ((6, 6, 51, 38, 768), (48, 2, 3, 40), 'R48', True),           # 2 side rows, 40 words
+    ((5, 4, 57, 90, 64), (48, 8, 6, 96), 'R48', True),            # 8 side rows
+    ((9, 5, 49, 9, 64), (48, 0, 1, 8), 'R48', True),              # no side rows
+    ((3, 4, 71, 71, 64), (96, 0, 6, 96), '32X32', None),
+    # more than 64 workgroup tiles
+    ((72, 96, 34, 50, 64), (32, 1, 3, 48), 'TALL', False),        # Q = 1
+    ((36, 64, 60, 50, 64), (64, 0, 3, 48), 'TALL', False),        # Q = 2, whole tiles
+    ((40, 72, 66, 50, 64), (64, 1, 3, 48), 'TALL', False),        # Q = 2 + side row
+    ((72, 96, 34, 67, 64), (32, 1, 4, 64), 'WIDE', False),        # 4 x 2 waves
+    ((72, 96, 51, 50, 64), (48, 2, 3, 48), 'R48', False),         # 2 x 4 waves
+    ((254, 270, 51, 38, 256), (48, 2, 3, 40), 'R48X3', False),    # with the overhanging tile
+    ((256, 256, 50, 36, 256), (48, 1, 3, 40), 'R48', False),      # 192 x 320
+)
+# (R, T) at B = 64, D = 256 -> (mrows, rem) of the arg-max kernel's class
+ARGMAX_CASES = (((34, 50), (32, 1)), ((38, 30), (32, 5)), ((51, 38), (48, 2)), ((50, 38), (48, 1)), ((49, 38), (48, 0)), ((58, 38), (64, 0)))
+
+
+def score_body(g):
+    """(body, small-grid variant) of a geometry: select_scores of csrc/align_fwd.hip."""
+    words40 = g.trows == 40
+    M, N = g.xm_rows, g.y_rows
+    if g.mrows == 96:
+        return '32X32', None
+    if g.mrows == 48:
+        small = (M // 192) * (N // (320 if words40 else 384)) <= 64
+        if words40 and not small:
+            n_n = N // 320
+            r192, r288 = -(-(M // 192) * n_n // 256), -(-(-(-M // 288)) * n_n // 256)
+            if 1.37 * r288 < 0.97 * r192:
+                return 'R48X3', False
+        return 'R48', small
+    if words40:
+        return 'TALL', (M // 256) * (N // 320) <= 64
+    small = (M // 256) * (N // 384) <= 64
+    return ('WIDE' if small or 6 % g.tp16 else 'TALL'), small
+
+
+def score_cases(ops, synth, dev):
+    """-> {name: scores} of SCORE_CASES, ragged, in both precisions."""
+    out = {}
+    for (Bi, Bc, R, Tn, D), cls, body, small in SCORE_CASES:
+        im, s, il, sl = synth.alignment_batch(Bi, R, Tn, D, seed=8000 + 100 * R + Tn, ragged=True, Bc=Bc)
+        il[0], sl[0] = R, Tn
+        a, b = torch.from_numpy(im).to(dev), torch.from_numpy(s).to(dev)
+        for prec in ('fp16', 'split'):
+            g = ops.align_geometry(Bi, Bc, R, Tn, D, precision=prec)
+            assert (g.mrows, g.rem, g.tp16, g.trows) == cls and score_body(g) == (body, small), ((Bi, Bc, R, Tn, D), prec, score_body(g))
+            with torch.no_grad():
+                out['scores-%dx%d-R%d-T%d-D%d-%s' % (Bi, Bc, R, Tn, D, prec)] = ops.alignment_scores(a, b, il, sl, precision=prec).cpu()
+    return out
+
+
+def argmax_cases(ops, synth, dev):
+    """-> {name: tensor}: loss and gradients of the sum-of-violations step through the dense arg-max table."""
+    from aladin_amd.loss import AlignmentContrastiveLoss
+    out = {}
+    crit = AlignmentContrastiveLoss(margin=0.2, measure='dot', max_violation=False, aggregation='MrSw')
+    saved = ops.DENSE_BACKWARD, ops.DENSE_ROWS_GEMM, ops.DENSE_MIN_FRACTION, ops.DENSE_GEMM_FORCE, ops.DENSE_MIN_PAIRS
+    try:
+        # B = 64 is below the batch size from which the dense table pays: forced all the same
+        ops.DENSE_BACKWARD, ops.DENSE_ROWS_GEMM, ops.DENSE_MIN_FRACTION, ops.DENSE_GEMM_FORCE, ops.DENSE_MIN_PAIRS = True, True, 0.0, True, 0
+        for (R, Tn), cls in ARGMAX_CASES:
+            g = ops.align_geometry(64, 64, R, Tn, 256, precision='split')
+            assert (g.mrows, g.rem) == cls and 6 % g.tp16 == 0, ((R, Tn), g.mrows, g.rem, g.tp16)
+            im, s, il, sl = synth.alignment_batch(64, R, Tn, 256, seed=8500 + R, ragged=True)
+            a = torch.from_numpy(im).to(dev).requires_grad_(True)
+            b = torch.from_numpy(s).to(dev).requires_grad_(True)
+            loss = crit(a, b, il, sl)
+            loss.backward()
+            assert ops._LAST_BWD_FLAGS[0] & 2, 'the dense path was not taken'
+            tag = 'argmax64-R%d-T%d' % (R, Tn)
+            out[tag + '/loss'], out[tag + '/d_im'], out[tag + '/d_s'] = loss.detach().cpu(), a.grad.cpu(), b.grad.cpu()
+    finally:
+        ops.DENSE_BACKWARD, ops.DENSE_ROWS_GEMM, ops.DENSE_MIN_FRACTION, ops.DENSE_GEMM_FORCE, ops.DENSE_MIN_PAIRS = saved
+    return out
 
 
 def gradient_cases(ops, synth, dev):
@@ -102,7 +191,7 @@ def main():
                 continue
             same = torch.equal(a[k], b[k])
             ok &= same
-            print('%-26s %s  max |diff| %.3g' % (k, 'bit-identical' if same else 'DIFFERENT', float((a[k] - b[k]).abs().max())))
+            print('%-34s %s  max |diff| %.3g' % (k, 'bit-identical' if same else 'DIFFERENT', float((a[k] - b[k]).abs().max())))
         sys.exit(0 if ok else 1)
     from aladin_amd import ops, synth
     dev = torch.device('cuda:0')
@@ -111,6 +200,8 @@ def main():
         im, s, il, sl = synth.alignment_batch(256, 34, 50, 768, seed=seed, ragged=ragged)
         with torch.no_grad():
             out[tag] = ops.alignment_scores(torch.from_numpy(im).to(dev), torch.from_numpy(s).to(dev), il, sl, precision='fp16').cpu()
+    out.update(score_cases(ops, synth, dev))
+    out.update(argmax_cases(ops, synth, dev))
     out.update(gradient_cases(ops, synth, dev))
     torch.save(out, sys.argv[2])
     print('saved', sys.argv[2], {k: float(v.double().sum()) for k, v in out.items()})
