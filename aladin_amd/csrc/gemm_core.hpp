@@ -77,7 +77,7 @@ __device__ __forceinline__ void gemm_stage(const half_t* __restrict__ a_rows, co
 }
 
 // The same staging with the K position given per panel (a_k / b_k, in halfs, wave-uniform): the evaluation similarity GEMM walks
-// operand rows laid out [hi | lo] in the chain order hi.hi, lo.hi, hi.lo (recall.hip), so the two panels sit at different K offsets.
+// operand rows laid out [hi | lo] in the chain order hi.hi, lo.hi, hi.lo (sim_common.hpp), so the two panels sit at different K offsets.
 // a_avail > 0: only that many rows exist behind a_rows (a multiple of 8); pieces past them re-read the last piece -- the last row
 // tile of a grid whose row count is not a multiple of BM (their accumulator rows are never looked at).
 template <class Cfg, int C0 = 0, int C1 = Cfg::CHUNKS_PER_WAVE>

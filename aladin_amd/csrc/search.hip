@@ -11,7 +11,7 @@
 //   1. search_gemm_kernel<DIM, false>: the full chain hi.hi, lo.hi, hi.lo (the main loop of sim_gemm_store_kernel), epilogue
 //      gmax[query][group] = the group's maximum.  Gallery positions past the gallery (the partial last group, tile padding)
 //      and NaN count as -inf -- never as the 0 a zero-padded operand row produces, or an all-negative query would select padding;
-//   2. topk_kernel on gmax (recall.hip): the min(k, n_groups) best groups of every query, by exactly that key;
+//   2. topk_kernel on gmax (sim_topk_launch): the min(k, n_groups) best groups of every query, by exactly that key;
 //      search_slots_kernel: the selected groups sorted by INDEX are the query's slots; table[query][group] = slot, 0xFFFF = none;
 //   3. search_gemm_kernel<DIM, true>: the same GEMM again, epilogue cand[query][slot][16] = the scores of the selected
 //      (query, group) pairs, each written once by one lane;
@@ -33,7 +33,7 @@ struct SearchGeom {
   int G_ld;              // groups per row of gmax / table: the padded gallery axis / 16 (a multiple of 24 or 16)
 };
 struct SearchWs {
-  SimWs sim;
+  SimPacked sim;         // the packed operands and their padded sizes
   float* gmax;           // n_q x G_ld           (passes 1, 2)
   float* cand;           // n_q x kk x 16        (passes 3, 4: the same bytes as gmax, which is dead by then)
   uint16_t* table;       // n_q x G_ld
@@ -41,31 +41,25 @@ struct SearchWs {
   int32_t* sorted;       // n_q x kk: the same groups, ascending = slot -> group
 };
 
-static size_t search_layout(int n_img, int n_cap, int D, int k, int dim, char* base, SearchWs* ws, SearchGeom* geo, int* Mp_, int* Np_, int* Dp_) {
-  int Mp, Np, Dp;
-  size_t off = sim_ws_layout(n_img, n_cap, D, base, ws ? &ws->sim : nullptr, &Mp, &Np, &Dp);
-  if (Mp_) *Mp_ = Mp;
-  if (Np_) *Np_ = Np;
-  if (Dp_) *Dp_ = Dp;
+static size_t search_layout(int n_img, int n_cap, int D, int k, int dim, char* base, SearchWs* ws, SearchGeom* geo) {
+  SimPacked p;
+  WsCursor c{base, (sim_ws_layout(n_img, n_cap, D, base, &p) + 255) / 256 * 256};
   SearchGeom g;
   g.n_q = dim == 1 ? n_img : n_cap;
   g.n_g = dim == 1 ? n_cap : n_img;
   g.n_groups = cdiv(g.n_g, SEARCH_GROUP);
   g.kk = k < g.n_groups ? k : g.n_groups;
-  g.G_ld = (dim == 1 ? Np : Mp) / SEARCH_GROUP;
+  g.G_ld = (dim == 1 ? p.Np : p.Mp) / SEARCH_GROUP;
   if (geo) *geo = g;
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  off = up(off);
-  const size_t gmax_bytes = (size_t)g.n_q * g.G_ld * 4, cand_bytes = (size_t)g.n_q * g.kk * SEARCH_GROUP * 4;
-  if (ws) { ws->gmax = (float*)(base + off); ws->cand = (float*)(base + off); }
-  off += up(gmax_bytes > cand_bytes ? gmax_bytes : cand_bytes);
-  if (ws) ws->table = (uint16_t*)(base + off);
-  off += up((size_t)g.n_q * g.G_ld * 2);
-  if (ws) ws->sel = (int32_t*)(base + off);
-  off += up((size_t)g.n_q * g.kk * 4);
-  if (ws) ws->sorted = (int32_t*)(base + off);
-  off += up((size_t)g.n_q * g.kk * 4);
-  return off;
+  SearchWs w;
+  w.sim = p;
+  const size_t gmax_n = (size_t)g.n_q * g.G_ld, cand_n = (size_t)g.n_q * g.kk * SEARCH_GROUP;
+  w.gmax = w.cand = c.take<float>(gmax_n > cand_n ? gmax_n : cand_n, 256);
+  w.table = c.take<uint16_t>((size_t)g.n_q * g.G_ld, 256);
+  w.sel = c.take<int32_t>((size_t)g.n_q * g.kk, 256);
+  w.sorted = c.take<int32_t>((size_t)g.n_q * g.kk, 256);
+  if (ws) *ws = w;
+  return c.off;
 }
 
 static bool search_shape_ok(int n_img, int n_cap, int D, int k, int dim) {
@@ -75,7 +69,7 @@ static bool search_gallery_ok(int n_img, int n_cap, int dim) { return cdiv(dim =
 
 extern "C" size_t aladin_search_workspace_bytes(int n_img, int n_cap, int D, int k, int dim) {
   if (!search_shape_ok(n_img, n_cap, D, k, dim) || !search_gallery_ok(n_img, n_cap, dim)) return 0;
-  return search_layout(n_img, n_cap, D, k, dim, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return search_layout(n_img, n_cap, D, k, dim, nullptr, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -229,8 +223,8 @@ __global__ __launch_bounds__(256) void search_slots_kernel(const int32_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-// Pass 4, one workgroup per query: topk_kernel's rounds (recall.hip) over cand[q][kk * 16].  Candidate c is gallery item
-// sorted[q][c >> 4] * 16 + (c & 15), ascending in c; positions past the gallery are retired before the first round.
+// Pass 4, one workgroup per query: the selection rounds of aladin_topk (topk_rounds, sim_common.hpp) over cand[q][kk * 16].  Candidate c
+// is gallery item sorted[q][c >> 4] * 16 + (c & 15), ascending in c; positions past the gallery are retired before the first round.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void search_final_kernel(const float* __restrict__ cand, const int32_t* __restrict__ sorted, int n_g, int kk,
                                                            int k, int32_t* __restrict__ out_idx, float* __restrict__ out_val) {
@@ -239,57 +233,32 @@ __global__ __launch_bounds__(256) void search_final_kernel(const float* __restri
   __shared__ float redv[4];
   __shared__ int redi[4];
   const int q = blockIdx.x;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
   const int n_c = kk * SEARCH_GROUP;
   const float* row = cand + (int64_t)q * n_c;
   if (tid < kk) grp[tid] = sorted[(int64_t)q * kk + tid];
   __syncthreads();
-  float best = -INFINITY;
-  int besti = 0x7fffffff;
-  for (int c = tid; c < n_c; c += 256) {
+  for (int c = tid; c < n_c; c += 256) {                 // the positions this thread owns in topk_rounds: no barrier needed
     const int gi = grp[c >> 4];
     float v = row[c];
     if (!(v == v)) v = -INFINITY;                        // NaN sorts last
     if (gi < 0 || gi * SEARCH_GROUP + (c & 15) >= n_g) v = __builtin_nanf("");      // not a gallery item: retired
     val[c] = v;
-    if (v == v && (besti == 0x7fffffff || v > best)) { best = v; besti = c; }      // ascending c: the first maximum is the lowest index
   }
-  __syncthreads();
-  for (int r = 0; r < k; ++r) {
-    float bv = best;
-    int bi = besti;
-    wave_argmax(bv, bi);
-    if (lane == 0) { redv[wave] = bv; redi[wave] = bi; }
-    __syncthreads();
-    bv = redv[0]; bi = redi[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-      if (redv[w] > bv || (redv[w] == bv && redi[w] < bi)) { bv = redv[w]; bi = redi[w]; }
-    const bool live = bi != 0x7fffffff;
-    if (tid == 0) {
-      out_idx[(int64_t)q * k + r] = live ? grp[bi >> 4] * SEARCH_GROUP + (bi & 15) : -1;
-      if (out_val) out_val[(int64_t)q * k + r] = live ? bv : -INFINITY;
-    }
-    if (live && (bi & 255) == tid) {                     // the owner retires the winner and rescans its elements
-      val[bi] = __builtin_nanf("");
-      best = -INFINITY;
-      besti = 0x7fffffff;
-      for (int c = tid; c < n_c; c += 256) {
-        const float v = val[c];
-        if (v == v && (besti == 0x7fffffff || v > best)) { best = v; besti = c; }
-      }
-    }
-    __syncthreads();
-  }
+  topk_rounds(val, n_c, k, redv, redi, [&](int r, bool live, float v, int pos) {
+    out_idx[(int64_t)q * k + r] = live ? grp[pos >> 4] * SEARCH_GROUP + (pos & 15) : -1;
+    if (out_val) out_val[(int64_t)q * k + r] = live ? v : -INFINITY;
+  });
 }
 
 template <int DIM, bool COLLECT>
-static int search_gemm_launch(const SearchWs& ws, const SearchGeom& g, int n_img, int n_cap, int Mp, int Np, int Dp, hipStream_t st) {
+static int search_gemm_launch(const SearchWs& ws, const SearchGeom& g, int n_img, int n_cap, hipStream_t st) {
+  const int Mp = ws.sim.Mp, Np = ws.sim.Np, Dp = ws.sim.Dp;
   static unsigned long long lds_reserved = 0;
   if (int rc = aladin_reserve_lds((const void*)search_gemm_kernel<DIM, COLLECT>, SimCfg::LDS_BYTES, &lds_reserved, "search_gemm")) return rc;
   const int n_mblk = Mp / SimCfg::BM, n_nblk = Np / SimCfg::BN;
-  hipLaunchKernelGGL((search_gemm_kernel<DIM, COLLECT>), dim3(n_mblk * n_nblk), dim3(SimCfg::THREADS), SimCfg::LDS_BYTES, st, ws.sim.a, ws.sim.b,
-                     ws.sim.scale, n_img, n_cap, (int64_t)2 * Dp, Dp / 64, n_nblk, n_mblk * n_nblk, ws.gmax, ws.table, ws.cand, g.G_ld, g.kk);
+  hipLaunchKernelGGL((search_gemm_kernel<DIM, COLLECT>), dim3(n_mblk * n_nblk), dim3(SimCfg::THREADS), SimCfg::LDS_BYTES, st, ws.sim.ws.a, ws.sim.ws.b,
+                     ws.sim.ws.scale, n_img, n_cap, (int64_t)2 * Dp, Dp / 64, n_nblk, n_mblk * n_nblk, ws.gmax, ws.table, ws.cand, g.G_ld, g.kk);
   return aladin_check_launch(COLLECT ? "search_gemm_kernel (collect)" : "search_gemm_kernel (group maxima)");
 }
 
@@ -308,18 +277,17 @@ extern "C" int aladin_search_topk(const float* img, int64_t img_rs, const float*
   hipStream_t st = (hipStream_t)stream;
   SearchWs ws;
   SearchGeom g;
-  int Mp, Np, Dp;
-  search_layout(n_img, n_cap, D, k, dim, (char*)workspace, &ws, &g, &Mp, &Np, &Dp);
-  int rc = sim_prepare(img, img_rs, cap, cap_rs, n_img, n_cap, D, workspace, &ws.sim, &Mp, &Np, &Dp, st);
+  search_layout(n_img, n_cap, D, k, dim, (char*)workspace, &ws, &g);
+  int rc = sim_prepare(SimIn{img, img_rs, cap, cap_rs, n_img, n_cap, D}, workspace, st, &ws.sim, nullptr);
   if (rc) return rc;
-  if ((rc = dim == 1 ? search_gemm_launch<1, false>(ws, g, n_img, n_cap, Mp, Np, Dp, st)
-                     : search_gemm_launch<0, false>(ws, g, n_img, n_cap, Mp, Np, Dp, st)))
+  if ((rc = dim == 1 ? search_gemm_launch<1, false>(ws, g, n_img, n_cap, st)
+                     : search_gemm_launch<0, false>(ws, g, n_img, n_cap, st)))
     return rc;
   if ((rc = sim_topk_launch(ws.gmax, g.G_ld, 1, g.n_q, g.n_groups, g.kk, ws.sel, nullptr, st))) return rc;
   hipLaunchKernelGGL(search_slots_kernel, dim3(g.n_q), dim3(256), 0, st, ws.sel, g.n_groups, g.kk, g.G_ld, ws.sorted, ws.table);
   if ((rc = aladin_check_launch("search_slots_kernel"))) return rc;
-  if ((rc = dim == 1 ? search_gemm_launch<1, true>(ws, g, n_img, n_cap, Mp, Np, Dp, st)
-                     : search_gemm_launch<0, true>(ws, g, n_img, n_cap, Mp, Np, Dp, st)))
+  if ((rc = dim == 1 ? search_gemm_launch<1, true>(ws, g, n_img, n_cap, st)
+                     : search_gemm_launch<0, true>(ws, g, n_img, n_cap, st)))
     return rc;
   hipLaunchKernelGGL(search_final_kernel, dim3(g.n_q), dim3(256), 0, st, ws.cand, ws.sorted, g.n_g, g.kk, k, out_idx, out_val);
   return aladin_check_launch("search_final_kernel");

@@ -27,6 +27,11 @@ def sim_matrix(img, cap):
     return sim
 
 
+def _rank_outputs(n_img, n_cap, dev):
+    """(rank_i2t, top1_i2t, rank_t2i, top1_t2i): uninitialised int32 outputs of the two rank entry points."""
+    return tuple(torch.empty(n, dtype=torch.int32, device=dev) for n in (n_img, n_img, n_cap, n_cap))
+
+
 def recall_ranks(sim, caps_per_img=5):
     """(rank_i2t, top1_i2t, rank_t2i, top1_t2i) int32 device tensors from a (n_img, 5*n_img) score
     matrix; replaces the argsort/where loops of reference alad/recall_auxiliary.py:34-56."""
@@ -35,10 +40,7 @@ def recall_ranks(sim, caps_per_img=5):
     sim = sim if sim.stride(1) == 1 else sim.contiguous()
     n_img, n_cap = sim.shape
     dev = sim.device
-    r_i2t = torch.empty(n_img, dtype=torch.int32, device=dev)
-    t_i2t = torch.empty(n_img, dtype=torch.int32, device=dev)
-    r_t2i = torch.empty(n_cap, dtype=torch.int32, device=dev)
-    t_t2i = torch.empty(n_cap, dtype=torch.int32, device=dev)
+    r_i2t, t_i2t, r_t2i, t_t2i = _rank_outputs(n_img, n_cap, dev)
     ws = _workspace(lib.aladin_recall_workspace_bytes(n_cap), dev)
     _lib.check(lib.aladin_recall_ranks(_ptr(sim), _ld(sim), n_img, n_cap, caps_per_img, _ptr(r_i2t), _ptr(t_i2t),
                                        _ptr(r_t2i), _ptr(t_t2i), _ptr(ws), _stream()), 'recall_ranks')
@@ -64,10 +66,7 @@ def retrieval_ranks(img, cap, caps_per_img=5, exact=False, return_stats=False):
     cap = cap if cap.stride(1) == 1 else cap.contiguous()
     n_img, n_cap, D = img.shape[0], cap.shape[0], img.shape[1]
     dev = img.device
-    r_i2t = torch.empty(n_img, dtype=torch.int32, device=dev)
-    t_i2t = torch.empty(n_img, dtype=torch.int32, device=dev)
-    r_t2i = torch.empty(n_cap, dtype=torch.int32, device=dev)
-    t_t2i = torch.empty(n_cap, dtype=torch.int32, device=dev)
+    r_i2t, t_i2t, r_t2i, t_t2i = _rank_outputs(n_img, n_cap, dev)
     ws = _workspace(lib.aladin_retrieval_workspace_bytes(n_img, n_cap, D), dev)
     fn = lib.aladin_retrieval_ranks_exact if exact else lib.aladin_retrieval_ranks
     _lib.check(fn(_ptr(img), img.stride(0), _ptr(cap), cap.stride(0), n_img, n_cap, D, caps_per_img,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Timing of BASELINE configs[2] (evaluation): 5000 x 25000 x 768 matching-head similarity + ranks,
 and the alignment-head grid 1000 x 5000 at padded length 71.  Prints one JSON line per workload.
-Not the driver's bench (that is bench.py); used for DESIGN.md / profiles."""
+Not the driver's bench (that is bench.py); used for DESIGN.md / profiles.  --matching-only: the first workload alone."""
 import json
 import os
 import sys
@@ -43,6 +43,8 @@ def main():
                       'rank_ms': round(ms_rank, 3), 'torch_mm_fp32_ms': round(ms_torch, 3),
                       'fused_sim_plus_rank_ms': round(ms_fused, 3),
                       'sim_tflops_algorithmic': round(flops / ms_sim / 1e9, 1)}))
+    if '--matching-only' in sys.argv:
+        return
     n = 1000
     images, captions, il, cl = synth.eval_sets(n, 768, seed=9)
     ia = torch.from_numpy(images[0::5]).to(dev)

@@ -6,6 +6,10 @@ builds (an old library built from another checkout against the new one):
     python tools/check_variant.py save new.pt
     python tools/check_variant.py cmp old.pt new.pt
 
+`save FILE retrieval` saves the retrieval group instead (`save FILE all`: both): the stored similarity matrix with its ranks and
+top-k lists, the fused retrieval (screened and exact=True; its four outputs, not its scheduling-dependent statistics) on clean
+data and on the 'bulk' / 'exact_ties' recipes of tests/test_gpu_parity.py, and the top-k gallery search with its scores.
+
 Scores: the bench batch (B = 256, full lengths) and a ragged batch; one small ragged problem per body and epilogue variant of the
 score kernels (SCORE_CASES: the geometry and the grid rule that select the body are asserted), in fp16 and split precision.
 Arg-max table: the sum-of-violations step with the dense table forced, one problem per variant of the arg-max kernels
@@ -180,6 +184,61 @@ def gradient_cases(ops, synth, dev):
     return out
 
 
+def adversarial_retrieval(case, n_img, cpi, D, seed):
+    """The 'bulk' and 'exact_ties' recipes of tests/test_gpu_parity.py::_adversarial_retrieval."""
+    rng = np.random.default_rng(seed)
+    img = rng.standard_normal((n_img, D)).astype(np.float32)
+    img /= np.linalg.norm(img, axis=1, keepdims=True)
+    if case == 'bulk':                   # ground truths inside the bulk of the scores: captions unrelated to their images
+        cap = rng.standard_normal((n_img * cpi, D)).astype(np.float32)
+        cap /= np.linalg.norm(cap, axis=1, keepdims=True)
+    elif case == 'exact_ties':           # bit-identical caption rows under different images, duplicated images too
+        cap = np.repeat(img, cpi, axis=0) + 0.8 * rng.standard_normal((n_img * cpi, D)).astype(np.float32)
+        cap /= np.linalg.norm(cap, axis=1, keepdims=True)
+        k = n_img * cpi
+        src = rng.integers(0, k, size=k // 3)
+        dst = rng.permutation(k)[:src.size]
+        cap[dst] = cap[src]
+        isrc = rng.integers(0, n_img, size=n_img // 4)
+        idst = rng.permutation(n_img)[:isrc.size]
+        img[idst] = img[isrc]
+    else:
+        raise ValueError(case)
+    return img, cap.astype(np.float32)
+
+
+def retrieval_cases(ops, synth, dev):
+    """-> {name: tensor}: every output of the evaluation similarity paths, for equality between two builds."""
+    out = {}
+    T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    names = ('rank_i2t', 'top1_i2t', 'rank_t2i', 'top1_t2i')
+    # the stored matrix and its ranks: the three row splits of aladin_recall_ranks (below 256 images, from 256, from 2048)
+    for n_img, cpi, D in ((7, 1, 33), (300, 5, 64), (2050, 1, 40)):
+        img, cap = synth.retrieval_embeddings(n_img, D, seed=300 + n_img, sigma=2.0, caps_per_img=cpi)
+        sim = ops.sim_matrix(T(img[::cpi]), T(cap))
+        tag = 'stored-%dx%d-D%d' % (n_img, cpi, D)
+        out[tag + '/sim'] = sim.cpu()
+        for nm, t in zip(names, ops.recall_ranks(sim, caps_per_img=cpi)):
+            out[tag + '/' + nm] = t.cpu()
+        for dim in (0, 1):
+            for k in (1, 50):
+                out['%s/topk-dim%d-k%d' % (tag, dim, k)] = ops.topk_indices(sim, k, dim=dim).cpu()
+    for n_img, cpi, D in ((1, 5, 8), (257, 8, 50), (700, 5, 768)):
+        img_rep, cap = synth.retrieval_embeddings(n_img, D, seed=400 + n_img, sigma=2.0, caps_per_img=cpi)
+        data = [('clean', img_rep[::cpi], cap)]
+        data += [(case,) + adversarial_retrieval(case, n_img, cpi, D, seed=500 + n_img) for case in ('bulk', 'exact_ties')]
+        for case, img, cap in data:
+            for exact in (False, True):
+                for nm, t in zip(names, ops.retrieval_ranks(T(img), T(cap), caps_per_img=cpi, exact=exact)):
+                    out['fused-%dx%d-D%d-%s-%s/%s' % (n_img, cpi, D, case, 'exact' if exact else 'screened', nm)] = t.cpu()
+    img, cap = T(synth.normal((70, 64), 601)), T(synth.normal((4000, 64), 602))
+    for dim in (0, 1):
+        for k in (1, 50, 256):
+            idx, val = ops.search_topk(img, cap, k, dim=dim, return_scores=True)
+            out['search-70x4000-D64-dim%d-k%d/idx' % (dim, k)], out['search-70x4000-D64-dim%d-k%d/val' % (dim, k)] = idx.cpu(), val.cpu()
+    return out
+
+
 def main():
     if sys.argv[1] == 'cmp':
         a, b = torch.load(sys.argv[2]), torch.load(sys.argv[3])
@@ -191,18 +250,23 @@ def main():
                 continue
             same = torch.equal(a[k], b[k])
             ok &= same
-            print('%-34s %s  max |diff| %.3g' % (k, 'bit-identical' if same else 'DIFFERENT', float((a[k] - b[k]).abs().max())))
+            print('%-34s %s  max |diff| %.3g' % (k, 'bit-identical' if same else 'DIFFERENT', float((a[k].double() - b[k].double()).abs().max())))
         sys.exit(0 if ok else 1)
     from aladin_amd import ops, synth
     dev = torch.device('cuda:0')
     out = {}
-    for tag, ragged, seed in (('full', False, 1234), ('ragged', True, 99)):
-        im, s, il, sl = synth.alignment_batch(256, 34, 50, 768, seed=seed, ragged=ragged)
-        with torch.no_grad():
-            out[tag] = ops.alignment_scores(torch.from_numpy(im).to(dev), torch.from_numpy(s).to(dev), il, sl, precision='fp16').cpu()
-    out.update(score_cases(ops, synth, dev))
-    out.update(argmax_cases(ops, synth, dev))
-    out.update(gradient_cases(ops, synth, dev))
+    group = sys.argv[3] if len(sys.argv) > 3 else 'alignment'
+    assert group in ('alignment', 'retrieval', 'all'), group
+    if group in ('alignment', 'all'):
+        for tag, ragged, seed in (('full', False, 1234), ('ragged', True, 99)):
+            im, s, il, sl = synth.alignment_batch(256, 34, 50, 768, seed=seed, ragged=ragged)
+            with torch.no_grad():
+                out[tag] = ops.alignment_scores(torch.from_numpy(im).to(dev), torch.from_numpy(s).to(dev), il, sl, precision='fp16').cpu()
+        out.update(score_cases(ops, synth, dev))
+        out.update(argmax_cases(ops, synth, dev))
+        out.update(gradient_cases(ops, synth, dev))
+    if group in ('retrieval', 'all'):
+        out.update(retrieval_cases(ops, synth, dev))
     torch.save(out, sys.argv[2])
     print('saved', sys.argv[2], {k: float(v.double().sum()) for k, v in out.items()})
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC passes (one counter group per run, kernel-trace only) over configs[2]'s kernels (recall.hip: sim_screen_kernel on easy .. hard data,
+# PMC passes (one counter group per run, kernel-trace only) over configs[2]'s kernels (retrieval.hip, sim_pack.hip: sim_screen_kernel on easy .. hard data,
 # packers, ground-truth and re-score kernels; tools/bench_retrieval.py --profile) -> gpurun_out/<tag>/pmc_*; materialise with tools/materialise_profiles.py <tag> -> profiles/<tag>_pmc.json
 set -u
 TAG=${1:-r04_eval}

@@ -19,9 +19,9 @@ for sigma, exact in ((3.0, False), (6.0, False), (8.0, False), (12.0, False), (1
     torch.cuda.synchronize()
     so = lib.aladin_retrieval_stats_offset(n_img, n_cap, D)
     n_tiles = 20 * 66
-    CAP = 512                                        # SIM_LIST_CAP (csrc/recall.hip)
+    CAP = 512                                        # SIM_LIST_CAP (csrc/retrieval.hip)
     r256 = lambda b: (b + 255) // 256 * 256
-    # workspace behind the statistics (retr_layout): lob_i2t (Mp words), lob_t2i (Np words), list_cnt (n_tiles words), lists
+    # workspace behind the statistics (retr_layout, csrc/retrieval.hip): lob_i2t (Mp words), lob_t2i (Np words), list_cnt (n_tiles words), lists
     lo = so + 256 + r256(20 * 256 * 4) + r256(66 * 384 * 4) + r256(n_tiles * 4)
     seg = ws[lo:lo + n_tiles * CAP * 16].view(torch.int64).view(n_tiles, 2 * CAP)[:, 2 * CAP - 12:].cpu().numpy().astype(np.float64)
     # a tile that listed more than CAP - 6 pairs wrote list entries over its stamps: leave it out (counted below)
