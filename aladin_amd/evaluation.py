@@ -154,7 +154,7 @@ def compute_sim_matrix(img, cap, img_len=None, cap_len=None, mode='matching', pr
 
     mode='matching'  : img (N_img, D), cap (N_cap, D) global embeddings -> img @ cap.T
     mode='alignment' : img (N_img, R, D), cap (N_cap, T, D) sets with length lists -> MrSw scores
-                       (trimmed to the real lengths, chunked, in the evaluation precision: ops._scores_nograd;
+                       (trimmed to the real lengths, chunked, in the evaluation precision: eval_grid.score_grid;
                        precision='fp16' | 'split' overrides ops.set_eval_precision())
     Both arguments may instead be PackedSetStore / StoreView objects (encode_data_packed).
     """
@@ -228,11 +228,14 @@ def _metrics(ranks):
     return r1, r5, r10, medr, meanr
 
 
-def _ranks(sim):
-    r_i2t, t_i2t, r_t2i, t_t2i = ops.recall_ranks(sim, CAPS_PER_IMG)
-    both = torch.cat([r_i2t, t_i2t, r_t2i, t_t2i]).cpu().numpy().astype(np.float64)      # one D2H copy
-    n_img, n_cap = sim.shape
+def _to_host(ranks4, n_img, n_cap):
+    """(rank_i2t, top1_i2t, rank_t2i, top1_t2i) device vectors -> float64 numpy arrays with ONE device-to-host copy."""
+    both = torch.cat(list(ranks4)).cpu().numpy().astype(np.float64)
     return both[:n_img], both[n_img:2 * n_img], both[2 * n_img:2 * n_img + n_cap], both[2 * n_img + n_cap:]
+
+
+def _ranks(sim):
+    return _to_host(ops.recall_ranks(sim, CAPS_PER_IMG), *sim.shape)
 
 
 def _fused_ranks(img, cap):
@@ -241,11 +244,8 @@ def _fused_ranks(img, cap):
     dev = _device()
     img = torch.as_tensor(img).to(dev, torch.float32)
     cap = torch.as_tensor(cap).to(dev, torch.float32)
-    n_img, n_cap = img.shape[0], cap.shape[0]
     with torch.no_grad():
-        r_i2t, t_i2t, r_t2i, t_t2i = ops.retrieval_ranks(img, cap, CAPS_PER_IMG)
-    both = torch.cat([r_i2t, t_i2t, r_t2i, t_t2i]).cpu().numpy().astype(np.float64)      # one D2H copy
-    return both[:n_img], both[n_img:2 * n_img], both[2 * n_img:2 * n_img + n_cap], both[2 * n_img + n_cap:]
+        return _to_host(ops.retrieval_ranks(img, cap, CAPS_PER_IMG), img.shape[0], cap.shape[0])
 
 
 def recall(images, captions, model, mode='i2t', lenghts=None, return_ranks=False):

@@ -35,7 +35,6 @@ _GEOM_CACHE = {}
 # Differentiable scores always use fp16 operands (north_star's 1e-3 tolerance; the backward re-decides its
 # arg-maxima in exact fp32 anyway).
 _EVAL_PRECISION = ['split']
-E_SCRATCH_LIMIT = 2 << 30       # bytes of side-GEMM scratch per score launch before the sum side is chunked
 
 
 def set_eval_precision(precision):
@@ -610,189 +609,9 @@ def alignment_triplet_loss(im_set, s_seq, im_len, s_len, margin, max_violation):
     return _AlignTriplet.apply(im_set, s_seq, im_len_t, s_len_t, margin, max_violation, fill)
 
 
-def _host_lengths(lens):
-    return [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
-
-
-# ------------------------------------------------------------------------------------------------
-# Length-bucketed evaluation grids.  The packed geometry pads the max side to its region classes (32 rows, 32 + up to 8
-# side rows, 48, 48 + up to 8 side rows, 64, 96: align_fwd.hip geometry) and the sum side to 8, 16, 24, 32, 40, 48, 64 or 96
-# words: one launch over the whole grid pays
-# for the LONGEST image and caption at every pair.  Real sets are ragged (COCO: 10-50 boxes, captions of ~12 tokens),
-# so the samples of each side are grouped by the tile class their own length needs, every (image class x caption
-# class) block is scored with its own geometry, and the blocks are laid back in the callers' order.  A score only
-# depends on its own image and caption rows (masked positions are zero rows whatever the class), so the scores are
-# those of the single launch up to the summation order of a different kernel variant (~1e-7 in split precision).
-# ------------------------------------------------------------------------------------------------
-X_CLASS_BOUNDS = (32, 40, 48, 56, 64, 96)  # scored max-side positions (incl. the one masked position kept for the zero fill)
-Y_CLASS_BOUNDS = (8, 16, 24, 32, 40, 48, 64, 96)   # scored sum-side positions (8 / 24 / 40: two captions share one / three / five 16-word tiles)
-BUCKET_MIN_PAIRS = 1 << 18                 # below this a grid is one launch
-BUCKET_MIN_SAMPLES = 64                    # smaller classes join the next longer one
-BUCKET_MIN_GAIN = 0.10                     # padded work saved before bucketing is worth its extra launches
-
-
-def _needed_positions(lens, tail, total, keep_masked):
-    """Positions of the packed operand sample k needs: its scored positions (len - 1 - tail, clamped to the set), plus one
-    masked position on the max side when the sample is shorter than the set (alad/loss.py:116,124: the zero fill takes
-    part in the max)."""
-    cap = max(total - 1 - tail, 1)
-    out = []
-    for v in lens:
-        n = min(max(int(v) - 1 - tail, 1), cap)
-        out.append(min(n + 1, cap) if keep_masked and n < cap else n)
-    return out
-
-
-def bucket_plan(x_need, y_need):
-    """-> (x_groups, y_groups) lists of index lists (callers' order inside a group), or None when one launch is the better
-    choice.  x_need / y_need: positions per sample (_needed_positions)."""
-    def groups(need, bounds):
-        cls = [[] for _ in bounds]
-        for k, n in enumerate(need):
-            for c, b in enumerate(bounds):
-                if n <= b or c == len(bounds) - 1:
-                    cls[c].append(k)
-                    break
-        for c in range(len(cls) - 1):                               # small classes join the next longer one
-            if 0 < len(cls[c]) < BUCKET_MIN_SAMPLES:
-                cls[c + 1] = sorted(cls[c] + cls[c + 1])
-                cls[c] = []
-        last = [c for c in range(len(cls)) if cls[c]]
-        if len(last) > 1 and len(cls[last[-1]]) < BUCKET_MIN_SAMPLES:   # a small LAST class takes its neighbour in
-            cls[last[-1]] = sorted(cls[last[-2]] + cls[last[-1]])
-            cls[last[-2]] = []
-        return [(g, bounds[c]) for c, g in enumerate(cls) if g]
-    if len(x_need) * len(y_need) < BUCKET_MIN_PAIRS:
-        return None
-    gx, gy = groups(x_need, X_CLASS_BOUNDS), groups(y_need, Y_CLASS_BOUNDS)
-    if len(gx) == 1 and len(gy) == 1:
-        return None
-
-    def padded(n, bounds):
-        return next((b for b in bounds if n <= b), bounds[-1])
-    one = len(x_need) * len(y_need) * padded(max(x_need), X_CLASS_BOUNDS) * padded(max(y_need), Y_CLASS_BOUNDS)
-    work = sum(len(a) * len(b) * padded(max(x_need[k] for k in a), X_CLASS_BOUNDS) * padded(max(y_need[k] for k in b), Y_CLASS_BOUNDS)
-               for a, _ in gx for b, _ in gy)
-    if work > (1.0 - BUCKET_MIN_GAIN) * one:
-        return None
-    return [a for a, _ in gx], [b for b, _ in gy]
-
-
-def _index_tensor(ids, device, dtype=torch.int64):
-    """Index list -> device tensor WITHOUT making the host wait for the device (torch.tensor(..., device=...) is a blocking
-    copy: it drains the stream, and a grid scored in blocks would serialise host and GPU work block by block)."""
-    return torch.tensor(ids, dtype=dtype).to(device, non_blocking=True)
-
-
-class GridPlan:
-    """The length classes of one evaluation grid, with everything the blocks need already on the device: per-class index
-    tensors and the permutation that lays the class-ordered blocks back in the callers' order.  Built once per
-    (lengths, device) and cached: validation scores the same sets twice per epoch (i2t, t2i) and every epoch again."""
-
-    def __init__(self, gx, gy, device):
-        self.gx, self.gy = gx, gy
-        self.ix = [_index_tensor(g, device) for g in gx]
-        self.iy = [_index_tensor(g, device) for g in gy]
-        Bx, By = sum(len(g) for g in gx), sum(len(g) for g in gy)
-        inv_x = torch.empty(Bx, dtype=torch.int64)
-        inv_x[torch.tensor([k for g in gx for k in g], dtype=torch.int64)] = torch.arange(Bx, dtype=torch.int64)
-        inv_y = torch.empty(By, dtype=torch.int64)
-        inv_y[torch.tensor([k for g in gy for k in g], dtype=torch.int64)] = torch.arange(By, dtype=torch.int64)
-        self.inv_x, self.inv_y = inv_x.to(device, non_blocking=True), inv_y.to(device, non_blocking=True)
-        self.extra = {}                                   # per-caller attachments (store views)
-
-    def assemble(self, blocks):
-        """Blocks scored in class order -> the (Bx, By) matrix in the callers' order."""
-        rows = [torch.cat([blocks[(a, b)] for b in range(len(self.gy))], dim=1) for a in range(len(self.gx))]
-        return torch.cat(rows, dim=0).index_select(0, self.inv_x).index_select(1, self.inv_y)
-
-
-_PLAN_CACHE = {}
-
-
-def grid_plan(key, x_need_fn, y_need_fn, device):
-    """Cached GridPlan (or None: one launch) for `key`; the *_need_fn callables are only evaluated on a miss."""
-    key = key + (str(device),)
-    if key in _PLAN_CACHE:
-        return _PLAN_CACHE[key]
-    plan = bucket_plan(x_need_fn(), y_need_fn())
-    entry = GridPlan(plan[0], plan[1], device) if plan is not None else None
-    if len(_PLAN_CACHE) >= 8:
-        _PLAN_CACHE.clear()
-    _PLAN_CACHE[key] = entry
-    return entry
-
-
-def _scores_nograd(xs, ys, x_len, y_len, x_tail, y_tail, precision):
-    """(Bx, By) scores of a max-side set xs (Bx, N, D) against a sum-side set ys (By, M, D) outside autograd:
-    the evaluation path.  Four things the differentiable path does not do:
-      * operands in the evaluation precision (split fp16 by default: rank-exact Recall);
-      * both sets are trimmed to the positions that can matter.  encode_data pads every set to 71 positions
-        (alad/evaluation.py:98-99); positions past a set's length are masked to 0 by alad/loss.py:103-116
-        whatever they hold.  On the SUM side a masked position adds exactly 0, so the set is cut at the
-        longest length.  On the MAX side the masked positions still take part in the max as zeros
-        (`max(real dots, 0)`, alad/loss.py:116,124) for every sample shorter than the padded set, so ONE
-        masked position is kept: the set is cut at the longest length + 1 (or not at all when some sample
-        fills it).  The 70 x 68 padded block per pair shrinks to the real one and no score changes;
-      * large ragged grids are scored in length classes (bucket_plan above): a pair pays for the tile class of ITS image
-        and caption, not for the longest of the evaluation set;
-      * the sum side is chunked so the side-row scratch of the score kernel stays under E_SCRATCH_LIMIT
-        (16 GB at 5000 x 25000 otherwise); a score does not depend on the chunking."""
-    x_len, y_len = _host_lengths(x_len), _host_lengths(y_len)
-    dev = xs.device
-    plan = None
-    # a grid whose trimmed sets are past the tile classes is one launch of the long-set kernels (no length classes beyond 96)
-    if len(x_len) * len(y_len) >= BUCKET_MIN_PAIRS and \
-            not is_long(min(xs.shape[1], max(x_len) + 1), min(ys.shape[1], max(y_len)), x_tail, y_tail):
-        plan = grid_plan(('dense', tuple(x_len), tuple(y_len), x_tail, y_tail, xs.shape[1], ys.shape[1]),
-                         lambda: _needed_positions(x_len, x_tail, xs.shape[1], True),
-                         lambda: _needed_positions(y_len, y_tail, ys.shape[1], False), dev)
-    if plan is None:
-        return _scores_nograd_block(xs, ys, x_len, y_len, x_tail, y_tail, precision)
-    blocks = {}
-    ysub = []
-    for b, ib in zip(plan.gy, plan.iy):
-        m_eff = min(ys.shape[1], max(2 + y_tail, max(y_len[k] for k in b)))
-        ysub.append((ys[:, :m_eff].index_select(0, ib), [y_len[k] for k in b]))
-    for ia, (a, ixa) in enumerate(zip(plan.gx, plan.ix)):
-        n_eff = min(xs.shape[1], max(2 + x_tail, max(x_len[k] for k in a) + 1))
-        xa = xs[:, :n_eff].index_select(0, ixa)
-        la = [x_len[k] for k in a]
-        for ib, (yb, lb) in enumerate(ysub):
-            # the block keeps the FULL set's zero-fill rule: a sample is "shorter than the padded set" relative to xs, not to
-            # its class, which _scores_nograd_block reproduces because every class member is cut at its class's longest + 1
-            blocks[(ia, ib)] = _scores_nograd_block(xa, yb, la, lb, x_tail, y_tail, precision, x_total=xs.shape[1])
-    return plan.assemble(blocks)
-
-
-def _scores_nograd_block(xs, ys, x_len, y_len, x_tail, y_tail, precision, x_total=None):
-    """One geometry for the whole block (see _scores_nograd).  x_total: positions of the set the block's max side was cut
-    from (a sample that fills IT has no masked position; default: xs itself)."""
-    x_total = xs.shape[1] if x_total is None else x_total
-    longest = max(x_len)
-    n_eff = min(xs.shape[1], max(2 + x_tail, longest + (1 if longest < x_total else 0)))
-    m_eff = min(ys.shape[1], max(2 + y_tail, max(y_len)))
-    xs, ys = xs[:, :n_eff], ys[:, :m_eff]
-    dev = xs.device
-    x_len_t, y_len_t = lengths_tensor(x_len, dev), lengths_tensor(y_len, dev)
-    Bx, By, D = xs.shape[0], ys.shape[0], xs.shape[2]
-    geom = _scoring_geometry(Bx, By, n_eff, m_eff, D, x_tail, y_tail, precision)
-    if geom.e_bytes <= E_SCRATCH_LIMIT:
-        return _align_forward(xs, ys, x_len_t, y_len_t, x_tail, y_tail, precision, norms=False)[0]
-    step = max(geom.cap_unit, int(By * E_SCRATCH_LIMIT // geom.e_bytes) // geom.cap_unit * geom.cap_unit)
-    xm, xe = pack_images(xs, x_len_t, geom)
-    S = torch.empty((Bx, By), dtype=torch.float32, device=dev)
-    for j0 in range(0, By, step):
-        j1 = min(By, j0 + step)
-        g = align_geometry(Bx, j1 - j0, n_eff, m_eff, D, x_tail, y_tail, precision)        # same max-side layout
-        y = pack_captions(ys[j0:j1], y_len_t[j0:j1].contiguous(), g)
-        scores_from_packed(xm, xe, y, g, out=S[:, j0:j1])
-    return S
-
-
 def alignment_scores(im_set, s_seq, im_len, s_len, aggregation='MrSw', precision=None):
     """S (Bi, Bc); replaces reference alad/loss.py:80-135.  Differentiable when autograd is on and an
-    input requires grad (fp16 operands); otherwise the evaluation path of _scores_nograd in the evaluation
+    input requires grad (fp16 operands); otherwise the evaluation grid of eval_grid.score_grid in the evaluation
     precision (`precision` overrides set_eval_precision()).
       'MrSw'  sum over words of the max over regions                       (:124-125)
       'MwSr'  sum over regions of the max over words: the same kernels with the two sets swapped --
@@ -809,12 +628,13 @@ def alignment_scores(im_set, s_seq, im_len, s_len, aggregation='MrSw', precision
         if im_set.shape[2] != s_seq.shape[2]:
             raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (im_set.shape[2], s_seq.shape[2]))
         prec = precision if precision is not None else _EVAL_PRECISION[0]
+        from .eval_grid import TensorSide, _host_lengths, score_grid        # (eval_grid imports this module)
         with torch.no_grad():
-            S = None
+            im, s, S = TensorSide(im_set, _host_lengths(im_len), 0), TensorSide(s_seq, _host_lengths(s_len), 2), None
             if aggregation in ('MrSw', 'symm'):
-                S = _scores_nograd(im_set, s_seq, im_len, s_len, 0, 2, prec)
+                S = score_grid(im, s, prec)
             if aggregation in ('MwSr', 'symm'):
-                St = _scores_nograd(s_seq, im_set, s_len, im_len, 2, 0, prec).t()
+                St = score_grid(s, im, prec).t()
                 S = St if S is None else S + St
         return S
     if precision not in (None, 'fp16'):

@@ -12,11 +12,9 @@ two retrieval heads read and nothing else:
 COCO-5k captions (25 000 x ~12 scored words x 768) take 0.46 GB instead of 5.4 GB; alignment scores
 computed from a store are bit-identical to those computed from the fp32 sets (same fp16 operands).
 """
-import ctypes as C
-
 import torch
 
-from . import _lib, ops
+from . import _lib, eval_grid, ops
 
 
 class PackedSetStore:
@@ -142,95 +140,23 @@ def _unwrap(x):
     return (x.store, x.ids, x.ids_t) if isinstance(x, StoreView) else (x, None, None)
 
 
-def alignment_scores_from_stores(img, cap):
-    """(N_img, N_cap) 'MrSw' scores (reference alad/loss.py:80-125) between two stores / views: operands are row
-    copies of the stores (no fp32 read, no normalisation).  Large ragged grids are scored in length classes
-    (ops.bucket_plan: a pair pays for the tile class of its own image and caption); each class block is
-    _store_scores_block."""
-    si, ids_i, _ = _unwrap(img)
-    sc, ids_c, _ = _unwrap(cap)
+def _check_pair(img, cap):
+    """What every score of two stores / views needs: samples on both sides, one feature size, one precision."""
+    si, sc = getattr(img, 'store', img), getattr(cap, 'store', cap)
     if len(img) < 1 or len(cap) < 1:
         raise ValueError('aladin_amd: empty store')
-    if len(img) * len(cap) < ops.BUCKET_MIN_PAIRS:
-        return _store_scores_block(img, cap)
-    ids_i = list(range(len(si))) if ids_i is None else list(ids_i)
-    ids_c = list(range(len(sc))) if ids_c is None else list(ids_c)
-    cap_x = max(si.padded_len - 1 - si.tail, 1)
-
-    def need_x():
-        return [min(max(si._counts[k], 1) + 1, cap_x) if si._counts[k] < cap_x else cap_x for k in ids_i]
-
-    def need_y():
-        return [max(sc._counts[k], 1) for k in ids_c]
-    # keyed on the stores' identity and fill state: an append invalidates the plan
-    plan = ops.grid_plan(('store', id(si), si.n_rows, len(si), id(sc), sc.n_rows, len(sc), tuple(ids_i), tuple(ids_c)),
-                         need_x, need_y, si.device)
-    if plan is None:
-        return _store_scores_block(img, cap)
-    # class views: python id lists for the host-side geometry, device id tensors by an index_select of the callers' ids
-    # (no blocking copy between the blocks); nothing that references the stores is kept in the cached plan
-    base_i = img.ids_t if isinstance(img, StoreView) else torch.arange(len(si), dtype=torch.int32, device=si.device)
-    base_c = cap.ids_t if isinstance(cap, StoreView) else torch.arange(len(sc), dtype=torch.int32, device=sc.device)
-    vx, vy = [], []
-    for g, ig in zip(plan.gx, plan.ix):
-        v = StoreView(si, [ids_i[k] for k in g])
-        v._ids_t = base_i.index_select(0, ig)
-        vx.append(v)
-    for g, ig in zip(plan.gy, plan.iy):
-        v = StoreView(sc, [ids_c[k] for k in g])
-        v._ids_t = base_c.index_select(0, ig)
-        vy.append(v)
-    blocks = {(a, b): _store_scores_block(va, vb) for a, va in enumerate(vx) for b, vb in enumerate(vy)}
-    return plan.assemble(blocks)
-
-
-def _store_scores_block(img, cap):
-    """One geometry for the whole block.  One score launch, or one per caption chunk when the side-row scratch
-    (N_img x 16*tp16*N_cap floats when R' = 33) would pass E_SCRATCH_LIMIT -- 16 GB for a 5000 x 25000 grid otherwise;
-    a score does not depend on the chunking."""
-    si, ids_i, idt_i = _unwrap(img)
-    sc, ids_c, idt_c = _unwrap(cap)
     if si.D != sc.D:
         raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (si.D, sc.D))
-    Bi, Bc = len(img), len(cap)
-    if Bi < 1 or Bc < 1:
-        raise ValueError('aladin_amd: empty store')
     if si.precision != sc.precision:
         raise ValueError('aladin_amd: the two stores hold different precisions (%s vs %s)' % (si.precision, sc.precision))
-    # Max side: every sample shorter than the padded set (encode_data's 71 positions) takes the zero fill into
-    # its max over regions (alad/loss.py:116,124), so the geometry keeps ONE position past the longest count
-    # (a zero row in the operand) unless a sample fills the padded set; the sum side needs none.
-    Rq = min(max(si.max_count(ids_i), 1) + 1, si.padded_len - 1 - si.tail)
-    Tq = max(sc.max_count(ids_c), 1)
-    precision = si.precision
-    lib = _lib.load()
-    dev = si.device
-    oi, ci = si._tables()
-    oc, cc = sc._tables()
-    geom = ops.align_geometry(Bi, Bc, Rq + 1 + si.tail, Tq + 1 + sc.tail, si.D, si.tail, sc.tail, precision)
-    chunk = Bc
-    if geom.e_bytes > ops.E_SCRATCH_LIMIT:
-        chunk = max(geom.cap_unit, int(Bc * ops.E_SCRATCH_LIMIT // geom.e_bytes) // geom.cap_unit * geom.cap_unit)
-    xm = torch.empty(geom.xm_bytes // 2, dtype=torch.float16, device=dev)
-    xe = torch.empty(max(geom.xe_bytes // 2, 8), dtype=torch.float16, device=dev)
-    _lib.check(lib.aladin_align_pack_store_x(ops._ptr(si.rows), ops._ptr(oi), ops._ptr(ci), ops._ptr(idt_i), C.byref(geom),
-                                             ops._ptr(xm), ops._ptr(xe), ops._stream()), 'align_pack_store_x')
-    if chunk >= Bc:
-        y = torch.empty(geom.y_bytes // 2, dtype=torch.float16, device=dev)
-        _lib.check(lib.aladin_align_pack_store_y(ops._ptr(sc.rows), ops._ptr(oc), ops._ptr(cc), ops._ptr(idt_c), C.byref(geom),
-                                                 ops._ptr(y), ops._stream()), 'align_pack_store_y')
-        return ops.scores_from_packed(xm, xe, y, geom)
-    S = torch.empty((Bi, Bc), dtype=torch.float32, device=dev)
-    all_ids = idt_c if idt_c is not None else torch.arange(Bc, dtype=torch.int32, device=dev)
-    for j0 in range(0, Bc, chunk):
-        j1 = min(Bc, j0 + chunk)
-        g = ops.align_geometry(Bi, j1 - j0, Rq + 1 + si.tail, Tq + 1 + sc.tail, si.D, si.tail, sc.tail, precision)   # same x layout
-        y = torch.empty(g.y_bytes // 2, dtype=torch.float16, device=dev)
-        ids = all_ids[j0:j1].contiguous()
-        _lib.check(lib.aladin_align_pack_store_y(ops._ptr(sc.rows), ops._ptr(oc), ops._ptr(cc), ops._ptr(ids), C.byref(g),
-                                                 ops._ptr(y), ops._stream()), 'align_pack_store_y')
-        ops.scores_from_packed(xm, xe, y, g, out=S[:, j0:j1])
-    return S
+
+
+def alignment_scores_from_stores(img, cap):
+    """(N_img, N_cap) 'MrSw' scores (reference alad/loss.py:80-125) between two stores / views: operands are row copies of the
+    stores (no fp32 read, no normalisation).  The grid is eval_grid.score_grid's, as for tensors: length classes for large
+    ragged grids, caption chunks under eval_grid's scratch limit, and the zero fill of every image shorter than padded_len."""
+    _check_pair(img, cap)
+    return eval_grid.score_grid(eval_grid.StoreSide(img), eval_grid.StoreSide(cap), getattr(img, 'store', img).precision)
 
 
 def alignment_scores_for_pairs(img, cap, cand, direction='i2t'):
@@ -238,20 +164,15 @@ def alignment_scores_for_pairs(img, cap, cand, direction='i2t'):
     captions cand[q, :], 't2i' caption q against the images cand[q, :].  cand: (n_q, k) int32 device tensor of positions in the
     gallery view (a search_topk shortlist), -1 = no candidate (-inf in the result).  The rows are read where they lie in the
     stores (ops.align_rescore): work and memory follow n_q * k, not the grid, and a pair's bits do not depend on where it is
-    listed.  Semantics are those of _store_scores_block (zero fill for images shorter than the padded set included)."""
+    listed.  Semantics are those of alignment_scores_from_stores (zero fill for images shorter than the padded set included)."""
     from .evaluation import _is_packed_store
     if not (_is_packed_store(img) and _is_packed_store(cap)):
         raise ValueError('aladin_amd: alignment_scores_for_pairs takes two stores / views, not tensors')
     if direction not in ('i2t', 't2i'):
         raise ValueError("direction must be 'i2t' or 't2i'")
+    _check_pair(img, cap)
     si, ids_i, idt_i = _unwrap(img)
     sc, ids_c, idt_c = _unwrap(cap)
-    if si.D != sc.D:
-        raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (si.D, sc.D))
-    if si.precision != sc.precision:
-        raise ValueError('aladin_amd: the two stores hold different precisions (%s vs %s)' % (si.precision, sc.precision))
-    if len(img) < 1 or len(cap) < 1:
-        raise ValueError('aladin_amd: empty store')
     ops._check_shortlist(cand, len(img) if direction == 'i2t' else len(cap))
     oi, ci = si._tables()
     oc, cc = sc._tables()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised checks (GPU) of what round 3 added:
-  bucket    evaluation grids scored in length classes (ops.bucket_plan / GridPlan) vs the single launch and the float64 oracle,
+  bucket    evaluation grids scored in length classes (eval_grid.bucket_plan / GridPlan) vs the single launch and the float64 oracle,
             (N, L, D) tensors and packed stores (bit-equal to each other), random class thresholds;
   partners  the opt-in fp16-partner backward (ops.set_backward_precision('fp16')) vs the oracle's gradients: rtol 1e-3 + 5e-4 of the
             largest entry, and the same zero pattern as the exact path.
@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 import alad_oracle as O
-from aladin_amd import evaluation as E, ops, synth
+from aladin_amd import eval_grid, evaluation as E, ops, synth
 from aladin_amd.loss import AlignmentContrastiveLoss
 from aladin_amd.store import PackedSetStore
 
@@ -31,7 +31,7 @@ T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
 t0 = time.time()
 counts = {'bucket': 0, 'partners': 0, 'dense': 0}
 worst = {'bucket_split': 0.0, 'partners': 0.0, 'dense_gemm': 0.0, 'dense_gemm16': 0.0}
-real_plan = ops.bucket_plan
+real_plan = eval_grid.bucket_plan
 ops.DENSE_MIN_FRACTION = 0.0        # the dense path whatever the density of a case's dS
 ops.DENSE_GEMM_FORCE = True         # ... and the GEMM row step however full its captions
 while time.time() - t0 < budget:
@@ -46,11 +46,11 @@ while time.time() - t0 < budget:
         images, captions, il, cl = synth.eval_sets(n_img, D, case_seed % 100000, L=L, img_len_range=(lo_i, max(hi_i, lo_i)),
                                                    cap_len_range=(lo_c, max(hi_c, lo_c)), n_full=int(rng.randint(0, 3)))
         ims, ils = images[0::5], il[0::5]
-        ops.BUCKET_MIN_PAIRS, ops.BUCKET_MIN_SAMPLES, ops.BUCKET_MIN_GAIN = 1, int(rng.randint(1, 6)), float(rng.choice([0.0, 0.1]))
+        eval_grid.BUCKET_MIN_PAIRS, eval_grid.BUCKET_MIN_SAMPLES, eval_grid.BUCKET_MIN_GAIN = 1, int(rng.randint(1, 6)), float(rng.choice([0.0, 0.1]))
         for prec in ('split', 'fp16'):
             ops.set_eval_precision(prec)
-            ops._PLAN_CACHE.clear()
-            ops.bucket_plan = real_plan
+            eval_grid._PLAN_CACHE.clear()
+            eval_grid.bucket_plan = real_plan
             S_b = E.compute_sim_matrix(T(ims), T(captions), ils, cl, mode='alignment')
             si, sc = PackedSetStore(D, 0, dev, capacity_rows=64, precision=prec, padded_len=L), PackedSetStore(D, 2, dev, capacity_rows=64, precision=prec, padded_len=L)
             for k0 in range(0, images.shape[0], 7):
@@ -59,8 +59,8 @@ while time.time() - t0 < budget:
                 sc.append(T(captions[k0:k1, :max(cl[k0:k1])]), cl[k0:k1])
             S_s = E.compute_sim_matrix(si.view(slice(0, None, 5)), sc, mode='alignment')
             assert torch.equal(S_b, S_s), ('store != dense', case_seed, prec)
-            ops.bucket_plan = lambda *a: None
-            ops._PLAN_CACHE.clear()
+            eval_grid.bucket_plan = lambda *a: None
+            eval_grid._PLAN_CACHE.clear()
             S_1 = E.compute_sim_matrix(T(ims), T(captions), ils, cl, mode='alignment')
             ref = O.alignment_scores(ims, captions, ils, cl, dtype=np.float64)
             d1 = float((S_b - S_1).abs().max())
@@ -72,8 +72,8 @@ while time.time() - t0 < budget:
                 assert d1 <= 2e-6 + 1e-6 * scale and d2 <= 4e-6 + 3e-6 * scale, ('bucket split', case_seed, d1, d2, scale)
             else:
                 assert d1 <= 1e-5 * scale + 1e-6 and d2 <= 1e-3 * scale, ('bucket fp16', case_seed, d1, d2)
-        ops.bucket_plan = real_plan
-        ops._PLAN_CACHE.clear()
+        eval_grid.bucket_plan = real_plan
+        eval_grid._PLAN_CACHE.clear()
     elif kind == 'dense':
         B = int(rng.choice([128, 136, 160, 200, 256]))
         R, Tn, D = int(rng.randint(5, 67)), int(rng.randint(6, 51)), int(rng.choice([64, 128, 260, 768]))

@@ -791,30 +791,30 @@ def test_alignment_head_retrieval_coco1k(eval_precision, fixture):
 @pytest.mark.parametrize('img_range,cap_range,n_full', [((6, 70), (5, 66), 4), ((24, 56), (7, 30), 0)],
                          ids=['whole-range', 'coco-long-images'])
 def test_length_bucketed_grid_equals_the_single_launch(eval_precision, monkeypatch, img_range, cap_range, n_full):
-    """ops.bucket_plan: a large ragged evaluation grid is scored in length classes (each image / caption pays for the tile
+    """eval_grid.bucket_plan: a large ragged evaluation grid is scored in length classes (each image / caption pays for the tile
     class of its own length).  Against the single launch over the whole grid (the planner switched off) and the oracle, for
     (N, 71, D) tensors and for packed stores; images that fill the padded set (no zero fill in their max) included.  The
     second case is a COCO-like shape with images of up to 55 boxes + the global slot: its long images sit in the 48-row classes
     (48 and 48 + side rows), the single launch scores all of them there."""
-    from aladin_amd import evaluation as E, ops, synth
+    from aladin_amd import eval_grid, evaluation as E, synth
     n_img, D = 90, 128
     images, captions, il, cl = synth.eval_sets(n_img, D, seed=77, img_len_range=img_range, cap_len_range=cap_range, n_full=n_full)
     assert max(il) == (71 if n_full else img_range[1]) and min(il) < 30
     ims, ils = images[0::5], il[0::5]
-    monkeypatch.setattr(ops, 'BUCKET_MIN_PAIRS', 1)
-    monkeypatch.setattr(ops, 'BUCKET_MIN_SAMPLES', 8)
-    ops._PLAN_CACHE.clear()
-    plan = ops.bucket_plan(ops._needed_positions(ils, 0, 71, True), ops._needed_positions(cl, 2, 71, False))
+    monkeypatch.setattr(eval_grid, 'BUCKET_MIN_PAIRS', 1)
+    monkeypatch.setattr(eval_grid, 'BUCKET_MIN_SAMPLES', 8)
+    eval_grid._PLAN_CACHE.clear()
+    plan = eval_grid.bucket_plan([eval_grid.positions(v - 1, 70, True) for v in ils], [eval_grid.positions(v - 3, 68, False) for v in cl])
     assert plan is not None and len(plan[0]) >= 3 and len(plan[1]) >= (3 if n_full else 2)
     assert sorted(k for g in plan[0] for k in g) == list(range(n_img)) and sorted(k for g in plan[1] for k in g) == list(range(5 * n_img))
     S_b = E.compute_sim_matrix(T(ims), T(captions), ils, cl, mode='alignment')
     si, sc = _fill_stores(images, captions, il, cl, batch=53)
     S_bs = E.compute_sim_matrix(si.view(slice(0, None, 5)), sc, mode='alignment')
     assert torch.equal(S_b, S_bs)                                   # same plan, same operand bits
-    monkeypatch.setattr(ops, 'bucket_plan', lambda *a: None)
-    ops._PLAN_CACHE.clear()
+    monkeypatch.setattr(eval_grid, 'bucket_plan', lambda *a: None)
+    eval_grid._PLAN_CACHE.clear()
     S_1 = E.compute_sim_matrix(T(ims), T(captions), ils, cl, mode='alignment')
-    ops._PLAN_CACHE.clear()
+    eval_grid._PLAN_CACHE.clear()
     ref = O.alignment_scores(ims, captions, ils, cl, dtype=np.float64)
     if eval_precision == 'split':
         np.testing.assert_allclose(S_b.cpu().numpy(), S_1.cpu().numpy(), rtol=0, atol=2e-6)
@@ -822,6 +822,66 @@ def test_length_bucketed_grid_equals_the_single_launch(eval_precision, monkeypat
     else:
         assert_scores_close(S_b.cpu().numpy(), S_1.cpu().numpy(), rtol=1e-6, atol_rel=1e-6)      # same operands: summation order only
         assert_scores_close(S_b.cpu().numpy(), ref)
+
+
+@pytest.mark.parametrize('aggregation', ['MwSr', 'symm'])
+def test_length_bucketed_grid_in_the_swapped_orientation(eval_precision, monkeypatch, aggregation):
+    """'MwSr' puts the captions on the max side (tail 2) and the images on the sum side (tail 0), 'symm' adds both orientations:
+    the same 90 x 450 ragged grid as above, bucketed against the oracle, and bucketed + chunked bit-equal to bucketed."""
+    from aladin_amd import eval_grid, ops, synth
+    images, captions, il, cl = synth.eval_sets(90, 128, seed=77, img_len_range=(6, 70), cap_len_range=(5, 66), n_full=4)
+    ims, ils = T(images[0::5]), il[0::5]
+    monkeypatch.setattr(eval_grid, 'BUCKET_MIN_PAIRS', 1)
+    monkeypatch.setattr(eval_grid, 'BUCKET_MIN_SAMPLES', 8)
+    eval_grid._PLAN_CACHE.clear()
+    plan = eval_grid.bucket_plan([eval_grid.positions(v - 3, 68, True) for v in cl], [eval_grid.positions(v - 1, 70, False) for v in ils])
+    assert plan is not None and len(plan[0]) >= 3 and len(plan[1]) >= 3
+    S_b = ops.alignment_scores(ims, T(captions), ils, cl, aggregation)
+    ref = O.alignment_scores(images[0::5], captions, ils, cl, aggregation=aggregation, dtype=np.float64)
+    if eval_precision == 'split':
+        np.testing.assert_allclose(S_b.cpu().numpy(), ref, rtol=2e-6, atol=3e-6)
+    else:
+        assert_scores_close(S_b.cpu().numpy(), ref)
+    launches, score = [], ops.scores_from_packed
+
+    def counting(*a, **kw):
+        launches.append(1)
+        return score(*a, **kw)
+    monkeypatch.setattr(ops, 'scores_from_packed', counting)
+    S_b2 = ops.alignment_scores(ims, T(captions), ils, cl, aggregation)
+    n_blocks = len(launches)
+    monkeypatch.setattr(eval_grid, 'E_SCRATCH_LIMIT', 1 << 18)
+    S_c = ops.alignment_scores(ims, T(captions), ils, cl, aggregation)
+    assert len(launches) - n_blocks > n_blocks                      # some block was chunked
+    assert torch.equal(S_b2, S_b) and torch.equal(S_c, S_b)
+    eval_grid._PLAN_CACHE.clear()
+
+
+def test_long_evaluation_grid_is_one_launch(eval_precision, monkeypatch):
+    """A grid whose trimmed sets are past the tile classes is never bucketed: one launch of the long-set kernels, the bits of
+    ops._align_forward on the same trimmed sets."""
+    from aladin_amd import eval_grid, ops, synth
+    im, s, il, sl = synth.alignment_batch(12, 130, 130, 64, seed=130, ragged=True, Bc=20)
+    il[0], sl[0] = 120, 110                                         # the longest of each side: trimmed to 121 and 110 positions
+    il, sl = [min(v, 120) for v in il], [min(v, 110) for v in sl]
+    monkeypatch.setattr(eval_grid, 'BUCKET_MIN_PAIRS', 1)
+    monkeypatch.setattr(eval_grid, 'BUCKET_MIN_SAMPLES', 2)
+    monkeypatch.setattr(eval_grid, 'BUCKET_MIN_GAIN', 0.0)
+    eval_grid._PLAN_CACHE.clear()
+    assert eval_grid.bucket_plan([eval_grid.positions(v - 1, 129, True) for v in il], [eval_grid.positions(v - 3, 127, False) for v in sl]) is not None
+    launches, score = [], ops.scores_from_packed
+
+    def counting(*a, **kw):
+        launches.append(a[3])
+        return score(*a, **kw)
+    monkeypatch.setattr(ops, 'scores_from_packed', counting)
+    a, b = T(im), T(s)
+    S = ops.alignment_scores(a, b, il, sl)
+    assert len(launches) == 1 and isinstance(launches[0], ops.LongGeom) and (launches[0].R, launches[0].T) == (121, 110)
+    S_ref, _ = ops._align_forward(a[:, :121], b[:, :110], ops.lengths_tensor(il, dev()), ops.lengths_tensor(sl, dev()),
+                                  precision=eval_precision, norms=False)
+    assert torch.equal(S, S_ref)
+    assert eval_grid._PLAN_CACHE == {}                              # the planner was not even asked
 
 
 def _fill_store(sets, lens, tail, precision, batch=4):
@@ -1000,16 +1060,24 @@ def test_packed_store_scores_are_bit_identical_and_smaller():
     ref = E.compute_sim_matrix(images[pick_i], captions[pick_c], [il[k] for k in pick_i], [cl[k] for k in pick_c],
                                mode='alignment')
     assert torch.equal(sub, ref)
-    # caption-side chunking (bounds the side-row scratch on big grids) does not change a single bit
-    from aladin_amd import ops
-    limit = ops.E_SCRATCH_LIMIT
-    ops.E_SCRATCH_LIMIT = 1 << 20
+    # caption-side chunking (bounds the side-row scratch on big grids) does not change a single bit -- and it does happen under
+    # the lowered limit: more than one score launch per grid, from tensors and from stores
+    from aladin_amd import eval_grid, ops
+    limit, score, launches = eval_grid.E_SCRATCH_LIMIT, ops.scores_from_packed, []
+
+    def counting(*a, **kw):
+        launches.append(1)
+        return score(*a, **kw)
+    eval_grid.E_SCRATCH_LIMIT = 1 << 20
+    ops.scores_from_packed = counting
     try:
         assert torch.equal(E.compute_sim_matrix(images[0::5], captions, il[0::5], cl, mode='alignment'), S_dense)
+        n_dense = len(launches)
         assert torch.equal(E.compute_sim_matrix(si.view(slice(0, None, 5)), sc, mode='alignment'), S_dense)
+        assert n_dense > 1 and len(launches) - n_dense > 1, (n_dense, len(launches))
         assert torch.equal(alignment_scores_from_stores(si.view(pick_i), sc.view(pick_c)), ref)
     finally:
-        ops.E_SCRATCH_LIMIT = limit
+        eval_grid.E_SCRATCH_LIMIT, ops.scores_from_packed = limit, score
     # matching head reads the fp32 globals
     M_dense = E.compute_sim_matrix(images[0::5, 0, :], captions[:, 0, :])
     M_store = E.compute_sim_matrix(si.view(slice(0, None, 5)), sc)

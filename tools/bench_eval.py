@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Timing of BASELINE configs[2] (evaluation): 5000 x 25000 x 768 matching-head similarity + ranks,
 and the alignment-head grid 1000 x 5000 at padded length 71.  Prints one JSON line per workload.
-Not the driver's bench (that is bench.py); used for DESIGN.md / profiles.  --matching-only: the first workload alone."""
+Not the driver's bench (that is bench.py); used for DESIGN.md / profiles.  --matching-only: the first workload alone;
+--alignment-only: everything but the first (the rows tools/ab_eval_grid.py compares)."""
 import json
 import os
 import sys
@@ -27,6 +28,13 @@ def timed(fn, iters=10, warm=2):
 
 def main():
     dev = torch.device('cuda:0')
+    if '--alignment-only' not in sys.argv:
+        matching_head(dev)
+    if '--matching-only' not in sys.argv:
+        alignment_head(dev)
+
+
+def matching_head(dev):
     n_img = 5000
     img, cap = synth.retrieval_embeddings(n_img, 768, seed=303, sigma=12.0)
     a = torch.from_numpy(img[0::5]).to(dev)
@@ -43,8 +51,9 @@ def main():
                       'rank_ms': round(ms_rank, 3), 'torch_mm_fp32_ms': round(ms_torch, 3),
                       'fused_sim_plus_rank_ms': round(ms_fused, 3),
                       'sim_tflops_algorithmic': round(flops / ms_sim / 1e9, 1)}))
-    if '--matching-only' in sys.argv:
-        return
+
+
+def alignment_head(dev):
     n = 1000
     images, captions, il, cl = synth.eval_sets(n, 768, seed=9)
     ia = torch.from_numpy(images[0::5]).to(dev)

@@ -6,9 +6,13 @@ builds (an old library built from another checkout against the new one):
     python tools/check_variant.py save new.pt
     python tools/check_variant.py cmp old.pt new.pt
 
-`save FILE retrieval` saves the retrieval group instead (`save FILE all`: both): the stored similarity matrix with its ranks and
+`save FILE retrieval` saves the retrieval group instead (`save FILE all`: every group): the stored similarity matrix with its ranks and
 top-k lists, the fused retrieval (screened and exact=True; its four outputs, not its scheduling-dependent statistics) on clean
 data and on the 'bulk' / 'exact_ties' recipes of tests/test_gpu_parity.py, and the top-k gallery search with its scores.
+`save FILE eval` saves the no-grad evaluation grids: a ragged 90 x 450 grid scored in length classes, and in length classes with
+the sum side chunked, from tensors ('MrSw', 'MwSr', 'symm') and from packed stores, and a 1000 x 5000 grid at the default
+thresholds, all in fp16 and split precision.  Only host code decides these, so the file may be copied into a checkout of
+another commit and run there: the planner's knobs are taken from whichever module has them.
 
 Scores: the bench batch (B = 256, full lengths) and a ragged batch; one small ragged problem per body and epilogue variant of the
 score kernels (SCORE_CASES: the geometry and the grid rule that select the body are asserted), in fp16 and split precision.
@@ -239,6 +243,48 @@ def retrieval_cases(ops, synth, dev):
     return out
 
 
+def eval_cases(ops, synth, dev):
+    """-> {name: scores} of the no-grad evaluation grids."""
+    from aladin_amd import evaluation as E
+    from aladin_amd.store import PackedSetStore
+    try:
+        from aladin_amd import eval_grid as knobs
+    except ImportError:                                    # a checkout from before the grid had a module of its own
+        knobs = ops
+    out = {}
+    T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+
+    def stores(images, captions, il, cl, prec, batch):
+        si, sc = PackedSetStore(images.shape[2], 0, dev, precision=prec), PackedSetStore(images.shape[2], 2, dev, precision=prec)
+        for k0 in range(0, images.shape[0], batch):
+            k1 = min(images.shape[0], k0 + batch)
+            si.append(T(images[k0:k1, :max(il[k0:k1])]), il[k0:k1])
+            sc.append(T(captions[k0:k1, :max(cl[k0:k1])]), cl[k0:k1])
+        return si.view(slice(0, None, 5)), sc
+
+    def grids(tag, images, captions, il, cl, aggregations, batch):
+        ims, caps, ils = T(images[0::5]), T(captions), il[0::5]
+        for prec in ('fp16', 'split'):
+            vi, sc = stores(images, captions, il, cl, prec, batch)
+            knobs._PLAN_CACHE.clear()
+            with torch.no_grad():
+                for agg in aggregations:
+                    out['%s-%s-%s' % (tag, agg, prec)] = ops.alignment_scores(ims, caps, ils, cl, agg, precision=prec).cpu()
+                out['%s-stores-%s' % (tag, prec)] = E.compute_sim_matrix(vi, sc, mode='alignment').cpu()
+    saved = knobs.BUCKET_MIN_PAIRS, knobs.BUCKET_MIN_SAMPLES, knobs.E_SCRATCH_LIMIT
+    try:
+        small = synth.eval_sets(90, 128, seed=77, img_len_range=(6, 70), cap_len_range=(5, 66), n_full=4)
+        knobs.BUCKET_MIN_PAIRS, knobs.BUCKET_MIN_SAMPLES = 1, 8
+        grids('eval90x450-bucketed', *small, ('MrSw', 'MwSr', 'symm'), 53)
+        knobs.E_SCRATCH_LIMIT = 1 << 18
+        grids('eval90x450-chunked', *small, ('MrSw', 'MwSr', 'symm'), 53)
+    finally:
+        knobs.BUCKET_MIN_PAIRS, knobs.BUCKET_MIN_SAMPLES, knobs.E_SCRATCH_LIMIT = saved
+    grids('eval1000x5000', *synth.eval_sets(1000, 64, seed=9), ('MrSw',), 500)
+    knobs._PLAN_CACHE.clear()
+    return out
+
+
 def main():
     if sys.argv[1] == 'cmp':
         a, b = torch.load(sys.argv[2]), torch.load(sys.argv[3])
@@ -256,7 +302,7 @@ def main():
     dev = torch.device('cuda:0')
     out = {}
     group = sys.argv[3] if len(sys.argv) > 3 else 'alignment'
-    assert group in ('alignment', 'retrieval', 'all'), group
+    assert group in ('alignment', 'retrieval', 'eval', 'all'), group
     if group in ('alignment', 'all'):
         for tag, ragged, seed in (('full', False, 1234), ('ragged', True, 99)):
             im, s, il, sl = synth.alignment_batch(256, 34, 50, 768, seed=seed, ragged=ragged)
@@ -267,6 +313,8 @@ def main():
         out.update(gradient_cases(ops, synth, dev))
     if group in ('retrieval', 'all'):
         out.update(retrieval_cases(ops, synth, dev))
+    if group in ('eval', 'all'):
+        out.update(eval_cases(ops, synth, dev))
     torch.save(out, sys.argv[2])
     print('saved', sys.argv[2], {k: float(v.double().sum()) for k, v in out.items()})
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where the time of the COCO-1k alignment grid goes: wall time per call, host profile (cProfile), GPU time (events).
   --img-range LO HI    image lengths (default 12 34, the bench fixture; 18 51 = images of up to 50 boxes + the global slot)
-  --x-bounds a,b,...   override ops.X_CLASS_BOUNDS (A/B of the planner's image classes)
+  --x-bounds a,b,...   override eval_grid.X_CLASS_BOUNDS (A/B of the planner's image classes)
   --no-host-profile"""
 import argparse
 import cProfile
@@ -13,7 +13,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from aladin_amd import evaluation as E, ops, synth
+from aladin_amd import eval_grid, evaluation as E, ops, synth
 
 
 def main():
@@ -23,21 +23,21 @@ def main():
     ap.add_argument('--no-host-profile', action='store_true')
     a = ap.parse_args()
     if a.x_bounds:
-        ops.X_CLASS_BOUNDS = tuple(int(v) for v in a.x_bounds.split(','))
+        eval_grid.X_CLASS_BOUNDS = tuple(int(v) for v in a.x_bounds.split(','))
     dev = torch.device('cuda:0')
     n = 1000
     images, captions, il, cl = synth.eval_sets(n, 768, seed=9, img_len_range=tuple(a.img_range))
-    print('image lengths %d..%d, X_CLASS_BOUNDS %s' % (min(il), max(il), ops.X_CLASS_BOUNDS), flush=True)
+    print('image lengths %d..%d, X_CLASS_BOUNDS %s' % (min(il), max(il), eval_grid.X_CLASS_BOUNDS), flush=True)
     ia = torch.from_numpy(images[0::5]).to(dev)
     ca = torch.from_numpy(captions).to(dev)
     ilen = il[0::5]
     for prec in ('fp16', 'split'):
         ops.set_eval_precision(prec)
         for bucket in (True, False):
-            saved = ops.bucket_plan
+            saved = eval_grid.bucket_plan
             if not bucket:
-                ops.bucket_plan = lambda *a: None
-            ops._PLAN_CACHE.clear()
+                eval_grid.bucket_plan = lambda *a: None
+            eval_grid._PLAN_CACHE.clear()
             fn = lambda: E.compute_sim_matrix(ia, ca, ilen, cl, mode='alignment')
             for _ in range(3):
                 fn()
@@ -61,8 +61,8 @@ def main():
                 torch.cuda.synchronize()
                 pr.disable()
                 pstats.Stats(pr).sort_stats('tottime').print_stats(14)
-            ops.bucket_plan = saved
-            ops._PLAN_CACHE.clear()
+            eval_grid.bucket_plan = saved
+            eval_grid._PLAN_CACHE.clear()
 
 
 if __name__ == '__main__':
