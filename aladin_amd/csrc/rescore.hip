@@ -22,6 +22,9 @@
 // tiles, the 4 registers and the 4 lane groups (exact, any order), starts from 0 for an image shorter than the padded set (the
 // zero fill of alad/loss.py:116,124) and from -inf for one that fills it; the sum over words is row16_sum per tile, tiles added
 // in ascending order.  One lane writes the pair's score once: no atomics, and nothing depends on the slot, the chunk, k or n_q.
+//
+// aladin_align_pair_map is the kernel's second instance (rescore_kernel<true>): the same main loop, and an epilogue that keeps
+// the arg-max the score throws away -- per word the best region, per region the best word (rescore_map_epilogue).
 #include "../../include/aladin_hip.h"
 
 #include "sim_common.hpp"
@@ -62,8 +65,123 @@ __device__ __forceinline__ void rescore_stage(const half_t* __restrict__ panel, 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// aladin_align_pair_map: the alignment behind a pair's score.  The same accumulation (the body of rescore_kernel below), then
+// per word the best region and per region the best word, (value, index) carried through the reductions rescore_kernel runs on the value
+// alone, combined by ALADIN_ARGMAX_STEP: greater value, or equal value and lower index -- commutative and associative, so the
+// order of a reduction does not matter.  The zero fill of a side shorter than its padded set takes part as (0.0, RESCORE_FILL),
+// the largest index, so a real position wins a tie with it; it is written as -1 / 0.0.  Every output entry is written once,
+// by one lane; no atomics; a pair's bits depend on the pair alone.
+// ------------------------------------------------------------------------------------------------
+constexpr int RESCORE_FILL = 0x7fffffff;
+
+struct RescoreMapOut {
+  float* score;            // (n_q x k), or nullptr
+  int32_t* word_region;    // (n_q x k x word_ld) and its cosines, or both nullptr
+  float* word_cos;
+  int32_t* region_word;    // (n_q x k x region_ld) and its cosines, or both nullptr
+  float* region_cos;
+  int word_ld, region_ld;
+  int y_full;              // the count at which a caption fills its padded set
+};
+
+__device__ __forceinline__ void rescore_map_epilogue(const f32x4 (&acc)[RESCORE_TILES][RESCORE_TILES], int q, int slot, int k, bool live,
+                                                     int cnt_x, int cnt_y, int nrt, int nct, int x_full, int split, int lane,
+                                                     const RescoreMapOut& o) {
+  if (slot >= k) return;
+  const int64_t pair = (int64_t)q * k + slot;
+  const int row0 = 4 * (lane >> 4), col0 = lane & 15;
+  const float unscale = split ? RESCORE_SPLIT_UNSCALE : 1.0f;                    // exact: a power of two
+  int32_t* const w_idx = o.word_region ? o.word_region + pair * o.word_ld : nullptr;
+  float* const w_cos = o.word_region ? o.word_cos + pair * o.word_ld : nullptr;
+  int32_t* const r_idx = o.region_word ? o.region_word + pair * o.region_ld : nullptr;
+  float* const r_cos = o.region_word ? o.region_cos + pair * o.region_ld : nullptr;
+
+  // entries from the sample's count (0 where there is no candidate) up to the row stride: -1 / 0.0
+  if (w_idx)
+    for (int w = (live ? cnt_y : 0) + lane; w < o.word_ld; w += 64) { w_idx[w] = -1; w_cos[w] = 0.0f; }
+  if (r_idx)
+    for (int r = (live ? cnt_x : 0) + lane; r < o.region_ld; r += 64) { r_idx[r] = -1; r_cos[r] = 0.0f; }
+  if (!live) {
+    if (o.score && lane == 0) o.score[pair] = -INFINITY;
+    return;
+  }
+
+  // word -> region, and the pair's score from the per-word maxima exactly as rescore_kernel sums them
+  if (w_idx || o.score) {
+    float total = 0.0f;
+    const float floor_ = cnt_x < x_full ? 0.0f : -INFINITY;                    // the zero fill of an image shorter than the padded set
+#pragma unroll
+    for (int ct = 0; ct < RESCORE_TILES; ++ct) {
+      if (ct >= nct) continue;
+      float v = floor_;
+      int idx = RESCORE_FILL;
+#pragma unroll
+      for (int rt = 0; rt < RESCORE_TILES; ++rt) {
+        if (rt >= nrt) continue;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const int row = rt * 16 + row0 + reg;
+          const bool in = row < cnt_x;                                         // selected, never multiplied
+          ALADIN_ARGMAX_STEP(in ? acc[rt][ct][reg] : -INFINITY, in ? row : RESCORE_FILL);
+        }
+      }
+      ALADIN_ARGMAX_STEP(lane_xor16(v), lane_xor16(idx));
+      ALADIN_ARGMAX_STEP(lane_xor32(v), lane_xor32(idx));
+      const int w = ct * 16 + col0;
+      total += row16_sum(w < cnt_y ? v : 0.0f);
+      if (w_idx && lane < 16 && w < cnt_y) {
+        w_idx[w] = idx == RESCORE_FILL ? -1 : idx;
+        w_cos[w] = v * unscale;
+      }
+    }
+    if (split) total *= RESCORE_SPLIT_UNSCALE;
+    if (o.score && lane == 0) o.score[pair] = total;
+  }
+
+  // region -> word, one row tile at a time: in-lane over the word tiles, then the 16 lanes of the row (row_ror 8, 4, 2, 1)
+  if (r_idx) {
+    const float floor_ = cnt_y < o.y_full ? 0.0f : -INFINITY;                    // ... of a caption shorter than the padded set
+#pragma unroll
+    for (int rt = 0; rt < RESCORE_TILES; ++rt) {
+      if (rt >= nrt) continue;
+      float bv = 0.0f;
+      int bi = -1;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        float v = floor_;
+        int idx = RESCORE_FILL;
+#pragma unroll
+        for (int ct = 0; ct < RESCORE_TILES; ++ct) {
+          if (ct >= nct) continue;
+          const int w = ct * 16 + col0;
+          const bool in = w < cnt_y;
+          ALADIN_ARGMAX_STEP(in ? acc[rt][ct][reg] : -INFINITY, in ? w : RESCORE_FILL);
+        }
+        ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 8), __builtin_amdgcn_update_dpp(0, idx, 0x128, 0xF, 0xF, false));
+        ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 4), __builtin_amdgcn_update_dpp(0, idx, 0x124, 0xF, 0xF, false));
+        ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 2), __builtin_amdgcn_update_dpp(0, idx, 0x122, 0xF, 0xF, false));
+        ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 1), __builtin_amdgcn_update_dpp(0, idx, 0x121, 0xF, 0xF, false));
+        if (col0 == reg) { bv = v; bi = idx; }                                 // every lane of the row holds the result: lane `reg` keeps it
+      }
+      const int r = rt * 16 + row0 + col0;                                     // lanes 0..3 of each row: 16 consecutive regions a tile
+      if (col0 < 4 && r < cnt_x) {
+        r_idx[r] = bi == RESCORE_FILL ? -1 : bi;
+        r_cos[r] = bv * unscale;
+      }
+    }
+  }
+}
+
+// rescore_kernel<false> writes the pair's score (aladin_align_rescore), rescore_kernel<true> the alignment behind it
+// (aladin_align_pair_map): one body -- side selection, the double-buffered LDS-DMA loop, the accumulation -- and the instance's
+// epilogue.  acc[rt][ct][reg] = <region rt * 16 + 4 * (lane >> 4) + reg, word ct * 16 + (lane & 15)>, scaled by 2^28 for split rows.
+template <bool MAP> struct RescoreOut { typedef float* __restrict__ type; };
+template <> struct RescoreOut<true> { typedef RescoreMapOut type; };
+
+template <bool MAP>
 __global__ __launch_bounds__(512) void rescore_kernel(RescoreSide x, RescoreSide y, const int32_t* __restrict__ cand, int k, int dim,
-                                                      int x_full, int64_t ldk, int kps, int split, float* __restrict__ out) {
+                                                      int x_full, int64_t ldk, int kps, int split, typename RescoreOut<MAP>::type out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -135,33 +253,37 @@ __global__ __launch_bounds__(512) void rescore_kernel(RescoreSide x, RescoreSide
     }
   }
 
-  if (slot >= k) return;
-  float total = -INFINITY;
-  if (live) {
-    total = 0.0f;
-    const float floor_ = cnt_x < x_full ? 0.0f : -INFINITY;                    // the zero fill of an image shorter than the padded set
-    const int row0 = 4 * (lane >> 4);
-#pragma unroll
-    for (int ct = 0; ct < RESCORE_TILES; ++ct) {
-      if (ct >= nct) continue;
-      float m = floor_;
-#pragma unroll
-      for (int rt = 0; rt < RESCORE_TILES; ++rt) {
-        if (rt >= nrt) continue;
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const float v = rt * 16 + row0 + reg < cnt_x ? acc[rt][ct][reg] : -INFINITY;      // selected, never multiplied
-          m = fmax_nc(m, v);
+  if constexpr (MAP) {
+    rescore_map_epilogue(acc, q, slot, k, live, cnt_x, cnt_y, nrt, nct, x_full, split, lane, out);
+  } else {
+    if (slot >= k) return;
+    float total = -INFINITY;
+    if (live) {
+      total = 0.0f;
+      const float floor_ = cnt_x < x_full ? 0.0f : -INFINITY;                    // the zero fill of an image shorter than the padded set
+      const int row0 = 4 * (lane >> 4);
+  #pragma unroll
+      for (int ct = 0; ct < RESCORE_TILES; ++ct) {
+        if (ct >= nct) continue;
+        float m = floor_;
+  #pragma unroll
+        for (int rt = 0; rt < RESCORE_TILES; ++rt) {
+          if (rt >= nrt) continue;
+  #pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            const float v = rt * 16 + row0 + reg < cnt_x ? acc[rt][ct][reg] : -INFINITY;      // selected, never multiplied
+            m = fmax_nc(m, v);
+          }
         }
+        m = fmax_nc(m, lane_xor16(m));
+        m = fmax_nc(m, lane_xor32(m));
+        const float wv = ct * 16 + (lane & 15) < cnt_y ? m : 0.0f;
+        total += row16_sum(wv);
       }
-      m = fmax_nc(m, lane_xor16(m));
-      m = fmax_nc(m, lane_xor32(m));
-      const float wv = ct * 16 + (lane & 15) < cnt_y ? m : 0.0f;
-      total += row16_sum(wv);
+      if (split) total *= RESCORE_SPLIT_UNSCALE;                                 // exact: a power of two
     }
-    if (split) total *= RESCORE_SPLIT_UNSCALE;                                 // exact: a power of two
+    if (lane == 0) out[(int64_t)q * k + slot] = total;
   }
-  if (lane == 0) out[(int64_t)q * k + slot] = total;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -202,56 +324,106 @@ static int rescore_waves(int sh_rows, int ga_rows) {
   return 0;
 }
 
-extern "C" int aladin_align_rescore(const void* x_rows, const int64_t* x_offsets, const int32_t* x_counts, const int32_t* x_ids, int n_x,
-                                    int x_max_count, const void* y_rows, const int64_t* y_offsets, const int32_t* y_counts,
-                                    const int32_t* y_ids, int n_y, int y_max_count, int D, int precision, int dim, int x_full,
-                                    const int32_t* cand, int k, float* out, void* stream) {
-  if (!x_rows || !x_offsets || !x_counts || !y_rows || !y_offsets || !y_counts || !cand || !out || n_x < 1 || n_y < 1 || D < 1 ||
+// The checks and the launch geometry aladin_align_rescore and aladin_align_pair_map share; `who` names the caller in messages.
+struct RescorePlan {
+  RescoreSide x, y;
+  int width, kps, split, nw, lds_bytes;
+  unsigned blocks;
+};
+
+static int rescore_plan(const char* who, const void* x_rows, const int64_t* x_offsets, const int32_t* x_counts, const int32_t* x_ids, int n_x,
+                        int x_max_count, const void* y_rows, const int64_t* y_offsets, const int32_t* y_counts, const int32_t* y_ids, int n_y,
+                        int y_max_count, int D, int precision, int dim, int x_full, const int32_t* cand, int k, bool outputs_ok,
+                        RescorePlan* p) {
+  if (!x_rows || !x_offsets || !x_counts || !y_rows || !y_offsets || !y_counts || !cand || !outputs_ok || n_x < 1 || n_y < 1 || D < 1 ||
       (dim != 0 && dim != 1) || (precision != ALADIN_PRECISION_FP16 && precision != ALADIN_PRECISION_SPLIT) || x_full < 1 ||
       x_max_count < 0 || y_max_count < 0) {
-    aladin_set_error("align_rescore: bad argument (n_x=%d n_y=%d D=%d precision=%d dim=%d x_full=%d; null table or output, dim 0 or 1)", n_x,
+    aladin_set_error("%s: bad argument (n_x=%d n_y=%d D=%d precision=%d dim=%d x_full=%d; null table or output, dim 0 or 1)", who, n_x,
                      n_y, D, precision, dim, x_full);
     return ALADIN_ERR_ARG;
   }
   if (k < 1 || k > RESCORE_MAX_K) {
-    aladin_set_error("align_rescore: 1 <= k <= %d candidates per query, got %d", RESCORE_MAX_K, k);
+    aladin_set_error("%s: 1 <= k <= %d candidates per query, got %d", who, RESCORE_MAX_K, k);
     return ALADIN_ERR_UNSUPPORTED;
   }
   if (x_max_count > RESCORE_MAX_COUNT || y_max_count > RESCORE_MAX_COUNT) {
-    aladin_set_error("align_rescore: at most %d scored positions per set, got %d regions / %d words", RESCORE_MAX_COUNT, x_max_count,
+    aladin_set_error("%s: at most %d scored positions per set, got %d regions / %d words", who, RESCORE_MAX_COUNT, x_max_count,
                      y_max_count);
     return ALADIN_ERR_UNSUPPORTED;
   }
-  const int width = aladin_store_row_width(D, precision);
-  if (width < D) {
-    aladin_set_error("align_rescore: feature size %d is not one a store holds", D);
+  p->width = aladin_store_row_width(D, precision);
+  if (p->width < D) {
+    aladin_set_error("%s: feature size %d is not one a store holds", who, D);
     return ALADIN_ERR_UNSUPPORTED;
   }
-  const int split = precision == ALADIN_PRECISION_SPLIT;
-  const int Dp = split ? width / 2 : width;
+  p->split = precision == ALADIN_PRECISION_SPLIT;
+  const int Dp = p->split ? p->width / 2 : p->width;
   if (Dp % 64) {
-    aladin_set_error("align_rescore: store rows of %d halfs are not whole 64-deep K steps", Dp);
+    aladin_set_error("%s: store rows of %d halfs are not whole 64-deep K steps", who, Dp);
     return ALADIN_ERR_UNSUPPORTED;
   }
-  RescoreSide x{(const half_t*)x_rows, x_offsets, x_counts, x_ids, n_x, x_max_count, round_up(x_max_count > 0 ? x_max_count : 1, 16)};
-  RescoreSide y{(const half_t*)y_rows, y_offsets, y_counts, y_ids, n_y, y_max_count, round_up(y_max_count > 0 ? y_max_count : 1, 16)};
-  const int sh_rows = dim == 1 ? x.prows : y.prows, ga_rows = dim == 1 ? y.prows : x.prows;
-  const int nw = rescore_waves(sh_rows, ga_rows);
-  if (!nw) {
-    aladin_set_error("align_rescore: no chunk of %d + n x %d rows fits the LDS", sh_rows, ga_rows);
+  p->kps = Dp / 64;
+  p->x = RescoreSide{(const half_t*)x_rows, x_offsets, x_counts, x_ids, n_x, x_max_count, round_up(x_max_count > 0 ? x_max_count : 1, 16)};
+  p->y = RescoreSide{(const half_t*)y_rows, y_offsets, y_counts, y_ids, n_y, y_max_count, round_up(y_max_count > 0 ? y_max_count : 1, 16)};
+  const int sh_rows = dim == 1 ? p->x.prows : p->y.prows, ga_rows = dim == 1 ? p->y.prows : p->x.prows;
+  p->nw = rescore_waves(sh_rows, ga_rows);
+  if (!p->nw) {
+    aladin_set_error("%s: no chunk of %d + n x %d rows fits the LDS", who, sh_rows, ga_rows);
     return ALADIN_ERR_UNSUPPORTED;
   }
-  static unsigned long long lds_reserved = 0;
-  if (int rc = aladin_reserve_lds((const void*)rescore_kernel, RESCORE_LDS_LIMIT, &lds_reserved, "rescore_kernel")) return rc;
+  p->lds_bytes = 2 * (sh_rows + p->nw * ga_rows) * 128;
   const int n_q = dim == 1 ? n_x : n_y;
-  const int64_t blocks = (int64_t)n_q * cdiv(k, nw);
+  const int64_t blocks = (int64_t)n_q * cdiv(k, p->nw);
   if (blocks > 0x7fffffff) {
-    aladin_set_error("align_rescore: %d queries x %d candidates are more workgroups than one launch takes", n_q, k);
+    aladin_set_error("%s: %d queries x %d candidates are more workgroups than one launch takes", who, n_q, k);
     return ALADIN_ERR_UNSUPPORTED;
   }
-  hipLaunchKernelGGL(rescore_kernel, dim3((unsigned)blocks), dim3(nw * 64), 2 * (sh_rows + nw * ga_rows) * 128, (hipStream_t)stream, x, y,
-                     cand, k, dim, x_full, (int64_t)width, Dp / 64, split, out);
+  p->blocks = (unsigned)blocks;
+  return ALADIN_OK;
+}
+
+extern "C" int aladin_align_rescore(const void* x_rows, const int64_t* x_offsets, const int32_t* x_counts, const int32_t* x_ids, int n_x,
+                                    int x_max_count, const void* y_rows, const int64_t* y_offsets, const int32_t* y_counts,
+                                    const int32_t* y_ids, int n_y, int y_max_count, int D, int precision, int dim, int x_full,
+                                    const int32_t* cand, int k, float* out, void* stream) {
+  RescorePlan p;
+  if (int rc = rescore_plan("align_rescore", x_rows, x_offsets, x_counts, x_ids, n_x, x_max_count, y_rows, y_offsets, y_counts, y_ids, n_y,
+                            y_max_count, D, precision, dim, x_full, cand, k, out != nullptr, &p))
+    return rc;
+  static unsigned long long lds_reserved = 0;
+  if (int rc = aladin_reserve_lds((const void*)rescore_kernel<false>, RESCORE_LDS_LIMIT, &lds_reserved, "rescore_kernel")) return rc;
+  hipLaunchKernelGGL(rescore_kernel<false>, dim3(p.blocks), dim3(p.nw * 64), p.lds_bytes, (hipStream_t)stream, p.x, p.y, cand, k, dim, x_full,
+                     (int64_t)p.width, p.kps, p.split, out);
   return aladin_check_launch("rescore_kernel");
+}
+
+extern "C" int aladin_align_pair_map(const void* x_rows, const int64_t* x_offsets, const int32_t* x_counts, const int32_t* x_ids, int n_x,
+                                     int x_max_count, const void* y_rows, const int64_t* y_offsets, const int32_t* y_counts,
+                                     const int32_t* y_ids, int n_y, int y_max_count, int D, int precision, int dim, int x_full, int y_full,
+                                     const int32_t* cand, int k, float* out_score, int32_t* word_region, float* word_cos, int64_t word_ld,
+                                     int32_t* region_word, float* region_cos, int64_t region_ld, void* stream) {
+  const bool words = word_region || word_cos, regions = region_word || region_cos;
+  if ((!out_score && !words && !regions) || !word_region != !word_cos || !region_word != !region_cos) {
+    aladin_set_error("align_pair_map: no output, or one of an (index, cosine) pair of outputs without the other");
+    return ALADIN_ERR_ARG;
+  }
+  if (y_full < 1 || (words && (word_ld < y_max_count || word_ld > 0x7fffffff)) ||
+      (regions && (region_ld < x_max_count || region_ld > 0x7fffffff))) {
+    aladin_set_error("align_pair_map: bad argument (y_full=%d word_ld=%lld for %d words, region_ld=%lld for %d regions)", y_full,
+                     (long long)word_ld, y_max_count, (long long)region_ld, x_max_count);
+    return ALADIN_ERR_ARG;
+  }
+  RescorePlan p;
+  if (int rc = rescore_plan("align_pair_map", x_rows, x_offsets, x_counts, x_ids, n_x, x_max_count, y_rows, y_offsets, y_counts, y_ids, n_y,
+                            y_max_count, D, precision, dim, x_full, cand, k, true, &p))
+    return rc;
+  static unsigned long long lds_reserved = 0;
+  if (int rc = aladin_reserve_lds((const void*)rescore_kernel<true>, RESCORE_LDS_LIMIT, &lds_reserved, "rescore_kernel<true>")) return rc;
+  const RescoreMapOut o{out_score, word_region, word_cos, region_word, region_cos, words ? (int)word_ld : 0, regions ? (int)region_ld : 0,
+                        y_full};
+  hipLaunchKernelGGL(rescore_kernel<true>, dim3(p.blocks), dim3(p.nw * 64), p.lds_bytes, (hipStream_t)stream, p.x, p.y, cand, k, dim,
+                     x_full, (int64_t)p.width, p.kps, p.split, o);
+  return aladin_check_launch("rescore_kernel<true>");
 }
 
 extern "C" int aladin_rerank_order(const int32_t* cand, const float* scores, int n_q, int k, int32_t* out_idx, float* out_val,

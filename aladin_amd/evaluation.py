@@ -218,6 +218,20 @@ def search_rerank(images, captions, k=50, direction='i2t', shortlist=None):
         return ops.rerank_order(shortlist, scores)
 
 
+def search_explain(images, captions, k=50, direction='i2t', shortlist=None, top=5):
+    """search_rerank plus the alignment behind its best results: (indices, scores, PairAlignment).  indices / scores are exactly
+    search_rerank(images, captions, k, direction, shortlist)'s; the PairAlignment (store.alignment_map_for_pairs) covers every
+    query's first min(top, k) re-ranked candidates -- for each word the region that carried its max and the cosine, for each
+    region its best word; -1 slots of a short shortlist stay -1 / -inf there."""
+    top = int(top)
+    if top < 1:
+        raise ValueError('search_explain: top must be >= 1 (got %d)' % top)
+    idx, val = search_rerank(images, captions, k, direction, shortlist)
+    from .store import alignment_map_for_pairs
+    with torch.no_grad():
+        return idx, val, alignment_map_for_pairs(images, captions, idx[:, :min(top, idx.shape[1])].contiguous(), direction)
+
+
 def _metrics(ranks):
     ranks = np.asarray(ranks, dtype=np.float64)
     r1 = 100.0 * len(np.where(ranks < 1)[0]) / len(ranks)

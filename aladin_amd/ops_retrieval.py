@@ -173,6 +173,45 @@ def align_rescore(x, y, cand, dim, D, precision, x_full, out=None):
     return out
 
 
+def align_pair_map(x, y, cand, dim, D, precision, x_full, y_full, words=True, regions=True, out=None):
+    """The alignment behind align_rescore's scores: (score, word_region, word_cos, region_word, region_cos) of the listed pairs.
+    x, y, cand, dim, D, precision, x_full: as align_rescore takes them; y_full: the count at which a caption fills its padded set.
+    score (n_q, k) float32: align_rescore's bits.  word_region int32 / word_cos float32, (n_q, k, y[5]): per word the best region
+    (position among the image's scored rows) and its cosine; region_word / region_cos, (n_q, k, x[5]): per region the best word.
+    Ties -> the lowest index; -1 / 0.0 where the zero fill of a shorter-than-padded side wins, past a sample's count and at -1
+    slots (score -inf).  words=False / regions=False: that pair of outputs is None and is not computed.
+    out: a preallocated 5-tuple of contiguous results (None where not requested; graph capture)."""
+    if dim not in (0, 1):
+        raise ValueError('aladin_amd: align_pair_map takes dim 0 or 1')
+    n_q = x[4] if dim == 1 else y[4]
+    _check_shortlist(cand, n_q)
+    if x[5] > RESCORE_MAX_COUNT or y[5] > RESCORE_MAX_COUNT:
+        raise ValueError('aladin_amd: align_pair_map maps sets of at most %d positions (got %d regions, %d words)'
+                         % (RESCORE_MAX_COUNT, x[5], y[5]))
+    if int(x_full) < 1 or int(y_full) < 1:
+        raise ValueError('aladin_amd: align_pair_map needs x_full >= 1 and y_full >= 1 (got %d, %d)' % (x_full, y_full))
+    if not cand.is_cuda:
+        raise RuntimeError('aladin_amd: the shortlist must live on the GPU (no CPU fallback exists)')
+    cand = cand.contiguous()
+    n_q, k = cand.shape
+    shapes = [((n_q, k), torch.float32), ((n_q, k, int(y[5])), torch.int32), ((n_q, k, int(y[5])), torch.float32),
+              ((n_q, k, int(x[5])), torch.int32), ((n_q, k, int(x[5])), torch.float32)]
+    wanted = [True, words, words, regions, regions]
+    if out is None:
+        out = tuple(torch.empty(sh, dtype=dt, device=cand.device) if w else None for (sh, dt), w in zip(shapes, wanted))
+    elif len(out) != 5 or any((o is None) == w or (w and (tuple(o.shape) != sh or o.dtype != dt or not o.is_contiguous()))
+                              for o, (sh, dt), w in zip(out, shapes, wanted)):
+        raise ValueError('aladin_amd: align_pair_map needs contiguous (score, word_region, word_cos, region_word, region_cos) outputs of '
+                         'the shortlist\'s shape x the views\' largest counts, None where not requested')
+    from .ops import _precision_code
+    _lib.check(_lib.load().aladin_align_pair_map(_ptr(x[0]), _ptr(x[1]), _ptr(x[2]), _ptr(x[3]), int(x[4]), int(x[5]),
+                                                 _ptr(y[0]), _ptr(y[1]), _ptr(y[2]), _ptr(y[3]), int(y[4]), int(y[5]),
+                                                 int(D), _precision_code(precision), int(dim), int(x_full), int(y_full), _ptr(cand), k,
+                                                 _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), int(y[5]), _ptr(out[3]), _ptr(out[4]),
+                                                 int(x[5]), _stream()), 'align_pair_map')
+    return tuple(out)
+
+
 def rerank_order(cand, scores, out_idx=None, out_val=None):
     """(indices, scores): every row of the shortlist `cand` and of its scores in descending score order -- a stable sort, ties go
     to the earlier shortlist slot; -1 entries last, as -1 / -inf.  out_idx / out_val: preallocated results (graph capture)."""

@@ -12,6 +12,8 @@ two retrieval heads read and nothing else:
 COCO-5k captions (25 000 x ~12 scored words x 768) take 0.46 GB instead of 5.4 GB; alignment scores
 computed from a store are bit-identical to those computed from the fp32 sets (same fp16 operands).
 """
+import collections
+
 import torch
 
 from . import _lib, eval_grid, ops
@@ -159,15 +161,11 @@ def alignment_scores_from_stores(img, cap):
     return eval_grid.score_grid(eval_grid.StoreSide(img), eval_grid.StoreSide(cap), getattr(img, 'store', img).precision)
 
 
-def alignment_scores_for_pairs(img, cap, cand, direction='i2t'):
-    """(n_q, k) float32 'MrSw' scores of LISTED pairs between two stores / views: direction='i2t' scores image q against the
-    captions cand[q, :], 't2i' caption q against the images cand[q, :].  cand: (n_q, k) int32 device tensor of positions in the
-    gallery view (a search_topk shortlist), -1 = no candidate (-inf in the result).  The rows are read where they lie in the
-    stores (ops.align_rescore): work and memory follow n_q * k, not the grid, and a pair's bits do not depend on where it is
-    listed.  Semantics are those of alignment_scores_from_stores (zero fill for images shorter than the padded set included)."""
+def _pair_sides(img, cap, cand, direction, who):
+    """The checks of every call on LISTED pairs of two stores / views, and the two sides as ops.align_rescore takes them."""
     from .evaluation import _is_packed_store
     if not (_is_packed_store(img) and _is_packed_store(cap)):
-        raise ValueError('aladin_amd: alignment_scores_for_pairs takes two stores / views, not tensors')
+        raise ValueError('aladin_amd: %s takes two stores / views, not tensors' % who)
     if direction not in ('i2t', 't2i'):
         raise ValueError("direction must be 'i2t' or 't2i'")
     _check_pair(img, cap)
@@ -178,4 +176,30 @@ def alignment_scores_for_pairs(img, cap, cand, direction='i2t'):
     oc, cc = sc._tables()
     x = (si.rows, oi, ci, idt_i, len(img), si.max_count(ids_i))
     y = (sc.rows, oc, cc, idt_c, len(cap), sc.max_count(ids_c))
+    return si, sc, x, y
+
+
+def alignment_scores_for_pairs(img, cap, cand, direction='i2t'):
+    """(n_q, k) float32 'MrSw' scores of LISTED pairs between two stores / views: direction='i2t' scores image q against the
+    captions cand[q, :], 't2i' caption q against the images cand[q, :].  cand: (n_q, k) int32 device tensor of positions in the
+    gallery view (a search_topk shortlist), -1 = no candidate (-inf in the result).  The rows are read where they lie in the
+    stores (ops.align_rescore): work and memory follow n_q * k, not the grid, and a pair's bits do not depend on where it is
+    listed.  Semantics are those of alignment_scores_from_stores (zero fill for images shorter than the padded set included)."""
+    si, sc, x, y = _pair_sides(img, cap, cand, direction, 'alignment_scores_for_pairs')
     return ops.align_rescore(x, y, cand, 1 if direction == 'i2t' else 0, si.D, si.precision, si.padded_len - 1 - si.tail)
+
+
+PairAlignment = collections.namedtuple('PairAlignment', 'score word_region word_cos region_word region_cos')
+
+
+def alignment_map_for_pairs(img, cap, cand, direction='i2t', words=True, regions=True):
+    """The alignment behind alignment_scores_for_pairs, for the same LISTED pairs of two stores / views: a PairAlignment of
+    score (n_q, k) float32 -- alignment_scores_for_pairs' bits; word_region int32 / word_cos float32 (n_q, k, max words of the
+    caption view): for every word the region that carried the max over regions, and that cosine; region_word / region_cos
+    (n_q, k, max regions of the image view): for every region the word it matches best.  An index is the position among the
+    sample's scored rows, i.e. position index + 1 of the padded set.  Ties -> the lowest index.  -1 / 0.0: the zero fill of a
+    side shorter than its padded set won (every real cosine < 0), the entry lies past the sample's count, or the slot holds no
+    candidate (score -inf).  words=False / regions=False: that pair of outputs is None (and is not computed)."""
+    si, sc, x, y = _pair_sides(img, cap, cand, direction, 'alignment_map_for_pairs')
+    return PairAlignment(*ops.align_pair_map(x, y, cand, 1 if direction == 'i2t' else 0, si.D, si.precision, si.padded_len - 1 - si.tail,
+                                             sc.padded_len - 1 - sc.tail, words=words, regions=regions))

@@ -504,6 +504,35 @@ ALADIN_API int aladin_align_rescore(const void* x_rows, const int64_t* x_offsets
 ALADIN_API int aladin_rerank_order(const int32_t* cand, const float* scores, int n_q, int k, int32_t* out_idx, float* out_val,
                         void* stream);
 
+/* The alignment behind the score of LISTED pairs (csrc/rescore.hip, the main loop of aladin_align_rescore with another epilogue):
+ * for every word of the caption the region that carried the max over regions and its cosine, for every region of the image the
+ * word it matches best, and the pair's score.
+ *   x_* / y_*, D, precision, dim, x_full, cand, k: exactly as aladin_align_rescore takes them.
+ *   y_full: the count at which a caption fills the padded set (the caption store's padded_len - 1 - tail).
+ *   out_score (n_q x k fp32): the bits aladin_align_rescore writes for the same pair.
+ *   word_region (int32) / word_cos (fp32), n_q x k x word_ld, word_ld >= y_max_count: entry w of pair (q, s) = the region with
+ *   the largest cosine to word w, and that cosine.
+ *   region_word (int32) / region_cos (fp32), n_q x k x region_ld, region_ld >= x_max_count: entry r = the word with the largest
+ *   cosine to region r, and that cosine.
+ *   out_score may be NULL; word_region and word_cos may be NULL together, region_word and region_cos may be NULL together;
+ *   ALADIN_ERR_ARG if nothing is asked for or if one output of a pair is NULL without the other.
+ * Index convention: an index is the position among the sample's SCORED rows (0 .. count - 1), i.e. position idx + 1 of the
+ * padded set (slot 0 is the global embedding).
+ * Tie rule: equal cosines -> the lowest index, in both directions.
+ * Fill rule: a side with fewer positions than its padded set (x_full / y_full) competes with the zero fill of
+ * alad/loss.py:116,124: where every real cosine is < 0 the entry is -1 / 0.0f; a real position wins a tie with the fill (a
+ * cosine of exactly 0 keeps its index).  A side that fills its set keeps its negative maximum and a real index.
+ * Entries from the sample's count up to word_ld / region_ld are -1 / 0.0f; a slot without a candidate gets score -inf and all
+ * entries -1 / 0.0f; a caption without scored words gives score 0.0f, every region -1 / 0.0f.  Cosines of split stores are
+ * the accumulator times 2^-28 (exact).  Each entry is written once; a pair's bits depend on the pair alone.
+ * Limits and their checks are those of aladin_align_rescore (1 <= k <= 256, counts <= 96, D, LDS; ALADIN_ERR_UNSUPPORTED, before
+ * any launch).  No allocation, no synchronisation, no atomics: graph-capturable. */
+ALADIN_API int aladin_align_pair_map(const void* x_rows, const int64_t* x_offsets, const int32_t* x_counts, const int32_t* x_ids, int n_x,
+                          int x_max_count, const void* y_rows, const int64_t* y_offsets, const int32_t* y_counts,
+                          const int32_t* y_ids, int n_y, int y_max_count, int D, int precision, int dim, int x_full, int y_full,
+                          const int32_t* cand, int k, float* out_score, int32_t* word_region, float* word_cos, int64_t word_ld,
+                          int32_t* region_word, float* region_cos, int64_t region_ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
