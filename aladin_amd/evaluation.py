@@ -7,6 +7,8 @@
     i2t / t2i                                <- alad/evaluation.py:158-327
     search_topk                              new: the k best gallery items of every query from matching-head embeddings,
                                              without the score matrix (ops.search_topk)
+    search_ndcg                              new: the nDCG of any ranking table by an aladin_amd.dcg.DCG scorer (ops.ndcg_from_ranking);
+                                             i2t / t2i with ndcg_scorer= report its means
     AverageMeter / LogCollector              <- alad/evaluation.py:22-77 (host bookkeeping)
 
 The per-query Python loops, per-iteration host->device copies and numpy argsort of the reference
@@ -415,20 +417,63 @@ def _npts(images, npts):
     return n_img if npts is None else min(int(npts), n_img)
 
 
+def search_ndcg(indices, ndcg_scorer, direction='i2t', fold_index=0, npts=None):
+    """nDCG of any (n_q, k) ranking table -- search_topk's, search_rerank's, a caller's -- as {method: float64 (n_q,) device
+    tensor}: row i is query i of fold `fold_index` of the scorer (aladin_amd.dcg.DCG), its entries gallery positions inside the
+    fold, best first (-1 = none); the first min(k, scorer.rank) count.  direction='i2t': images query captions (the scorer's
+    retrieval='sentence'); 't2i': captions query images ('image').  npts: the fold's images, default n_q ('i2t') or n_q // 5."""
+    if direction not in ('i2t', 't2i'):
+        raise ValueError("direction must be 'i2t' or 't2i'")
+    if ndcg_scorer is None or not hasattr(ndcg_scorer, 'compute_ndcg_batch'):
+        raise ValueError('search_ndcg: pass an aladin_amd.dcg.DCG scorer')
+    if not hasattr(indices, 'shape') or len(indices.shape) != 2 or indices.shape[0] < 1 or indices.shape[1] < 1:
+        raise ValueError('search_ndcg: the ranking must be an (n_q, k) table')
+    n_q = indices.shape[0]
+    if npts is None:
+        npts = n_q if direction == 'i2t' else n_q // CAPS_PER_IMG
+    return ndcg_scorer.compute_ndcg_batch(int(npts), indices, fold_index, 'sentence' if direction == 'i2t' else 'image')
+
+
+def _ndcg_means(sim, npts, direction, ndcg_scorer, fold_index):
+    """The last two entries of the i2t / t2i tuple: (0, 0) without a scorer, else the mean nDCG of the first npts images' (or their
+    captions') top-`rank` lists by the scorer's first two relevance methods."""
+    if ndcg_scorer is None:
+        return (0, 0)
+    n_img, n_cap = sim.shape
+    gallery, window, what = (n_cap, CAPS_PER_IMG * npts, 'captions') if direction == 'i2t' else (n_img, npts, 'images')
+    if gallery != window:
+        # the reference indexes the fold window with positions of the FULL ranking (dcg.py:25,29): an IndexError or silently wrong
+        # relevances when the two differ
+        raise ValueError('aladin_amd: nDCG needs the ranked gallery to be the fold window: %d %s ranked, %d in the window of npts=%d'
+                         % (gallery, what, window, npts))
+    with torch.no_grad():
+        if direction == 'i2t':
+            top = ops.topk_indices(sim[:npts], ndcg_scorer.rank, dim=1)
+        else:
+            top = ops.topk_indices(sim[:, :CAPS_PER_IMG * npts], ndcg_scorer.rank, dim=0)
+        per_query = search_ndcg(top, ndcg_scorer, direction, fold_index, npts)
+    means = [float(per_query[m].mean().item()) for m in list(ndcg_scorer.relevance_methods)[:2]]
+    return tuple(means + [0] * (2 - len(means)))
+
+
 def i2t(images, captions, img_lenghts, cap_lenghts, npts=None, return_ranks=False, ndcg_scorer=None, fold_index=0,
         measure='dot', sim_function=None, cap_batches=1):
     """reference alad/evaluation.py:158-241.  sim_function may be None (matching head), the string
     'alignment' (HIP alignment scores) or a callable (img, cap, img_len, cap_len) -> scores; it is
     called ONCE on the whole (n_img x n_cap) grid instead of once per query and caption chunk
     (cap_batches is accepted and ignored).  npts: only the first npts images are queries (:164-165); they are
-    still ranked against every caption.  Returns the 7-tuple, plus (ranks, top1) with return_ranks."""
-    if ndcg_scorer is not None:
-        raise NotImplementedError('aladin_amd: ndcg_scorer is out of scope (None at every reference call site)')
+    still ranked against every caption.  Returns the 7-tuple, plus (ranks, top1) with return_ranks.
+    ndcg_scorer: an aladin_amd.dcg.DCG; the last two entries of the tuple are then the MEAN nDCG over the queries by the scorer's
+    first and second relevance method (0 for a method it does not have), from every query's top-`scorer.rank` list
+    (ops.topk_indices on the grid) inside fold `fold_index`.  A deviation: the reference computes the per-query values and then
+    returns literal zeros (:236-237); the means are what its call sites print.  The ranked gallery must be exactly the fold's
+    window (5 * npts captions), ValueError otherwise.  Without a scorer the two entries stay 0."""
     sim = _eval_scores(images, captions, img_lenghts, cap_lenghts, measure, sim_function)
-    ranks, top1, _, _ = _ranks(sim)
     n = _npts(images, npts)
+    ndcg = _ndcg_means(sim, n, 'i2t', ndcg_scorer, fold_index)
+    ranks, top1, _, _ = _ranks(sim)
     ranks, top1 = ranks[:n], top1[:n]
-    m = _metrics(ranks) + (0, 0)
+    m = _metrics(ranks) + ndcg
     return (m, (ranks, top1)) if return_ranks else m
 
 
@@ -437,14 +482,16 @@ def t2i(images, captions, img_lenghts, cap_lenghts, npts=None, return_ranks=Fals
     """reference alad/evaluation.py:244-327.  With return_ranks the second element is (ranks, top50) as in the
     reference (:262,309,324-325): top50[c] = the 50 best images of caption c, best first (HIP top-k kernel; -1
     where there are fewer than 50 images).  npts: only the captions of the first npts images are queries
-    (:250-251), ranked against every image."""
-    if ndcg_scorer is not None:
-        raise NotImplementedError('aladin_amd: ndcg_scorer is out of scope (None at every reference call site)')
+    (:250-251), ranked against every image.
+    ndcg_scorer / fold_index: as in i2t -- the last two entries become the mean nDCG over the caption queries (the reference
+    returns literal zeros, :321-322); the ranked gallery must be exactly the fold's npts images, ValueError otherwise."""
     sim = _eval_scores(images, captions, img_lenghts, cap_lenghts, measure, sim_function)
+    n_img = _npts(images, npts)
+    ndcg = _ndcg_means(sim, n_img, 't2i', ndcg_scorer, fold_index)
     _, _, ranks, _ = _ranks(sim)
-    n = CAPS_PER_IMG * _npts(images, npts)
+    n = CAPS_PER_IMG * n_img
     ranks = ranks[:n]
-    m = _metrics(ranks) + (0, 0)
+    m = _metrics(ranks) + ndcg
     if not return_ranks:
         return m
     top50 = ops.topk_indices(sim[:, :n], 50, dim=0).cpu().numpy().astype(np.float64)     # float table like numpy.zeros((5*npts, 50))

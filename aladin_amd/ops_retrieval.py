@@ -227,3 +227,47 @@ def rerank_order(cand, scores, out_idx=None, out_val=None):
     _lib.check(_lib.load().aladin_rerank_order(_ptr(cand), _ptr(scores), cand.shape[0], cand.shape[1], _ptr(out_idx), _ptr(out_val),
                                                _stream()), 'rerank_order')
     return out_idx, out_val
+
+
+NDCG_MAX_GALLERY = 36864             # relevances per query among which the ideal DCG is selected (topk's candidate limit)
+NDCG_IDEAL_GIVEN = 1                 # ALADIN_NDCG_IDEAL_GIVEN of include/aladin_hip.h
+
+
+def ndcg_from_ranking(rel, ranking, dim=1, rank=None, ideal=None, return_parts=False):
+    """nDCG of n_q ranked lists, a float64 (n_q,) device tensor: dcg_from_ranking / ndcg_from_ranking of reference
+    alad/evaluate_utils/dcg.py:169-216 for every query at once (exponential gain 2 ** rel - 1 in float32, discount log2(r + 2) and
+    both sums in double; 0 where the ideal DCG is 0).
+    rel: 2-D float32 device tensor of relevances; the queries are its rows (dim=1) or its columns (dim=0, read in place: no
+    transpose), the other axis is the gallery.  ranking: (n_q, >= rank) int32, entry r of row q = the gallery position ranked r-th,
+    -1 (or anything outside the gallery) = no item: it adds nothing and keeps its position's discount.  rank: how many entries
+    count (default: the table's width); past the gallery size min(rank, gallery) counts.
+    ideal: the float64 (n_q,) ideal DCG of the same relevances AT THE SAME rank, from an earlier call with return_parts -- the
+    selection is skipped (the result's bits do not change) and the gallery limit of 36864 items does not apply.
+    return_parts=True: (ndcg, dcg, ideal).  Relevances are expected finite: a NaN's effect is unspecified."""
+    if not isinstance(rel, torch.Tensor) or rel.dim() != 2 or rel.dtype != torch.float32 or dim not in (0, 1):
+        raise ValueError('aladin_amd: ndcg_from_ranking expects a 2-D float32 relevance tensor and dim 0 or 1')
+    n_q, n_c = (rel.shape[0], rel.shape[1]) if dim == 1 else (rel.shape[1], rel.shape[0])
+    if n_q < 1 or n_c < 1:
+        raise ValueError('aladin_amd: ndcg_from_ranking needs a non-empty relevance matrix')
+    if not isinstance(ranking, torch.Tensor) or ranking.dim() != 2 or ranking.dtype != torch.int32 or ranking.shape[0] != n_q:
+        raise ValueError('aladin_amd: the ranking must be an (n_q, k) int32 tensor with one row per query (%d queries)' % n_q)
+    rank = ranking.shape[1] if rank is None else int(rank)
+    if not 1 <= rank <= ranking.shape[1]:
+        raise ValueError('aladin_amd: ndcg_from_ranking needs 1 <= rank <= the ranking\'s width %d (got %d)' % (ranking.shape[1], rank))
+    if ideal is None and n_c > NDCG_MAX_GALLERY:
+        raise ValueError('aladin_amd: ndcg_from_ranking selects the ideal DCG among at most %d gallery items (got %d); pass ideal='
+                         % (NDCG_MAX_GALLERY, n_c))
+    if ideal is not None and (not isinstance(ideal, torch.Tensor) or ideal.dtype != torch.float64 or tuple(ideal.shape) != (n_q,)):
+        raise ValueError('aladin_amd: ideal must be a float64 tensor of %d entries' % n_q)
+    _require_gpu(rel)                                    # after the limits: they hold whatever the device
+    if not ranking.is_cuda or (ideal is not None and not ideal.is_cuda):
+        raise RuntimeError('aladin_amd: the ranking and the ideal DCG must live on the GPU (no CPU fallback exists)')
+    sc = rel if rel.stride(1) == 1 else rel.contiguous()
+    ranking = ranking if ranking.stride(1) == 1 else ranking.contiguous()
+    q_stride, c_stride = (_ld(sc), 1) if dim == 1 else (1, _ld(sc))
+    out = torch.empty((3 if ideal is None else 2, n_q), dtype=torch.float64, device=sc.device)
+    best = out[2] if ideal is None else ideal.contiguous()
+    _lib.check(_lib.load().aladin_ndcg(_ptr(sc), q_stride, c_stride, n_q, n_c, _ptr(ranking), _ld(ranking), rank,
+                                       0 if ideal is None else NDCG_IDEAL_GIVEN, _ptr(out[0]), _ptr(out[1]), _ptr(best), _stream()),
+               'ndcg')
+    return (out[0], out[1], best) if return_parts else out[0]

@@ -533,6 +533,27 @@ ALADIN_API int aladin_align_pair_map(const void* x_rows, const int64_t* x_offset
                           const int32_t* cand, int k, float* out_score, int32_t* word_region, float* word_cos, int64_t word_ld,
                           int32_t* region_word, float* region_cos, int64_t region_ld, void* stream);
 
+/* nDCG of ranked lists against a relevance matrix (csrc/ndcg.hip): dcg_from_ranking / ndcg_from_ranking of reference
+ * alad/evaluate_utils/dcg.py:169-216 for n_q queries at once, without the two host argsorts per query.
+ *   rel: query q's relevance row is rel[q * q_stride + c * c_stride], c < n_c -- the stride pair of aladin_topk, so the columns
+ *   of a row-major matrix serve as queries without a transpose.
+ *   ranking (int32): ranking[q * ld_rank + r], r < rank, is the gallery position ranked r-th.  -1, or anything outside
+ *   [0, n_c), is "no item": it adds nothing, keeps its position's discount and is never dereferenced.
+ * Per query, with k = min(rank, n_c): gain = exp2f(rel) - 1.0f in float32, discount = log2(r + 2) in double,
+ *   dcg   = sum over r < k of gain(rel[ranking[r]]) / discount(r)
+ *   ideal = the same sum over the k largest relevances in descending order
+ *   ndcg  = ideal == 0 ? 0 : dcg / ideal
+ * both sums in double, in ascending r, by one instruction sequence: a ranking that lists the k largest relevances in descending
+ * order gives ndcg == 1.0 exactly.  ndcg / dcg / ideal: n_q doubles each; dcg may be NULL, ideal may be NULL without the flag.
+ * flags & ALADIN_NDCG_IDEAL_GIVEN: `ideal` is an INPUT (it depends on the data set and on rank, not on the ranking); nothing is
+ * staged or selected, the listed relevances are read straight from memory, and ndcg / dcg are bit-equal to the other path's.
+ * Relevances are expected finite; what a NaN does to the result is unspecified.
+ * Limits: n_c <= 36864 without the flag (ALADIN_ERR_UNSUPPORTED, checked before any launch); none on n_c with it.
+ * No workspace, no allocation, no synchronisation, no atomics: deterministic and graph-capturable. */
+#define ALADIN_NDCG_IDEAL_GIVEN 1
+ALADIN_API int aladin_ndcg(const float* rel, int64_t q_stride, int64_t c_stride, int n_q, int n_c, const int32_t* ranking,
+                int64_t ld_rank, int rank, int flags, double* ndcg, double* dcg, double* ideal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
