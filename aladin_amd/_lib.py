@@ -32,7 +32,7 @@ SYMBOLS = [
     'aladin_store_row_width', 'aladin_store_append', 'aladin_align_pack_store_x', 'aladin_align_pack_store_y', 'aladin_topk',
     'aladin_loss_total', 'aladin_grad_combine', 'aladin_heads_small_workspace_bytes', 'aladin_heads_small_fwd', 'aladin_heads_small_bwd',
     'aladin_search_workspace_bytes', 'aladin_search_topk', 'aladin_align_rescore', 'aladin_rerank_order',
-    'aladin_align_pair_map', 'aladin_ndcg',
+    'aladin_align_pair_map', 'aladin_ndcg', 'aladin_rouge_l',
 ]
 
 
@@ -128,6 +128,7 @@ def _declare(lib):
         'aladin_align_pair_map': (C.c_int, [p, p, p, p, i32, i32, p, p, p, p, i32, i32, i32, i32, i32, i32, i32, p, i32, p, p, p, i64, p, p, i64,
                                             p]),
         'aladin_ndcg': (C.c_int, [p, i64, i64, i32, i32, p, i64, i32, i32, p, p, p, p]),
+        'aladin_rouge_l': (C.c_int, [p, p, p, i32, i32, p, p, i32, i32, p, i32, p, i64, i32, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -2,6 +2,8 @@
 
     DCG                                      <- alad/evaluate_utils/dcg.py:7-33 (same relevance files, same window arithmetic)
     DCG.compute_ndcg_batch                   new: every query of a fold window in one launch
+    DCG.from_captions                        new: the 'rougeL' scorer of a split's captions, its relevance matrix computed on the device
+                                             (aladin_amd/rouge.py) instead of read from a precomputed file
     ndcg_from_ranking / dcg_from_ranking     <- alad/evaluate_utils/dcg.py:169-216
 
 The reference takes two numpy.argsorts per query and relevance method on the host; here a fold window of the relevance matrix is
@@ -71,6 +73,16 @@ class DCG:
                     raise ValueError('DCG: a relevance matrix must be (n_queries=%d, n_images), got %s' % (n_queries, tuple(r.shape)))
         self._windows = {}           # (method index, npts, fold_index) -> (5*npts, npts) float32 device tensor, both retrieval kinds
         self._ideals = {}            # (method index, npts, fold_index, retrieval) -> (rank, float64 (n_q,) ideal DCG)
+
+    @classmethod
+    def from_captions(cls, captions, rank=25, caps_per_img=5):
+        """A 'rougeL' scorer straight from the captions of a split (image j owns captions 5j .. 5j + 4): the relevance matrix is
+        computed on the device (aladin_amd.rouge.relevance_matrix) instead of being read from the reference's precomputed file."""
+        if int(caps_per_img) != CAPS_PER_IMG:
+            raise ValueError('DCG: the fold windows hold %d captions per image (got caps_per_img=%d)' % (CAPS_PER_IMG, caps_per_img))
+        from .rouge import relevance_matrix
+        rel = relevance_matrix(captions, caps_per_img)
+        return cls(None, rel.shape[0], None, rank=rank, relevance_methods=['rougeL'], relevances=[rel])
 
     def clear(self):
         """Drop the uploaded fold windows and their ideal DCGs."""

@@ -271,3 +271,96 @@ def ndcg_from_ranking(rel, ranking, dim=1, rank=None, ideal=None, return_parts=F
                                        0 if ideal is None else NDCG_IDEAL_GIVEN, _ptr(out[0]), _ptr(out[1]), _ptr(best), _stream()),
                'ndcg')
     return (out[0], out[1], best) if return_parts else out[0]
+
+
+ROUGE_MAX_LEN = 256                  # tokens of a caption the LCS kernel scores (4 words of 64 query positions); longer ones are truncated
+ROUGE_CLASSES = (64, 128, 256)       # query length classes: 1, 2 or 4 words per query, one launch each
+ROUGE_LCS = 1                        # ALADIN_ROUGE_LCS of include/aladin_hip.h
+
+
+def _check_captions(q_tok, q_off, g_tok, g_off, grp_off):
+    """The CSR operands of rouge_l: -> (n_q, n_g, n_img)."""
+    for tok, off, what in ((q_tok, q_off, 'query'), (g_tok, g_off, 'gallery')):
+        if not isinstance(tok, torch.Tensor) or tok.dim() != 1 or tok.dtype != torch.int32:
+            raise ValueError('aladin_amd: rouge_l: the %s tokens must be a 1-D int32 tensor of ids' % what)
+        if not isinstance(off, torch.Tensor) or off.dim() != 1 or off.dtype != torch.int64 or off.shape[0] < 2:
+            raise ValueError('aladin_amd: rouge_l: the %s offsets must be a 1-D int64 tensor of count + 1 >= 2 entries' % what)
+    if not isinstance(grp_off, torch.Tensor) or grp_off.dim() != 1 or grp_off.dtype != torch.int64 or grp_off.shape[0] < 2:
+        raise ValueError('aladin_amd: rouge_l: the group offsets must be a 1-D int64 tensor of n_img + 1 >= 2 entries')
+    return q_off.shape[0] - 1, g_off.shape[0] - 1, grp_off.shape[0] - 1
+
+
+def _require_gpu_ints(*tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError('aladin_amd: ROUGE-L is computed by a HIP kernel on an MI355X only; got a %s tensor '
+                               '(no CPU fallback exists)' % t.device)
+
+
+def rouge_l_launch(q_tok, q_off, q_max_len, g_tok, g_off, g_max_len, grp_off, out, q_rows=None, lcs=False):
+    """ONE aladin_rouge_l launch into `out`, nothing read back from the device (graph-capturable): the queries are scored with
+    1, 2 or 4 words by q_max_len <= 64 / 128 / 256, captions longer than q_max_len / g_max_len are truncated to it.
+    out: float32, rows with a unit inner stride and n_img columns (a column slice of a wider matrix keeps its other columns);
+    q_rows (int32, one per query): the row of `out` each query is written to (None: its own index).  lcs=True: the largest LCS
+    length instead of the F-measure.  rouge_l_relevance is the front end that finds the lengths and splits the classes."""
+    n_q, n_g, n_img = _check_captions(q_tok, q_off, g_tok, g_off, grp_off)
+    q_max_len, g_max_len = int(q_max_len), int(g_max_len)
+    if not (1 <= q_max_len <= ROUGE_MAX_LEN and 1 <= g_max_len <= ROUGE_MAX_LEN):
+        raise ValueError('aladin_amd: rouge_l scores captions of 1 to %d tokens (got maximum lengths %d and %d)'
+                         % (ROUGE_MAX_LEN, q_max_len, g_max_len))
+    if q_rows is not None and (not isinstance(q_rows, torch.Tensor) or q_rows.dtype != torch.int32 or tuple(q_rows.shape) != (n_q,)):
+        raise ValueError('aladin_amd: rouge_l: q_rows must be an int32 tensor with one output row per query (%d)' % n_q)
+    if not isinstance(out, torch.Tensor) or out.dim() != 2 or out.dtype != torch.float32 or out.shape[1] != n_img or \
+            (out.shape[1] > 1 and out.stride(1) != 1) or (q_rows is None and out.shape[0] != n_q):
+        raise ValueError('aladin_amd: rouge_l needs a float32 output of %s rows x %d images with a unit inner stride'
+                         % ('one row per query (%d)' % n_q if q_rows is None else 'the listed', n_img))
+    _require_gpu_ints(q_tok, q_off, g_tok, g_off, grp_off, out, q_rows)
+    q_tok, q_off, g_tok, g_off, grp_off = (t.contiguous() for t in (q_tok, q_off, g_tok, g_off, grp_off))
+    q_rows = q_rows.contiguous() if q_rows is not None else None
+    ld = out.stride(0) if out.shape[0] > 1 else max(out.stride(0), n_img)
+    _lib.check(_lib.load().aladin_rouge_l(_ptr(q_tok), _ptr(q_off), _ptr(q_rows), n_q, q_max_len, _ptr(g_tok), _ptr(g_off), n_g, g_max_len,
+                                          _ptr(grp_off), n_img, _ptr(out), ld, ROUGE_LCS if lcs else 0, _stream()), 'rouge_l')
+    return out
+
+
+def rouge_l_relevance(q_tok, q_off, g_tok, g_off, grp_off, out=None, q_rows=None, lcs=False):
+    """(n_q, n_img) float32 device tensor of ROUGE-L relevances: Rouge.score of reference alad/evaluate_utils/rouge.py:46-76 for
+    every (query caption, image) pair, the bits of the float32 file alad/evaluate_utils/compute_relevance.py writes.
+    q_tok / g_tok: int32 token ids of the query / gallery captions, one after another (any non-negative ids: no vocabulary limit);
+    q_off / g_off: int64 offsets, count + 1 entries; grp_off: int64, n_img + 1 entries -- image j owns gallery captions
+    grp_off[j] .. grp_off[j + 1] - 1.  Captions longer than 256 tokens are truncated to 256.
+    The maximum lengths are found on the host (one copy of the offsets); the queries go in one launch per non-empty length class
+    (<= 64, <= 128, <= 256 tokens: 1, 2 or 4 words of query positions).
+    out: a preallocated result (rows with a unit inner stride; other columns of a wider matrix are left alone).  q_rows (int32,
+    needs out): the row of `out` each query is written to.  lcs=True: the largest LCS length instead of the F-measure."""
+    n_q, _, n_img = _check_captions(q_tok, q_off, g_tok, g_off, grp_off)
+    if q_rows is not None and out is None:
+        raise ValueError('aladin_amd: rouge_l: q_rows names rows of a preallocated out=')
+    _require_gpu_ints(q_tok, q_off, g_tok, g_off, grp_off, out, q_rows)
+    if out is None:
+        out = torch.empty((n_q, n_img), dtype=torch.float32, device=q_tok.device)
+    q_len = (q_off[1:] - q_off[:-1]).cpu()
+    g_len = g_off[1:] - g_off[:-1]
+    if int(q_len.min()) < 1 or int(g_len.min()) < 1:
+        raise ValueError('aladin_amd: rouge_l: every caption holds at least one token (the empty caption is the one token \'\')')
+    g_max = min(int(g_len.max()), ROUGE_MAX_LEN)
+    if int(q_len.max()) <= ROUGE_CLASSES[0]:                 # COCO: every query in the one-word class, nothing to regroup
+        return rouge_l_launch(q_tok, q_off, int(q_len.max()), g_tok, g_off, g_max, grp_off, out, q_rows, lcs)
+    lo = 0
+    for hi in ROUGE_CLASSES:
+        pick = (q_len > lo) & (q_len <= hi) if hi < ROUGE_MAX_LEN else q_len > lo
+        lo = hi
+        idx = torch.nonzero(pick).flatten()
+        if idx.numel() == 0:
+            continue
+        # the class as a CSR of its own: its captions' tokens gathered in order
+        lens = q_len[idx]
+        off_c = torch.zeros(idx.numel() + 1, dtype=torch.int64)
+        off_c[1:] = torch.cumsum(lens, 0)
+        dev = q_tok.device
+        idx_d, off_d = idx.to(dev), off_c.to(dev)
+        seg = torch.repeat_interleave(torch.arange(idx.numel(), device=dev), lens.to(dev))
+        src = q_off[idx_d][seg] + (torch.arange(int(off_c[-1]), device=dev) - off_d[seg])
+        rows = idx_d.to(torch.int32) if q_rows is None else q_rows[idx_d].contiguous()
+        rouge_l_launch(q_tok[src], off_d, min(int(lens.max()), hi), g_tok, g_off, g_max, grp_off, out, rows, lcs)
+    return out

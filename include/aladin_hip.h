@@ -554,6 +554,30 @@ ALADIN_API int aladin_align_pair_map(const void* x_rows, const int64_t* x_offset
 ALADIN_API int aladin_ndcg(const float* rel, int64_t q_stride, int64_t c_stride, int n_q, int n_c, const int32_t* ranking,
                 int64_t ld_rank, int rank, int flags, double* ndcg, double* dcg, double* ideal, void* stream);
 
+/* ROUGE-L relevance of query captions against images (csrc/rouge.hip): Rouge.score of reference alad/evaluate_utils/rouge.py:46-76
+ * for every (query, image) pair at once -- the matrix alad/evaluate_utils/compute_relevance.py fills with one Python LCS table per
+ * (query, reference caption), and the `rel` aladin_ndcg grades against.
+ *   Captions are token-id sequences in CSR form: q_tok / g_tok (int32 ids, any non-negative value: there is no vocabulary limit;
+ *   equal ids = equal tokens) with q_off (n_q + 1) / g_off (n_g + 1) int64 offsets, the last one the token count.  A caption longer
+ *   than q_max_len / g_max_len is truncated to it on the device; offsets are clamped into their token array, so nothing outside the
+ *   arrays is read whatever they hold.  A gallery caption of no tokens is skipped, a query of none scores 0.
+ *   grp_off (n_img + 1 int64): image j owns the gallery captions grp_off[j] .. grp_off[j + 1] - 1 (ragged groups).
+ *   q_rows (n_q int32) or NULL: query i is written to row q_rows[i] of `out` (NULL: row i) -- a length class of a larger query
+ *   set is one launch.  The rows must exist; they are not checked.
+ * Per pair, with m the query's length, l_i the lengths of the image's references and lcs_i the longest common subsequences:
+ *   P = max_i lcs_i / m,   R = max_i (lcs_i / l_i),   out = (P != 0 && R != 0) ? ((1 + b2) * P) * R / (R + b2 * P) : 0
+ * with b2 = 1.2 * 1.2, in double, in this association and without contraction, rounded to float once on the store: the bits of the
+ * reference's float32 file.  A caption against an image that holds it scores exactly 1.0f.
+ * out[row * ld_out + j], j < n_img, ld_out >= n_img: each element written exactly once, columns past n_img untouched.
+ * flags & ALADIN_ROUGE_LCS: out = max_i lcs_i, the length itself (my_lcs of the reference file for one reference).
+ * Limits: 1 <= q_max_len, g_max_len <= 256 (ALADIN_ERR_UNSUPPORTED, checked before any launch); the kernel takes 1, 2 or 4
+ * 64-bit words per query by q_max_len <= 64 / 128 / 256.
+ * No workspace, no allocation, no synchronisation, no atomics on global memory: deterministic and graph-capturable. */
+#define ALADIN_ROUGE_LCS 1
+ALADIN_API int aladin_rouge_l(const int32_t* q_tok, const int64_t* q_off, const int32_t* q_rows, int n_q, int q_max_len,
+                   const int32_t* g_tok, const int64_t* g_off, int n_g, int g_max_len, const int64_t* grp_off, int n_img, float* out,
+                   int64_t ld_out, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
