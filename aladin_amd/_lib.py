@@ -10,36 +10,16 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # ALADIN_LIB points at an alternative build of the same ABI (kernel A/B runs, tools/ab_bench.py)
 LIB_PATH = os.environ.get('ALADIN_LIB') or os.path.join(_HERE, 'lib', 'libaladin_hip.so')
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 PRECISION_FP16, PRECISION_SPLIT = 0, 1      # ALADIN_PRECISION_* of include/aladin_hip.h
+LAYOUT_AUTO, LAYOUT_TILES, LAYOUT_TILES_WHOLE, LAYOUT_LONG = -1, 0, 1, 2      # ALADIN_LAYOUT_*
+TILE_MAX_SCORED = 96                        # ALADIN_TILE_MAX_SCORED
 BWD_PARTNERS_FP16, BWD_DENSE, BWD_DENSE_GATHER, TRIPLET_BWD_BASE_WORKSPACE, BWD_OWN_ROW_FP16 = 1, 2, 4, 8, 16      # ALADIN_BWD_*, ALADIN_TRIPLET_BWD_BASE_WORKSPACE
-
-# every symbol include/aladin_hip.h declares (tests check that the library exports all of them)
-SYMBOLS = [
-    'aladin_version', 'aladin_last_error', 'aladin_align_geometry', 'aladin_align_pack', 'aladin_align_scores',
-    'aladin_align_bwd_workspace_bytes', 'aladin_align_bwd',
-    'aladin_align_long_geometry', 'aladin_align_long_scores', 'aladin_align_long_bwd_workspace_bytes', 'aladin_align_long_bwd',
-    'aladin_align_triplet_workspace_bytes', 'aladin_align_triplet_fwd', 'aladin_align_triplet_bwd', 'aladin_heads_small_fwd_argmax',
-    'aladin_hinge_workspace_bytes', 'aladin_hinge_fwd_bwd', 'aladin_hinge_fused',
-    'aladin_listnet_workspace_bytes', 'aladin_listnet_fwd_bwd',
-    'aladin_distill_workspace_bytes', 'aladin_distill_mse_fwd_bwd', 'aladin_distill_contrastive_fwd_bwd',
-    'aladin_distill_ordinal_fwd_bwd', 'aladin_order_sim_fwd', 'aladin_order_sim_bwd', 'aladin_sgemm_strided',
-    'aladin_sim_workspace_bytes', 'aladin_sim_matrix', 'aladin_recall_workspace_bytes',
-    'aladin_recall_ranks', 'aladin_normsum_fwd', 'aladin_normsum_bwd',
-    'aladin_l2norm_fwd', 'aladin_l2norm_bwd',
-    'aladin_retrieval_workspace_bytes', 'aladin_retrieval_ranks', 'aladin_retrieval_ranks_exact', 'aladin_retrieval_stats_offset',
-    'aladin_scan_workspace_bytes', 'aladin_scan_fwd', 'aladin_scan_bwd',
-    'aladin_store_row_width', 'aladin_store_append', 'aladin_align_pack_store_x', 'aladin_align_pack_store_y', 'aladin_topk',
-    'aladin_loss_total', 'aladin_grad_combine', 'aladin_heads_small_workspace_bytes', 'aladin_heads_small_fwd', 'aladin_heads_small_bwd',
-    'aladin_search_workspace_bytes', 'aladin_search_topk', 'aladin_align_rescore', 'aladin_rerank_order',
-    'aladin_align_pair_map', 'aladin_ndcg', 'aladin_rouge_l',
-]
-
 
 class AlignGeom(C.Structure):
     """struct aladin_align_geom."""
     _fields_ = [(n, C.c_int32) for n in ('Bi', 'Bc', 'R', 'T', 'D', 'Rq', 'Tq', 'mrows', 'rem', 'tp16', 'trows', 'Dp',
-                                         'img_unit', 'cap_unit', 'Bi_pad', 'Bc_pad', 'x_tail', 'y_tail', 'split')] + \
+                                         'img_unit', 'cap_unit', 'Bi_pad', 'Bc_pad', 'x_tail', 'y_tail', 'split', 'layout')] + \
                [(n, C.c_int64) for n in ('xm_rows', 'xe_rows', 'y_rows', 'xm_bytes', 'xe_bytes', 'y_bytes',
                                          'e_bytes', 'rnorm_bytes')]
 
@@ -59,25 +39,18 @@ class Packed(C.Structure):
     _fields_ = [('xm', C.c_void_p), ('xe', C.c_void_p), ('y', C.c_void_p), ('rnorm', C.c_void_p)]
 
 
-_lib = None
-
-
-def _declare(lib):
+def _signatures():
     p, i32, i64, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
     G = C.POINTER(AlignGeom)
     SV, GV, PK = C.POINTER(SetView), C.POINTER(GradView), C.POINTER(Packed)
-    sig = {
+    return {
         'aladin_version': (C.c_int, []),
         'aladin_last_error': (C.c_char_p, []),
-        'aladin_align_geometry': (C.c_int, [i32, i32, i32, i32, i32, i32, i32, i32, G]),
+        'aladin_align_geometry': (C.c_int, [i32, i32, i32, i32, i32, i32, i32, i32, i32, G]),
         'aladin_align_pack': (C.c_int, [SV, SV, G, PK, p]),
         'aladin_align_scores': (C.c_int, [PK, G, p, p, i64, i32, p]),
         'aladin_align_bwd_workspace_bytes': (sz, [G, i32]),
         'aladin_align_bwd': (C.c_int, [SV, SV, G, PK, p, i64, p, p, p, GV, GV, p, i32, p]),
-        'aladin_align_long_geometry': (C.c_int, [i32, i32, i32, i32, i32, i32, i32, i32, G]),
-        'aladin_align_long_scores': (C.c_int, [PK, G, p, i64, p]),
-        'aladin_align_long_bwd_workspace_bytes': (sz, [G]),
-        'aladin_align_long_bwd': (C.c_int, [SV, SV, G, PK, p, i64, p, GV, GV, p, i32, p]),
         'aladin_align_triplet_workspace_bytes': (sz, [G]),
         'aladin_align_triplet_fwd': (C.c_int, [SV, SV, G, f32, PK, p, i64, p, p, p, p]),
         'aladin_align_triplet_bwd': (C.c_int, [SV, SV, G, PK, p, p, GV, GV, p, i32, p]),
@@ -130,7 +103,17 @@ def _declare(lib):
         'aladin_ndcg': (C.c_int, [p, i64, i64, i32, i32, p, i64, i32, i32, p, p, p, p]),
         'aladin_rouge_l': (C.c_int, [p, p, p, i32, i32, p, p, i32, i32, p, i32, p, i64, i32, p]),
     }
-    for name, (res, args) in sig.items():
+
+
+# every entry point include/aladin_hip.h declares, with its ctypes signature (tests check that the library exports all of them)
+SIGNATURES = _signatures()
+SYMBOLS = list(SIGNATURES)
+
+_lib = None
+
+
+def _declare(lib):
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

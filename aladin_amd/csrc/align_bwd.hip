@@ -66,7 +66,7 @@ static size_t dense_ws_layout(const aladin_align_geom* gs, char* base, DenseWs* 
 }
 // the tile classes the arg-max kernel covers; fills the split geometry of the problem
 static bool dense_supported(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail, aladin_align_geom* gs) {
-  if (aladin_align_geometry(Bi, Bc, R, T, D, x_tail, y_tail, ALADIN_PRECISION_SPLIT_TABLE, gs) != ALADIN_OK) return false;
+  if (aladin_align_geometry(Bi, Bc, R, T, D, x_tail, y_tail, ALADIN_PRECISION_SPLIT, ALADIN_LAYOUT_TILES_WHOLE, gs) != ALADIN_OK) return false;
   const int bm = gs->mrows == 48 ? 192 : 256;                  // the tile kernel's workgroup rows for the class
   return ((gs->mrows == 32 || gs->mrows == 48) ? gs->rem <= 8 : (gs->mrows == 64 && gs->rem == 0)) && 6 % gs->tp16 == 0 &&
          (gs->xm_rows / bm) * (gs->y_rows / 384) > 64 && gs->xm_rows % bm == 0 && gs->y_rows % 384 == 0;
@@ -74,6 +74,7 @@ static bool dense_supported(int Bi, int Bc, int R, int T, int D, int x_tail, int
 
 extern "C" size_t aladin_align_bwd_workspace_bytes(const aladin_align_geom* g, int flags) {
   if (!g) return 0;
+  if (g->layout == ALADIN_LAYOUT_LONG) return aladin_internal_long_bwd_bytes(g);      // the list path whatever the flags
   const int Bi = g->Bi, Bc = g->Bc, R = g->R, T = g->T, D = g->D;
   size_t n = bwd_base_bytes(Bi, Bc, T);
   if (n == 0 || !(flags & ALADIN_BWD_DENSE)) return n;
@@ -741,7 +742,7 @@ __global__ __launch_bounds__(256) void bwd_rows_kernel(
 // ------------------------------------------------------------------------------------------------
 // Classes the fp16 pair kernel covers (the comment above PairCfg).  ops._pair_kernel_covers is the Python mirror of this.
 static bool pair16_covers(const aladin_align_geom* g) {
-  return (g->mrows == 32 || g->mrows == 48 || (g->mrows == 64 && g->rem == 0)) && g->tp16 <= 4;
+  return g->layout != ALADIN_LAYOUT_LONG && (g->mrows == 32 || g->mrows == 48 || (g->mrows == 64 && g->rem == 0)) && g->tp16 <= 4;
 }
 static inline int bwd_Rq(const aladin_align_geom* g) { return g->R - 1 - g->x_tail; }
 static inline int bwd_Tq(const aladin_align_geom* g) { return g->T - 1 - g->y_tail; }
@@ -896,7 +897,7 @@ static int rows_gather(const BwdProblem& pr, const float* dS, int64_t ld_dS, con
   return aladin_check_launch("bwd_rows_kernel");
 }
 
-// ---- the exported forms (include/aladin_hip.h, ABI 12) ----------------------------------------------------------------------
+// ---- the exported forms (include/aladin_hip.h, ABI 13) ----------------------------------------------------------------------
 static const char* bwd_common_check(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g) {
   if (!g) return "null geometry";
   if (!set_ok(im) || !set_ok(s)) return "null set";
@@ -909,6 +910,9 @@ extern "C" int aladin_align_bwd(const aladin_set* im, const aladin_set* s, const
   if (const char* e = bwd_common_check(im, s, g)) { aladin_set_error("align_bwd: %s", e); return ALADIN_ERR_ARG; }
   if (g->split) { aladin_set_error("align_bwd: split-precision operands are forward-only (evaluation); pack with ALADIN_PRECISION_FP16"); return ALADIN_ERR_UNSUPPORTED; }
   if (flags & ~(ALADIN_BWD_PARTNERS_FP16 | ALADIN_BWD_OWN_ROW_FP16 | ALADIN_BWD_DENSE | ALADIN_BWD_DENSE_GATHER)) { aladin_set_error("align_bwd: unknown flags %d", flags); return ALADIN_ERR_ARG; }
+  // long sets: their own stages (align_long.hip); the list path for any dS, so the dense bits and a given pair list mean nothing
+  if (g->layout == ALADIN_LAYOUT_LONG)
+    return aladin_internal_long_bwd(im, s, g, p, dS, ld_dS, gscale, d_im, d_s, workspace, flags & (ALADIN_BWD_PARTNERS_FP16 | ALADIN_BWD_OWN_ROW_FP16), stream);
   if (!grad_ok(d_im) || !grad_ok(d_s)) { aladin_set_error("align_bwd: bad gradient views"); return ALADIN_ERR_ARG; }
   if ((pairs == nullptr) != (pair_count == nullptr)) { aladin_set_error("align_bwd: pairs and pair_count go together"); return ALADIN_ERR_ARG; }
   const BwdProblem pr = bwd_problem(im, s, g, p, stream);
@@ -960,7 +964,7 @@ static bool triplet_supported(const aladin_align_geom* g) {
 }
 
 extern "C" size_t aladin_align_triplet_workspace_bytes(const aladin_align_geom* g) {
-  if (!g || g->Bi < 1 || g->Bc < 1) return 0;
+  if (!g || g->Bi < 1 || g->Bc < 1 || g->layout == ALADIN_LAYOUT_LONG) return 0;
   return triplet_ws_layout(g, nullptr, nullptr);
 }
 
@@ -997,6 +1001,7 @@ extern "C" int aladin_align_triplet_bwd(const aladin_set* im, const aladin_set* 
                                         void* workspace, int flags, void* stream) {
   if (const char* e = bwd_common_check(im, s, g)) { aladin_set_error("align_triplet_bwd: %s", e); return ALADIN_ERR_ARG; }
   if (!workspace) { aladin_set_error("align_triplet_bwd: null workspace"); return ALADIN_ERR_ARG; }
+  if (g->layout == ALADIN_LAYOUT_LONG) { aladin_set_error("align_triplet_bwd: the tile classes only, not a long-set geometry"); return ALADIN_ERR_UNSUPPORTED; }
   // the backward base workspace itself (aladin_heads_small_fwd_argmax's caller), or the one inside the triplet workspace
   void* bwd_workspace = workspace;
   if (!(flags & ALADIN_TRIPLET_BWD_BASE_WORKSPACE)) {

@@ -42,18 +42,23 @@
 // ------------------------------------------------------------------------------------------------
 // geometry
 // ------------------------------------------------------------------------------------------------
-extern "C" int aladin_align_geometry(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail, int precision,
+extern "C" int aladin_align_geometry(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail, int precision, int layout,
                                      aladin_align_geom* g) {
-  if (precision != ALADIN_PRECISION_FP16 && precision != ALADIN_PRECISION_SPLIT && precision != ALADIN_PRECISION_SPLIT_TABLE) { aladin_set_error("align_geometry: unknown precision %d", precision); return ALADIN_ERR_ARG; }
+  if (precision != ALADIN_PRECISION_FP16 && precision != ALADIN_PRECISION_SPLIT) { aladin_set_error("align_geometry: unknown precision %d", precision); return ALADIN_ERR_ARG; }
+  if (layout < ALADIN_LAYOUT_AUTO || layout > ALADIN_LAYOUT_LONG) { aladin_set_error("align_geometry: unknown layout %d", layout); return ALADIN_ERR_ARG; }
   if (!g || Bi < 1 || Bc < 1 || D < 1) { aladin_set_error("align_geometry: bad sizes Bi=%d Bc=%d D=%d", Bi, Bc, D); return ALADIN_ERR_ARG; }
   if (x_tail < 0 || y_tail < 0 || x_tail > 8 || y_tail > 8) { aladin_set_error("align_geometry: bad tails %d %d", x_tail, y_tail); return ALADIN_ERR_ARG; }
   if (R < 2 + x_tail || T < 2 + y_tail) { aladin_set_error("align_geometry: sets too short (R=%d T=%d): position 0 and the last %d / %d positions are dropped", R, T, x_tail, y_tail); return ALADIN_ERR_ARG; }
+  const bool past_tiles = R - 1 - x_tail > ALADIN_TILE_MAX_SCORED || T - 1 - y_tail > ALADIN_TILE_MAX_SCORED;
+  if (layout == ALADIN_LAYOUT_AUTO) layout = past_tiles ? ALADIN_LAYOUT_LONG : ALADIN_LAYOUT_TILES;
+  if (layout == ALADIN_LAYOUT_LONG) return aladin_internal_long_layout(Bi, Bc, R, T, D, x_tail, y_tail, precision, g);
   memset(g, 0, sizeof(*g));
   g->Bi = Bi; g->Bc = Bc; g->R = R; g->T = T; g->D = D;
   g->x_tail = x_tail; g->y_tail = y_tail;
   g->split = precision != ALADIN_PRECISION_FP16;
+  g->layout = layout;
   g->Rq = R - 1 - x_tail; g->Tq = T - 1 - y_tail;
-  if (g->Rq > 96 || g->Tq > 96) { aladin_set_error("align_geometry: at most 97 regions / 99 tokens supported (got R=%d T=%d)", R, T); return ALADIN_ERR_UNSUPPORTED; }
+  if (past_tiles) { aladin_set_error("align_geometry: at most 97 regions / 99 tokens supported (got R=%d T=%d)", R, T); return ALADIN_ERR_UNSUPPORTED; }
   // R' = mrows + rem: `mrows` rows per image in the main operand (16-row MFMA tiles; rows past R' repeat region 0), `rem`
   // leftover regions per image go through the side GEMM instead of opening another tile (measured at B=256, T=50, D=768, forward
   // incl. packing: R'=34 0.183 vs 0.271 ms with a second region tile, R'=36 0.200 vs 0.273, R'=38 0.215 vs 0.277, R'=40 0.236 vs 0.276).
@@ -76,10 +81,10 @@ extern "C" int aladin_align_geometry(int Bi, int Bc, int R, int T, int D, int x_
   // rows per caption in y: whole 16-word tiles, except the "half" classes -- T' <= 8 packs a caption into half a tile, T' 17..24
   // into 1.5, T' 33..40 (VinVL's 35-token captions: 35 words of 48 would be 27 % padding) into 2.5: two captions share 1 / 3 / 5
   // tiles and the epilogue splits the middle one between them by lane (caption_add).  Region classes of the 16x16x32 kernels (32,
-  // 48 or 64 main rows); every precision except ALADIN_PRECISION_SPLIT_TABLE (the arg-max table kernel of the dense backward keeps
+  // 48 or 64 main rows); not under ALADIN_LAYOUT_TILES_WHOLE (the arg-max table kernel of the dense backward keeps
   // whole tiles).  Captions per unit: 384 / 640 rows = whole score tiles (384; 320 and 160 columns) and side GEMM tiles (64 / 128).
   g->trows = 16 * g->tp16;
-  if (precision != ALADIN_PRECISION_SPLIT_TABLE && g->mrows <= 64) {
+  if (layout != ALADIN_LAYOUT_TILES_WHOLE && g->mrows <= 64) {
     if (g->Tq <= 8) { g->trows = 8; g->cap_unit = 48; }
     else if (g->Tq > 16 && g->Tq <= 24) { g->trows = 24; g->cap_unit = 16; }
     else if (g->Tq > 32 && g->Tq <= 40) { g->trows = 40; g->cap_unit = 16; }
@@ -1183,6 +1188,7 @@ extern "C" int aladin_align_scores(const aladin_packed* p, const aladin_align_ge
                                    void* stream) {
   if (!p) { aladin_set_error("align_scores: null argument"); return ALADIN_ERR_ARG; }
   if (flags & ~ALADIN_SCORES_REUSE_SIDE) { aladin_set_error("align_scores: unknown flags %d", flags); return ALADIN_ERR_ARG; }
+  if (g && g->layout == ALADIN_LAYOUT_LONG) return aladin_internal_long_scores(p, g, S, ldS, stream);
   return aladin_internal_scores(p->xm, p->xe, p->y, g, e_scratch, S, ldS, flags, stream);
 }
 

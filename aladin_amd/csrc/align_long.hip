@@ -3,7 +3,7 @@
 // (32 / 48 / 64 / 96 region rows, a caption inside one 96-column strip) are the limit of those kernels; this file holds the
 // path beside them, and nothing the shorter shapes launch lives here.
 //
-// packing        the packers of align_fwd.hip (aladin_align_pack) on the geometry of aladin_align_long_geometry: mrows =
+// packing        the packers of align_fwd.hip (aladin_align_pack) on an ALADIN_LAYOUT_LONG geometry: mrows =
 //                round_up(R', 32) rows per max-side sample (rows past R' repeat position 1: max is idempotent), no side rows,
 //                trows = round_up(T', 16) rows per sum-side sample; the masking conventions of align_fwd.hip carry over
 //                (masked positions are zero rows, so the zero fill takes part in the max of a shorter sample).
@@ -22,6 +22,8 @@
 //                   packed fp16 operands under ALADIN_BWD_PARTNERS_FP16 / ALADIN_BWD_OWN_ROW_FP16) and applies the
 //                   normalise backward.  Every output row written exactly once, no atomics.
 //                Dense dS (the sum-of-violations hinge, a gradient on S) takes the same pair-list path.
+// Nothing is exported from here: aladin_align_geometry / aladin_align_scores (align_fwd.hip) and aladin_align_bwd with its workspace
+// query (align_bwd.hip) hand a geometry whose layout is ALADIN_LAYOUT_LONG to the aladin_internal_long_* functions below.
 #include <string.h>
 
 #include "../../include/aladin_hip.h"
@@ -33,17 +35,14 @@
 #define LS_NT 8            // 16-column tiles per wave: a workgroup covers up to 512 columns
 #define LS_COLS (16 * LS_WAVES * LS_NT)
 
-extern "C" int aladin_align_long_geometry(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail, int precision,
-                                          aladin_align_geom* g) {
-  if (precision != ALADIN_PRECISION_FP16 && precision != ALADIN_PRECISION_SPLIT) { aladin_set_error("align_long_geometry: unknown precision %d", precision); return ALADIN_ERR_ARG; }
-  if (!g || Bi < 1 || Bc < 1 || D < 1) { aladin_set_error("align_long_geometry: bad sizes Bi=%d Bc=%d D=%d", Bi, Bc, D); return ALADIN_ERR_ARG; }
-  if (x_tail < 0 || y_tail < 0 || x_tail > 8 || y_tail > 8) { aladin_set_error("align_long_geometry: bad tails %d %d", x_tail, y_tail); return ALADIN_ERR_ARG; }
-  if (R < 2 + x_tail || T < 2 + y_tail) { aladin_set_error("align_long_geometry: sets too short (R=%d T=%d): position 0 and the last %d / %d positions are dropped", R, T, x_tail, y_tail); return ALADIN_ERR_ARG; }
-  if (R > LONG_MAX_POS || T > LONG_MAX_POS) { aladin_set_error("align_long_geometry: at most %d positions per set (got R=%d T=%d)", LONG_MAX_POS, R, T); return ALADIN_ERR_UNSUPPORTED; }
+// the ALADIN_LAYOUT_LONG branch of aladin_align_geometry, which has checked precision, sizes, tails and set lengths
+int aladin_internal_long_layout(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail, int precision, aladin_align_geom* g) {
+  if (R > LONG_MAX_POS || T > LONG_MAX_POS) { aladin_set_error("align_geometry: at most %d positions per set (got R=%d T=%d)", LONG_MAX_POS, R, T); return ALADIN_ERR_UNSUPPORTED; }
   memset(g, 0, sizeof(*g));
   g->Bi = Bi; g->Bc = Bc; g->R = R; g->T = T; g->D = D;
   g->x_tail = x_tail; g->y_tail = y_tail;
   g->split = precision == ALADIN_PRECISION_SPLIT;
+  g->layout = ALADIN_LAYOUT_LONG;
   g->Rq = R - 1 - x_tail; g->Tq = T - 1 - y_tail;
   g->mrows = round_up(g->Rq, 32);
   g->rem = 0;
@@ -65,12 +64,13 @@ extern "C" int aladin_align_long_geometry(int Bi, int Bc, int R, int T, int D, i
   return ALADIN_OK;
 }
 
-// the entry points below take only geometries of aladin_align_long_geometry (a tile-class geometry has another layout)
+// the functions below take only what aladin_align_geometry makes for ALADIN_LAYOUT_LONG: recomputed and compared, layout included
+// (a tile-class geometry relabelled by hand has other rows and units)
 static bool long_geom_ok(const aladin_align_geom* g) {
   if (!g) return false;
   aladin_align_geom ref;
-  if (aladin_align_long_geometry(g->Bi, g->Bc, g->R, g->T, g->D, g->x_tail, g->y_tail,
-                                 g->split ? ALADIN_PRECISION_SPLIT : ALADIN_PRECISION_FP16, &ref) != ALADIN_OK) return false;
+  if (aladin_align_geometry(g->Bi, g->Bc, g->R, g->T, g->D, g->x_tail, g->y_tail, g->split ? ALADIN_PRECISION_SPLIT : ALADIN_PRECISION_FP16,
+                            ALADIN_LAYOUT_LONG, &ref) != ALADIN_OK) return false;
   return memcmp(&ref, g, sizeof(ref)) == 0;
 }
 
@@ -145,10 +145,10 @@ __global__ __launch_bounds__(256) void long_scores_kernel(const half_t* __restri
   }
 }
 
-extern "C" int aladin_align_long_scores(const aladin_packed* p, const aladin_align_geom* g, float* S, int64_t ldS, void* stream) {
-  if (!p || !p->xm || !p->y || !S) { aladin_set_error("align_long_scores: null argument"); return ALADIN_ERR_ARG; }
-  if (!long_geom_ok(g)) { aladin_set_error("align_long_scores: the geometry is not one of aladin_align_long_geometry"); return ALADIN_ERR_ARG; }
-  if (ldS < g->Bc) { aladin_set_error("align_long_scores: ldS %lld < Bc %d", (long long)ldS, g->Bc); return ALADIN_ERR_ARG; }
+int aladin_internal_long_scores(const aladin_packed* p, const aladin_align_geom* g, float* S, int64_t ldS, void* stream) {
+  if (!p || !p->xm || !p->y || !S) { aladin_set_error("align_scores: null argument"); return ALADIN_ERR_ARG; }
+  if (!long_geom_ok(g)) { aladin_set_error("align_scores: not a long-set geometry of aladin_align_geometry"); return ALADIN_ERR_ARG; }
+  if (ldS < g->Bc) { aladin_set_error("align_scores: ldS %lld < Bc %d", (long long)ldS, g->Bc); return ALADIN_ERR_ARG; }
   const float scale = g->split ? 1.0f / (16384.0f * 16384.0f) : 1.0f;       // split operands carry 2^14 each (align_fwd.hip)
   hipLaunchKernelGGL(long_scores_kernel, dim3((unsigned)(g->Bc_pad / g->cap_unit), (unsigned)g->Bi), dim3(256), 0, (hipStream_t)stream,
                      (const half_t*)p->xm, (const half_t*)p->y, g->mrows, g->trows, g->Dp, g->Bc, g->cap_unit, S, ldS, scale);
@@ -160,7 +160,7 @@ extern "C" int aladin_align_long_scores(const aladin_packed* p, const aladin_ali
 // ------------------------------------------------------------------------------------------------
 using LongWs = PairWs<uint16_t>;     // the table: Bi*Bc rows of table_stride(Tq) 16-bit entries
 
-extern "C" size_t aladin_align_long_bwd_workspace_bytes(const aladin_align_geom* g) {
+size_t aladin_internal_long_bwd_bytes(const aladin_align_geom* g) {
   if (!long_geom_ok(g)) return 0;
   return pair_ws_layout<uint16_t>(g->Bi, g->Bc, g->Tq, nullptr, nullptr);
 }
@@ -267,7 +267,7 @@ __device__ __forceinline__ void long_gather(const float* __restrict__ raw, const
   }
 }
 
-// where the packers put region r of max-side sample b / word w of sum-side sample b (aladin_align_long_geometry), and the rows'
+// where the packers put region r of max-side sample b / word w of sum-side sample b (ALADIN_LAYOUT_LONG), and the rows'
 // inverse norms ([xm rows | y rows])
 struct LongPacked { const half_t* xm; const half_t* y; const float* rnorm; int Dp, mrows, trows; int64_t y_row0; };
 
@@ -390,23 +390,23 @@ static int launch_long_rows(bool p16, bool o16, dim3 grid, hipStream_t st, const
   return aladin_check_launch("long_rows_kernel");
 }
 
-extern "C" int aladin_align_long_bwd(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* p,
-                                     const float* dS, int64_t ld_dS, const float* gscale, const aladin_set_grad* d_im,
-                                     const aladin_set_grad* d_s, void* workspace, int flags, void* stream) {
-  if (!set_ok(im) || !set_ok(s) || !dS || !workspace) { aladin_set_error("align_long_bwd: null argument"); return ALADIN_ERR_ARG; }
-  if (!grad_ok(d_im) || !grad_ok(d_s)) { aladin_set_error("align_long_bwd: bad gradient views"); return ALADIN_ERR_ARG; }
-  if (!long_geom_ok(g)) { aladin_set_error("align_long_bwd: the geometry is not one of aladin_align_long_geometry"); return ALADIN_ERR_ARG; }
-  if (g->split) { aladin_set_error("align_long_bwd: split-precision operands are forward-only (evaluation); pack with ALADIN_PRECISION_FP16"); return ALADIN_ERR_UNSUPPORTED; }
-  if (flags & ~(ALADIN_BWD_PARTNERS_FP16 | ALADIN_BWD_OWN_ROW_FP16)) { aladin_set_error("align_long_bwd: unknown flags %d", flags); return ALADIN_ERR_ARG; }
-  if ((flags & ALADIN_BWD_OWN_ROW_FP16) && !(flags & ALADIN_BWD_PARTNERS_FP16)) { aladin_set_error("align_long_bwd: ALADIN_BWD_OWN_ROW_FP16 needs ALADIN_BWD_PARTNERS_FP16"); return ALADIN_ERR_ARG; }
-  if ((flags & ALADIN_BWD_PARTNERS_FP16) && (!p || !p->xm || !p->y || !p->rnorm)) { aladin_set_error("align_long_bwd: ALADIN_BWD_PARTNERS_FP16 needs the packed operands with their inverse norms"); return ALADIN_ERR_ARG; }
-  if (g->D % 4 != 0 || g->D > 1024) { aladin_set_error("align_long_bwd: D must be a multiple of 4 and <= 1024 (got %d)", g->D); return ALADIN_ERR_UNSUPPORTED; }
-  if (ld_dS < g->Bc) { aladin_set_error("align_long_bwd: ld_dS %lld < Bc %d", (long long)ld_dS, g->Bc); return ALADIN_ERR_ARG; }
+// flags: the caller (aladin_align_bwd) has rejected unknown bits; the dense bits mean nothing here
+int aladin_internal_long_bwd(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* p,
+                             const float* dS, int64_t ld_dS, const float* gscale, const aladin_set_grad* d_im,
+                             const aladin_set_grad* d_s, void* workspace, int flags, void* stream) {
+  if (!set_ok(im) || !set_ok(s) || !dS || !workspace) { aladin_set_error("align_bwd: null argument"); return ALADIN_ERR_ARG; }
+  if (!grad_ok(d_im) || !grad_ok(d_s)) { aladin_set_error("align_bwd: bad gradient views"); return ALADIN_ERR_ARG; }
+  if (!long_geom_ok(g)) { aladin_set_error("align_bwd: not a long-set geometry of aladin_align_geometry"); return ALADIN_ERR_ARG; }
+  if (g->split) { aladin_set_error("align_bwd: split-precision operands are forward-only (evaluation); pack with ALADIN_PRECISION_FP16"); return ALADIN_ERR_UNSUPPORTED; }
+  if ((flags & ALADIN_BWD_OWN_ROW_FP16) && !(flags & ALADIN_BWD_PARTNERS_FP16)) { aladin_set_error("align_bwd: ALADIN_BWD_OWN_ROW_FP16 needs ALADIN_BWD_PARTNERS_FP16"); return ALADIN_ERR_ARG; }
+  if ((flags & ALADIN_BWD_PARTNERS_FP16) && (!p || !p->xm || !p->y || !p->rnorm)) { aladin_set_error("align_bwd: ALADIN_BWD_PARTNERS_FP16 needs the packed operands with their inverse norms"); return ALADIN_ERR_ARG; }
+  if (g->D % 4 != 0 || g->D > 1024) { aladin_set_error("align_bwd: D must be a multiple of 4 and <= 1024 (got %d)", g->D); return ALADIN_ERR_UNSUPPORTED; }
+  if (ld_dS < g->Bc) { aladin_set_error("align_bwd: ld_dS %lld < Bc %d", (long long)ld_dS, g->Bc); return ALADIN_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   LongWs ws;
   pair_ws_layout(g->Bi, g->Bc, g->Tq, (char*)workspace, &ws);
   const int tstride = table_stride(g->Tq);
-  if (int rc = aladin_internal_compact_pairs(dS, ld_dS, g->Bi, g->Bc, ws.counter, ws.pairs, "align_long_bwd", st)) return rc;     // list order is irrelevant: one workgroup per pair
+  if (int rc = aladin_internal_compact_pairs(dS, ld_dS, g->Bi, g->Bc, ws.counter, ws.pairs, "align_bwd", st)) return rc;     // list order is irrelevant: one workgroup per pair
   const int64_t n = (int64_t)g->Bi * g->Bc;
   const int pblocks = (int)(n < 2048 ? n : 2048);
   hipLaunchKernelGGL(long_pair_argmax_kernel, dim3(pblocks), dim3(256), 0, st, im->data, im->stride_b, im->stride_r, im->len, s->data,

@@ -21,6 +21,11 @@ static inline bool grad_ok(const aladin_set_grad* v) { return v && v->data && v-
 // align_bwd.hip: zero the workspace's counter block and list the non-zero pairs of dS (bwd_compact_kernel); `entry` names the
 // calling entry point in the error text
 int aladin_internal_compact_pairs(const float* dS, int64_t ld, int Bi, int Bc, int* counter, int* pairs, const char* entry, hipStream_t st);
+// align_long.hip: what aladin_align_bwd_workspace_bytes / aladin_align_bwd do for ALADIN_LAYOUT_LONG (0 bytes: not such a geometry)
+size_t aladin_internal_long_bwd_bytes(const aladin_align_geom* g);
+int aladin_internal_long_bwd(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* p, const float* dS,
+                             int64_t ld_dS, const float* gscale, const aladin_set_grad* d_im, const aladin_set_grad* d_s, void* workspace,
+                             int flags, void* stream);
 // align_bwd_dense.hip: the row step of the dense-dS backward as two MFMA GEMMs over the arg-max table (see there)
 size_t aladin_internal_dense_rows_bytes(const aladin_align_geom* g);
 int aladin_internal_dense_rows(const BwdProblem& pr, const float* dS, int64_t ld_dS, const float* gscale, const uint8_t* table,

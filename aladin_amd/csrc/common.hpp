@@ -38,6 +38,10 @@ int aladin_internal_side_with_main_pack(const aladin_set* im, const aladin_set* 
 int aladin_internal_align_argmax(const aladin_align_geom* g, const void* xm, const void* xe, const void* y, float* E,
                                  const int32_t* im_len, const int32_t* s_len, uint8_t* table, int tstride, uint8_t* flags, hipStream_t stream);
 
+// align_long.hip: what aladin_align_geometry / aladin_align_scores do for ALADIN_LAYOUT_LONG
+int aladin_internal_long_layout(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail, int precision, aladin_align_geom* g);
+int aladin_internal_long_scores(const aladin_packed* p, const aladin_align_geom* g, float* S, int64_t ldS, void* stream);
+
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 

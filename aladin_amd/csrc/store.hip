@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void store_pack_y_kernel(const half_t* __restr
 
 static int store_row_width_fp16(int D) {
   aladin_align_geom g;
-  if (aladin_align_geometry(1, 1, 2, 4, D, 0, 2, ALADIN_PRECISION_FP16, &g) != ALADIN_OK) return -1;
+  if (aladin_align_geometry(1, 1, 2, 4, D, 0, 2, ALADIN_PRECISION_FP16, ALADIN_LAYOUT_TILES, &g) != ALADIN_OK) return -1;
   return g.Dp;
 }
 
@@ -168,6 +168,7 @@ extern "C" int aladin_store_append(const float* sets, int64_t stride_b, int64_t 
 extern "C" int aladin_align_pack_store_x(const void* rows, const int64_t* offsets, const int32_t* counts, const int32_t* ids,
                                          const aladin_align_geom* g, void* xm, void* xe, void* stream) {
   if (!rows || !offsets || !counts || !g || !xm || (g->rem && !xe)) { aladin_set_error("align_pack_store_x: null argument"); return ALADIN_ERR_ARG; }
+  if (g->layout == ALADIN_LAYOUT_LONG) { aladin_set_error("align_pack_store_x: the store packers cover the tile classes, not a long-set geometry"); return ALADIN_ERR_ARG; }
   const int64_t total = g->xm_rows + g->xe_rows;
   hipLaunchKernelGGL(store_pack_x_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                      (const half_t*)rows, offsets, counts, ids, g->Bi, g->Rq, g->Dp, g->mrows, g->rem > 0 ? g->rem : 1, g->xm_rows, total, (half_t*)xm,
@@ -178,6 +179,7 @@ extern "C" int aladin_align_pack_store_x(const void* rows, const int64_t* offset
 extern "C" int aladin_align_pack_store_y(const void* rows, const int64_t* offsets, const int32_t* counts, const int32_t* ids,
                                          const aladin_align_geom* g, void* y, void* stream) {
   if (!rows || !offsets || !counts || !g || !y) { aladin_set_error("align_pack_store_y: null argument"); return ALADIN_ERR_ARG; }
+  if (g->layout == ALADIN_LAYOUT_LONG) { aladin_set_error("align_pack_store_y: the store packers cover the tile classes, not a long-set geometry"); return ALADIN_ERR_ARG; }
   hipLaunchKernelGGL(store_pack_y_kernel, dim3((unsigned)((g->y_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                      (const half_t*)rows, offsets, counts, ids, g->Bc, g->Tq, g->Dp, g->trows, g->y_rows, (half_t*)y, g->split);
   return aladin_check_launch("store_pack_y_kernel");

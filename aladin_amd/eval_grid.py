@@ -126,7 +126,7 @@ class _Side:
     """One set of a grid.  tail: the trailing positions the alignment head drops; total: the positions of the padded set (a
     class's sub(index list, device index tensor, keep_masked) keeps it: a sample fills THAT set or it does not); counts() /
     max_count: the scored counts len - 1 - tail; key(): what a cached plan depends on (nothing that keeps a store alive)."""
-    long_sets = False                       # may the side's geometry be the long-set one (ops._scoring_geometry)?
+    long_sets = False                       # may the side's geometry be the long-set one (layout='auto')?
     pack_pair = None                        # optional: (y_side, R, T, precision) -> scores with ONE pack launch for both sets
 
     def top(self, keep_masked):
@@ -244,8 +244,7 @@ def score_block(x, y, precision):
     side-row scratch (Bx x 16*tp16*By floats when R' = 33) would pass E_SCRATCH_LIMIT."""
     Bx, By = len(x), len(y)
     R, T = min(x.total, x.top(True) + 1 + x.tail), min(y.total, y.top(False) + 1 + y.tail)
-    geometry = ops._scoring_geometry if x.long_sets else ops.align_geometry
-    geom = geometry(Bx, By, R, T, x.D, x.tail, y.tail, precision)
+    geom = ops.align_geometry(Bx, By, R, T, x.D, x.tail, y.tail, precision, 'auto' if x.long_sets else 'tiles')
     step = By if geom.e_bytes <= E_SCRATCH_LIMIT else max(geom.cap_unit, int(By * E_SCRATCH_LIMIT // geom.e_bytes) // geom.cap_unit * geom.cap_unit)
     if step >= By and x.pack_pair is not None:
         return x.pack_pair(y, R, T, precision)
@@ -253,6 +252,7 @@ def score_block(x, y, precision):
     S = torch.empty((Bx, By), dtype=torch.float32, device=x.device)
     for j0 in range(0, By, step):
         j1 = min(By, j0 + step)
-        g = ops.align_geometry(Bx, j1 - j0, R, T, x.D, x.tail, y.tail, precision)        # same max-side layout
+        g = ops.align_geometry(Bx, j1 - j0, R, T, x.D, x.tail, y.tail, precision,        # same max-side layout
+                               'long' if geom.layout == _lib.LAYOUT_LONG else 'tiles')
         ops.scores_from_packed(xm, xe, y.pack_sum(g, j0, j1), g, out=S[:, j0:j1])
     return S

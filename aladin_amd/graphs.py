@@ -21,6 +21,7 @@ previous step's), the logged terms leave by ONE asynchronous device->host copy t
 next step is issued (log='deferred'; log='sync' keeps the reference's immediate `.item()` protocol) -- the host never
 waits for the device, so issuing step n + 1 overlaps the replay of step n.
 """
+import gc
 from collections import OrderedDict, deque
 
 import numpy as np
@@ -130,13 +131,24 @@ class GraphedLossStep:
         for t in e.inputs:
             t.grad = None
         e.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(e.graph):
-            loss, losses = self._run(e, before)
-            e.loss = loss.detach()
-            e.terms = OrderedDict((k, v.detach()) for k, v in losses.items())
-            # the logged values as ONE device buffer, filled inside the graph: a single copy brings them to the host
-            e.log_buf = torch.stack([torch.as_tensor(t).detach().reshape(()).to(torch.float32) for _, t, _ in e.logged]) \
-                if e.logged else None
+        # No cyclic garbage collection inside the capture: a dead reference cycle that holds captured graphs (a dropped
+        # ALADModel(graphed=True) and its GraphedLossStep point at each other) is finalised by whichever allocation trips the
+        # collector, and destroying a graph synchronises the device -- a call the capture forbids, failing inside a destructor
+        # (the process aborts).  torch.cuda.graph does not collect on entry, so such cycles are collected here, beforehand.
+        gc.collect()
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(e.graph):
+                loss, losses = self._run(e, before)
+                e.loss = loss.detach()
+                e.terms = OrderedDict((k, v.detach()) for k, v in losses.items())
+                # the logged values as ONE device buffer, filled inside the graph: a single copy brings them to the host
+                e.log_buf = torch.stack([torch.as_tensor(t).detach().reshape(()).to(torch.float32) for _, t, _ in e.logged]) \
+                    if e.logged else None
+        finally:
+            if collecting:
+                gc.enable()
         e.grads = [t.grad for t in e.inputs]
         e.log_names = [(key, n) for key, _, n in e.logged] if e.logged else []
         return e

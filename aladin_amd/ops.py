@@ -19,7 +19,7 @@ def _pair_kernel_covers(geom):
     """Shapes the fp16 pair kernel of the backward covers (csrc/align_bwd.hip: bwd_pair_argmax16_kernel): a 64-row block per
     pair = the image's 32 / 48 main rows + a window on its side rows, or its 64 main rows; at most 64 padded words.
     The Python mirror of pair16_covers() in csrc/align_bwd.hip."""
-    return (geom.mrows in (32, 48) or (geom.mrows == 64 and geom.rem == 0)) and geom.tp16 <= 4
+    return geom.layout != _lib.LAYOUT_LONG and (geom.mrows in (32, 48) or (geom.mrows == 64 and geom.rem == 0)) and geom.tp16 <= 4
 
 
 # ------------------------------------------------------------------------------------------------
@@ -126,58 +126,48 @@ def _precision_code(precision):
     raise ValueError("aladin_amd: precision must be 'fp16' or 'split', got %r" % (precision,))
 
 
-def _geometry(long, Bi, Bc, R, T, D, x_tail, y_tail, precision):
-    """The cached struct aladin_align_geom of a problem, from aladin_align_geometry or (long) aladin_align_long_geometry."""
+# Long sets: past the tile classes (more than _lib.TILE_MAX_SCORED scored positions on either side) the packed layout, the score
+# kernel and the backward are those of csrc/align_long.hip, up to LONG_POSITIONS positions per set: a geometry whose layout is
+# _lib.LAYOUT_LONG, which the same entry points take.  Shapes inside the classes never get one, except under LONG_PATH_FORCE
+# (tests / tools: the long kernels against the tile kernels on the same shape).
+LONG_POSITIONS = 512
+LONG_PATH_FORCE = False
+_LAYOUT_CODES = {'tiles': _lib.LAYOUT_TILES, 'auto': _lib.LAYOUT_AUTO, 'long': _lib.LAYOUT_LONG}
+
+
+def _check_positions(R, T):
+    """The long-set geometry's limit, as the ValueError of the Python layer."""
+    if R > LONG_POSITIONS or T > LONG_POSITIONS:
+        raise ValueError('aladin_amd: alignment scores support at most %d positions per set (got %d on the max side, %d on the '
+                         'sum side)' % (LONG_POSITIONS, R, T))
+
+
+def align_geometry(Bi, Bc, R, T, D, x_tail=0, y_tail=2, precision=None, layout='tiles'):
+    """Packed layout (the cached struct aladin_align_geom) for a (max-side set Bi x R) x (sum-side set Bc x T) problem; the
+    tails are the trailing positions each set drops (images 0, captions 2 -- reference alad/loss.py:87-90).
+    layout: 'tiles' (the tile classes: at most 96 scored positions), 'long' (the long-set layout) or 'auto' (the tile classes,
+    past them the long-set layout -- what the scoring path packs for)."""
     prec = _precision_code(precision)
-    key = (Bi, Bc, R, T, D, x_tail, y_tail, prec)
-    if long:
-        key = ('long',) + key
+    auto = layout == 'auto'
+    if auto and LONG_PATH_FORCE:
+        layout = 'long'
+    key = (Bi, Bc, R, T, D, x_tail, y_tail, prec, layout)
     g = _GEOM_CACHE.get(key)
     if g is None:
-        g = LongGeom() if long else _lib.AlignGeom()
-        name = 'align_long_geometry' if long else 'align_geometry'
-        _lib.check(getattr(_lib.load(), 'aladin_' + name)(Bi, Bc, R, T, D, x_tail, y_tail, prec, C.byref(g)), name)
+        if auto:
+            _check_positions(R, T)
+        g = _lib.AlignGeom()
+        _lib.check(_lib.load().aladin_align_geometry(Bi, Bc, R, T, D, x_tail, y_tail, prec, _LAYOUT_CODES[layout], C.byref(g)),
+                   'align_geometry')
         if len(_GEOM_CACHE) < 1024:
             _GEOM_CACHE[key] = g
     return g
 
 
-def align_geometry(Bi, Bc, R, T, D, x_tail=0, y_tail=2, precision=None):
-    """Packed layout for a (max-side set Bi x R) x (sum-side set Bc x T) problem; the tails are the
-    trailing positions each set drops (images 0, captions 2 -- reference alad/loss.py:87-90)."""
-    return _geometry(False, Bi, Bc, R, T, D, x_tail, y_tail, precision)
-
-
-# Long sets: past the tile classes of aladin_align_geometry (more than 96 scored positions on either side) the packed layout,
-# the score kernel and the backward are those of csrc/align_long.hip (aladin_align_long_*), up to LONG_POSITIONS positions per
-# set.  Shapes inside the classes never take them, except under LONG_PATH_FORCE (tests / tools: the long kernels against the
-# tile kernels on the same shape).
-LONG_POSITIONS = 512
-LONG_PATH_FORCE = False
-
-
-class LongGeom(_lib.AlignGeom):
-    """struct aladin_align_geom from aladin_align_long_geometry: the layout the long-set kernels read."""
-
-
 def is_long(R, T, x_tail=0, y_tail=2):
-    """Does a (max side R positions) x (sum side T positions) problem take the long-set kernels?"""
-    return LONG_PATH_FORCE or R - 1 - x_tail > 96 or T - 1 - y_tail > 96
-
-
-def long_geometry(Bi, Bc, R, T, D, x_tail=0, y_tail=2, precision=None):
-    """Packed layout of the long-set kernels (aladin_align_long_geometry) for up to LONG_POSITIONS positions per set."""
-    return _geometry(True, Bi, Bc, R, T, D, x_tail, y_tail, precision)
-
-
-def _scoring_geometry(Bi, Bc, R, T, D, x_tail, y_tail, precision=None):
-    """The layout the scoring path packs for: the tile classes, or past them the long-set layout."""
-    if is_long(R, T, x_tail, y_tail):
-        if R > LONG_POSITIONS or T > LONG_POSITIONS:
-            raise ValueError('aladin_amd: alignment scores support at most %d positions per set (got %d on the max side, %d on the '
-                             'sum side)' % (LONG_POSITIONS, R, T))
-        return long_geometry(Bi, Bc, R, T, D, x_tail, y_tail, precision)
-    return align_geometry(Bi, Bc, R, T, D, x_tail, y_tail, precision)
+    """Does a (max side R positions) x (sum side T positions) problem take the long-set kernels?  What layout='auto' answers
+    (tests/test_long_sets_cpu.py), for the callers that route without a geometry in hand."""
+    return LONG_PATH_FORCE or R - 1 - x_tail > _lib.TILE_MAX_SCORED or T - 1 - y_tail > _lib.TILE_MAX_SCORED
 
 
 def _set_view(t, len_t):
@@ -218,9 +208,6 @@ def scores_from_packed(xm, xe, y, geom, out=None, e_scratch=None, reuse_side=Fal
     lib = _lib.load()
     S = out if out is not None else torch.empty((geom.Bi, geom.Bc), dtype=torch.float32, device=xm.device)
     pk = Packed(geom, xm, xe, y).struct()
-    if isinstance(geom, LongGeom):
-        _lib.check(lib.aladin_align_long_scores(C.byref(pk), C.byref(geom), _ptr(S), S.stride(0), _stream()), 'align_long_scores')
-        return S
     e = e_scratch if e_scratch is not None else _workspace(geom.e_bytes, xm.device)
     _lib.check(lib.aladin_align_scores(C.byref(pk), C.byref(geom), _ptr(e), _ptr(S), S.stride(0), 1 if reuse_side else 0, _stream()),
                'align_scores')
@@ -247,9 +234,7 @@ def _check_backward_supported(im, s, x_tail, y_tail):
     if D % 4 != 0 or D > 1024:
         raise ValueError('aladin_amd: differentiable alignment scores need D <= 1024 (got D=%d; the public entry points pad a '
                          'feature size that is not a multiple of 4); score under torch.no_grad()' % D)
-    if R > LONG_POSITIONS or T > LONG_POSITIONS:            # = the long-set geometry's limit (aladin_align_long_geometry)
-        raise ValueError('aladin_amd: alignment scores support at most %d positions per set '
-                         '(got %d on the max side, %d on the sum side)' % (LONG_POSITIONS, R, T))
+    _check_positions(R, T)
 
 
 def pack_sets(im, s, im_len_t, s_len_t, geom, norms=True):
@@ -273,7 +258,7 @@ def _align_forward(im, s, im_len_t, s_len_t, x_tail=0, y_tail=2, precision=None,
     Bc, T, D2 = s.shape
     if D != D2:
         raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (D, D2))
-    geom = _scoring_geometry(Bi, Bc, R, T, D, x_tail, y_tail, precision)
+    geom = align_geometry(Bi, Bc, R, T, D, x_tail, y_tail, precision, layout='auto')
     packed = Packed(*pack_sets(_rows_inner_contig(im), _rows_inner_contig(s), im_len_t, s_len_t, geom, norms=norms))
     return scores_from_packed(packed.xm, packed.xe, packed.y, geom), packed
 
@@ -368,7 +353,7 @@ def _gemm_rows_pay(fill, Rq):
 
 
 def _align_backward(im, s, im_len_t, s_len_t, dS, gscale=None, packed=None, pairs=None, x_tails=(0, 2), dense=False, fill=None):
-    """aladin_align_bwd, or for a long-set problem aladin_align_long_bwd (the pair-list path for any dS, a dense one included).
+    """aladin_align_bwd (a long-set problem: the pair-list path for any dS, a dense one included).
     packed: Packed / (geom, xm, xe, y[, rnorm]) of the forward (None: the exact fp32 recompute); with its operands at hand the row
     step's unit vectors are as set_backward_precision() says.
     dense: the caller knows that (almost) every pair carries a gradient (sum-of-violations hinge, a gradient on S):
@@ -382,13 +367,10 @@ def _align_backward(im, s, im_len_t, s_len_t, dS, gscale=None, packed=None, pair
     Bc, T, _ = s.shape
     packed = Packed(*packed) if packed is not None else None
     have = packed is not None and packed.at_hand()
-    long = isinstance(packed.geom, LongGeom) if packed is not None else is_long(R, T, *x_tails)
-    if packed is not None:
-        geom = packed.geom
-    elif not long and x_tails != (0, 2):
+    geom = packed.geom if packed is not None else align_geometry(Bi, Bc, R, T, D, *x_tails, layout='auto')
+    long = geom.layout == _lib.LAYOUT_LONG
+    if packed is None and not long and x_tails != (0, 2):
         raise NotImplementedError('aladin_amd: the stand-alone backward entry point is the image/caption form')
-    else:
-        geom = _geometry(long, Bi, Bc, R, T, D, *x_tails, None)
     dense_flag = _lib.BWD_DENSE if (dense and not long and DENSE_BACKWARD and have and Bi * Bc >= DENSE_MIN_PAIRS) else 0
     if dense_flag and not (DENSE_ROWS_GEMM and _gemm_rows_pay(fill, R - 1 - geom.x_tail)):
         dense_flag |= _lib.BWD_DENSE_GATHER
@@ -397,15 +379,10 @@ def _align_backward(im, s, im_len_t, s_len_t, dS, gscale=None, packed=None, pair
     pk = C.byref(packed.struct()) if have else None
     flags = (_bwd_flags(packed) if have else 0) | dense_flag
     vi, vs, gi, gs = _set_view(im, im_len_t), _set_view(s, s_len_t), _grad_view(d_im), _grad_view(d_s)
-    if long:
-        ws = _workspace(lib.aladin_align_long_bwd_workspace_bytes(C.byref(geom)), im.device)
-        _lib.check(lib.aladin_align_long_bwd(C.byref(vi), C.byref(vs), C.byref(geom), pk, _ptr(dS), ld_dS, _ptr(gscale), C.byref(gi),
-                                             C.byref(gs), _ptr(ws), flags, _stream()), 'align_long_bwd')
-    else:
-        ws = _workspace(lib.aladin_align_bwd_workspace_bytes(C.byref(geom), dense_flag), im.device)
-        _lib.check(lib.aladin_align_bwd(C.byref(vi), C.byref(vs), C.byref(geom), pk, _ptr(dS), ld_dS, _ptr(gscale),
-                                        _ptr(pairs[0] if pairs else None), _ptr(pairs[1] if pairs else None),
-                                        C.byref(gi), C.byref(gs), _ptr(ws), flags, _stream()), 'align_bwd')
+    ws = _workspace(lib.aladin_align_bwd_workspace_bytes(C.byref(geom), dense_flag), im.device)
+    _lib.check(lib.aladin_align_bwd(C.byref(vi), C.byref(vs), C.byref(geom), pk, _ptr(dS), ld_dS, _ptr(gscale),
+                                    _ptr(pairs[0] if pairs else None), _ptr(pairs[1] if pairs else None),
+                                    C.byref(gi), C.byref(gs), _ptr(ws), flags, _stream()), 'align_bwd')
     return d_im, d_s
 
 
@@ -424,9 +401,7 @@ def _triplet_forward(im, s, im_len_t, s_len_t, margin, loss_out=None):
     the generic calls)."""
     Bi, R, D = im.shape
     Bc, T, _ = s.shape
-    if is_long(R, T):
-        return None
-    geom = align_geometry(Bi, Bc, R, T, D)
+    geom = align_geometry(Bi, Bc, R, T, D, layout='auto')
     if not _triplet_fused_ok(geom):
         return None
     lib = _lib.load()

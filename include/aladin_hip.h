@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ALADIN_ABI_VERSION 12
+#define ALADIN_ABI_VERSION 13
 
 /* The library is built with -fvisibility=hidden: the entry points declared here are its ONLY exports. */
 #if defined(__GNUC__)
@@ -73,7 +73,7 @@ typedef struct aladin_align_geom {
   int32_t Bi, Bc, R, T, D;      /* inputs: im (Bi,R,D), s (Bc,T,D)                              */
   int32_t Rq, Tq;               /* R-1 regions and T-3 words take part (alad/loss.py:87-88)     */
   int32_t mrows;                /* rows per image in the main operand xm: 32, 48, 64 or 96 (rows past R' repeat region 0);
-                                   round_up(R', 32) up to 512 from aladin_align_long_geometry */
+                                   ALADIN_LAYOUT_LONG: round_up(R', 32) up to 512 */
   int32_t rem;                  /* leftover regions per image (R' - mrows when positive) that go through the side GEMM: <= 8 */
   int32_t tp16;                 /* 16-word column tiles a caption needs: ceil(trows / 16)       */
   int32_t trows;                /* rows per caption in y: 16 * tp16, or 16 * tp16 - 8 = 8 / 24 / 40 (T' <= 8 / 17..24 / 33..40
@@ -85,6 +85,7 @@ typedef struct aladin_align_geom {
                                    set uses positions 1 .. N-1-tail and length len-1-tail.  Images 0
                                    (alad/loss.py:87,89), captions 2 (:88,90)                      */
   int32_t split;                /* 1: split-fp16 operands (ALADIN_PRECISION_SPLIT), Dp = 3 * round_up(D, 64) */
+  int32_t layout;               /* ALADIN_LAYOUT_TILES, _TILES_WHOLE or _LONG (below): which kernel family reads the operands */
   int64_t xm_rows, xe_rows, y_rows;            /* rows of the packed fp16 operands              */
   int64_t xm_bytes, xe_bytes, y_bytes;         /* their sizes                                   */
   int64_t e_bytes;              /* fp32 scratch for the side GEMM, xe_rows x y_rows (0 if !rem) */
@@ -113,14 +114,36 @@ typedef struct aladin_packed {
  *                           Forward only: the backward entry points reject split operands. */
 #define ALADIN_PRECISION_FP16 0
 #define ALADIN_PRECISION_SPLIT 1
-#define ALADIN_PRECISION_SPLIT_TABLE 2   /* split operands in whole 16-word caption tiles (no 24- / 40-word classes): the layout
-                                            the dense backward's arg-max table kernel reads */
+
+/* Packed layout of a geometry: the field `layout` of aladin_align_geom, which every entry point dispatches on.
+ *   ALADIN_LAYOUT_TILES        the tile classes: at most 96 scored positions on either side (R' = R - 1 - x_tail, T' = T - 1 -
+ *                              y_tail); 32 / 48 / 64 / 96 main rows + side rows, captions in 16-word tiles or the 8- / 24- /
+ *                              40-row classes (the fields of aladin_align_geom above).  0: a zero-initialised struct reads as tiles.
+ *   ALADIN_LAYOUT_TILES_WHOLE  the same with whole 16-word caption tiles only (no 8- / 24- / 40-row classes): what the dense
+ *                              backward's arg-max table kernel reads.
+ *   ALADIN_LAYOUT_LONG         long sets (csrc/align_long.hip): up to 512 positions per set -- R <= 512 and T <= 512, i.e. up to
+ *                              511 scored regions on the max side and 509 scored words on the sum side.  mrows = round_up(R', 32)
+ *                              rows per max-side sample (rows past R' repeat its first scored position), no side rows (rem 0,
+ *                              xe_bytes 0, e_bytes 0), trows = round_up(T', 16) rows per sum-side sample, cap_unit = 512 / trows
+ *                              samples per score workgroup, Bc_pad rounded to it; rnorm is [xm rows | y rows].
+ * aladin_align_pack, aladin_align_scores and aladin_align_bwd (with its workspace query) take every layout they are given a
+ * geometry of; the entry points that exist only for the tile classes (aladin_align_triplet_*, aladin_heads_small_fwd_argmax,
+ * aladin_align_pack_store_x / _y) refuse a LONG geometry before launching anything.  The score and backward entry points
+ * validate a LONG geometry by recomputation (one that aladin_align_geometry did not make: ALADIN_ERR_ARG, workspace 0); tile
+ * geometries are trusted.
+ * ALADIN_LAYOUT_AUTO is a REQUEST only: TILES when R' <= ALADIN_TILE_MAX_SCORED and T' <= ALADIN_TILE_MAX_SCORED, else LONG. */
+#define ALADIN_LAYOUT_AUTO (-1)
+#define ALADIN_LAYOUT_TILES 0
+#define ALADIN_LAYOUT_TILES_WHOLE 1
+#define ALADIN_LAYOUT_LONG 2
+#define ALADIN_TILE_MAX_SCORED 96
 
 /* Host-only: derive the packed layout.  The set on the MAX side (Bi x R) and the set on the SUM side (Bc x T) each state
  * how many trailing positions they drop: 'MrSw' = (images, x_tail 0) x (captions, y_tail 2); 'MwSr' (alad/loss.py:134-135,
  * max over words, sum over regions) = (captions, tail 2) x (images, tail 0), result transposed.  Every "image" / "caption"
- * argument below means max-side / sum-side set. */
-ALADIN_API int aladin_align_geometry(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail, int precision,
+ * argument below means max-side / sum-side set.  precision: ALADIN_PRECISION_FP16 or _SPLIT; layout: a request, ALADIN_LAYOUT_*
+ * above.  TILES / TILES_WHOLE past 96 scored positions and LONG past 512 positions per set: ALADIN_ERR_UNSUPPORTED. */
+ALADIN_API int aladin_align_geometry(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail, int precision, int layout,
                                      aladin_align_geom* out);
 
 /* L2-normalise (eps 1e-12, F.normalize), slice, length-mask and convert sets to the packed fp16 MFMA operands: the image
@@ -129,9 +152,10 @@ ALADIN_API int aladin_align_geometry(int Bi, int Bc, int R, int T, int D, int x_
 ALADIN_API int aladin_align_pack(const aladin_set* im, const aladin_set* s, const aladin_align_geom* geom,
                                  const aladin_packed* out, void* stream);
 
-/* S (Bi x Bc, row stride ldS floats) from packed operands.  e_scratch: geom->e_bytes.
+/* S (Bi x Bc, row stride ldS floats) from packed operands, any layout and both precisions; bitwise reproducible.
+ * e_scratch: geom->e_bytes (may be NULL when !geom->rem, so for every LONG geometry).
  * ALADIN_SCORES_REUSE_SIDE: e_scratch already holds the side-GEMM result of a previous call on the same operands, launch
- * the score kernel alone (used by bench.py to time the dominant kernel in isolation). */
+ * the score kernel alone (used by bench.py to time the dominant kernel in isolation); ignored without side rows. */
 #define ALADIN_SCORES_REUSE_SIDE 1
 ALADIN_API int aladin_align_scores(const aladin_packed* packed, const aladin_align_geom* geom, void* e_scratch, float* S,
                                    int64_t ldS, int flags, void* stream);
@@ -165,7 +189,12 @@ ALADIN_API int aladin_align_scores(const aladin_packed* packed, const aladin_ali
  *       P[(i,r),(c,w)] = dS[i,c] [argmax == r] generated in registers from the table (csrc/align_bwd_dense.hip), exact to
  *       ~2^-22 by hi + lo splitting (one product under ALADIN_BWD_PARTNERS_FP16) -- sums in a different order than the
  *       gather, so equal to it to rounding, not bit for bit.
- *   ALADIN_BWD_DENSE_GATHER  (with ALADIN_BWD_DENSE) keep the per-row gather as step 3: bit-identical to the list path. */
+ *   ALADIN_BWD_DENSE_GATHER  (with ALADIN_BWD_DENSE) keep the per-row gather as step 3: bit-identical to the list path.
+ * A LONG geometry takes the pair-list path for any dS, a dense one included: the non-zero pairs of dS are compacted here
+ * (`pairs` / `pair_count` are ignored, as are ALADIN_BWD_DENSE and ALADIN_BWD_DENSE_GATHER), every word's arg-max region of
+ * every listed pair is decided in fp32 from the raw rows (16-bit table entries), and one wave per output row gathers the partner
+ * rows.  ALADIN_BWD_PARTNERS_FP16 (`packed` then needs xm, y and rnorm) and ALADIN_BWD_OWN_ROW_FP16 mean what they mean above;
+ * `packed` may be NULL otherwise.  D % 4 == 0, D <= 1024. */
 #define ALADIN_BWD_PARTNERS_FP16 1
 #define ALADIN_BWD_DENSE 2
 #define ALADIN_BWD_DENSE_GATHER 4
@@ -175,33 +204,6 @@ ALADIN_API int aladin_align_bwd(const aladin_set* im, const aladin_set* s, const
                                 const aladin_packed* packed, const float* dS, int64_t ld_dS, const float* gscale,
                                 const int32_t* pairs, const int32_t* pair_count, const aladin_set_grad* d_im,
                                 const aladin_set_grad* d_s, void* workspace, int flags, void* stream);
-
-/* Long sets: more than 96 scored positions on either side (the tile classes of aladin_align_geometry stop there), up to
- * 512 positions per set -- R <= 512 and T <= 512, i.e. up to 511 scored regions on the max side and 509 scored words on the sum
- * side (csrc/align_long.hip).  aladin_align_geometry keeps its limits; shapes past them take these entry points:
- *   aladin_align_long_geometry   the packed layout: mrows = round_up(R', 32) rows per max-side sample (rows past R' repeat its
- *                                first scored position), no side rows (rem 0, xe_bytes 0, e_bytes 0), trows = round_up(T', 16)
- *                                rows per sum-side sample, cap_unit = 512 / trows samples per score workgroup, Bc_pad rounded to
- *                                it; rnorm is [xm rows | y rows].  ALADIN_PRECISION_FP16 or ALADIN_PRECISION_SPLIT; R or T past
- *                                512: ALADIN_ERR_UNSUPPORTED.  aladin_align_pack packs for this geometry as for the other one.
- *   aladin_align_long_scores     S (Bi x Bc, row stride ldS) from the packed operands, both precisions; bitwise reproducible.
- *   aladin_align_long_bwd        the backward of aladin_align_bwd for these shapes, any dS (the pair-list path also for a dense
- *                                dS): the non-zero pairs of dS are compacted, every word's arg-max region of every listed pair is
- *                                decided in fp32 from the raw rows (16-bit table entries), and one wave per output row gathers
- *                                the partner rows.  flags: ALADIN_BWD_PARTNERS_FP16 (partner rows from `packed`, which then
- *                                needs xm, y and rnorm) and ALADIN_BWD_OWN_ROW_FP16 (with it: the row's own unit vector too);
- *                                `packed` may be NULL otherwise.  D % 4 == 0, D <= 1024, fp16 operands (split is forward-only).
- *                                d_im / d_s fully written (zeros outside the alignment), no atomics.
- * Every entry point takes only a geometry of aladin_align_long_geometry (ALADIN_ERR_ARG otherwise). */
-ALADIN_API int aladin_align_long_geometry(int Bi, int Bc, int R, int T, int D, int x_tail, int y_tail, int precision,
-                                          aladin_align_geom* out);
-ALADIN_API int aladin_align_long_scores(const aladin_packed* packed, const aladin_align_geom* geom, float* S, int64_t ldS,
-                                        void* stream);
-ALADIN_API size_t aladin_align_long_bwd_workspace_bytes(const aladin_align_geom* geom);
-ALADIN_API int aladin_align_long_bwd(const aladin_set* im, const aladin_set* s, const aladin_align_geom* geom,
-                                     const aladin_packed* packed, const float* dS, int64_t ld_dS, const float* gscale,
-                                     const aladin_set_grad* d_im, const aladin_set_grad* d_s, void* workspace, int flags,
-                                     void* stream);
 
 /* The training step of AlignmentContrastiveLoss(max_violation=True, aggregation='MrSw') -- every shipped YAML,
  * alad/loss.py:79-159 through alad/alad_model.py:386 -- as ONE call per direction, so that an eager drop-in module costs one

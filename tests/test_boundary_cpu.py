@@ -86,6 +86,7 @@ def test_geometry_headline_and_edges():
     from aladin_amd import _lib, ops
     g = ops.align_geometry(256, 256, 34, 50, 768)
     assert (g.Rq, g.Tq, g.mrows, g.rem, g.tp16, g.Dp) == (33, 47, 32, 1, 3, 768)
+    assert g.layout == _lib.LAYOUT_TILES
     assert g.xm_rows == 256 * 32 and g.xe_rows == 256 and g.y_rows == 256 * 48
     g = ops.align_geometry(1000, 5000, 71, 71, 768)         # evaluation shape: 70 regions x 68 words
     assert (g.mrows, g.rem, g.tp16) == (96, 0, 6)
@@ -104,6 +105,11 @@ def test_geometry_headline_and_edges():
             assert g.trows == rows and g.tp16 == -(-rows // 16) and g.y_rows == g.Bc_pad * rows, (R_, T_, g.trows)
             assert g.cap_unit == {8: 48, 24: 16, 40: 16}[rows] if rows in (8, 24, 40) else g.trows == 16 * g.tp16
     assert ops.align_geometry(256, 256, 51, 38, 768, precision='split').trows == 40       # split operands: the same layout, K x 3
+    # whole 16-word caption tiles on request (the dense backward's arg-max table kernel): a layout, not a precision
+    whole, tiles = _lib.AlignGeom(), _lib.AlignGeom()
+    assert _lib.load().aladin_align_geometry(256, 256, 51, 38, 768, 0, 2, _lib.PRECISION_SPLIT, _lib.LAYOUT_TILES_WHOLE, whole) == 0
+    assert _lib.load().aladin_align_geometry(256, 256, 51, 38, 768, 0, 2, _lib.PRECISION_SPLIT, _lib.LAYOUT_TILES, tiles) == 0
+    assert (whole.trows, whole.layout, whole.split) == (48, _lib.LAYOUT_TILES_WHOLE, 1) and (tiles.trows, tiles.layout) == (40, _lib.LAYOUT_TILES)
     assert ops.align_geometry(9, 9, 71, 38, 64).trows == 48                              # three region tiles per image: whole tiles
     for g in (ops.align_geometry(256, 256, 34, 50, 768), ops.align_geometry(9, 9, 71, 71, 64), ops.align_geometry(9, 9, 51, 60, 64)):
         assert g.trows == 16 * g.tp16
@@ -116,6 +122,25 @@ def test_geometry_headline_and_edges():
         with pytest.raises(RuntimeError):
             ops.align_geometry(*args)
     assert _lib.load().aladin_last_error()
+
+
+def test_integration_stub_matches_the_binding():
+    """INTEGRATION.md section 3 is the ctypes stub a maintainer copies: its ABI version literals are _lib.ABI_VERSION and its Geom
+    struct lists the fields of _lib.AlignGeom in order, so the document cannot fall behind the header silently."""
+    import ctypes as C
+    from aladin_amd import _lib
+    doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+    versions = re.findall(r'aladin_version\(\) == (\d+)', doc) + re.findall(r'aladin_hip\.h, version (\d+)', doc) + \
+        re.findall(r'\nABI (\d+) has ONE entry point', doc)
+    assert len(versions) == 3 and set(versions) == {str(_lib.ABI_VERSION)}, versions
+    stub = re.search(r'class Geom\(C\.Structure\):.*?\n((?:    .*\n)+)', doc).group(1)
+    i32, i64 = re.findall(r'for n in \(([^)]*)\)', stub)
+    names = lambda txt: re.findall(r'"(\w+)"', txt)
+    fields = [(n, C.c_int32) for n in names(i32)] + [(n, C.c_int64) for n in names(i64)]
+    assert fields == list(_lib.AlignGeom._fields_)
+    # the stub's geometry call has as many arguments as the binding's signature
+    call = re.search(r'lib\.aladin_align_geometry\(([^)]*\))', doc).group(1)
+    assert len(call.split(',')) == len(_lib.SIGNATURES['aladin_align_geometry'][1])
 
 
 def test_workspace_queries():
@@ -449,6 +474,7 @@ def test_binding_matches_the_header_argument_for_argument():
                 got.append({C.c_int: 'i32', C.c_int64: 'i64', C.c_float: 'f32', C.c_size_t: 'sz'}[t])
         assert got == want, (name, got, want)
     src = open(os.path.join(ROOT, 'aladin_amd', '_lib.py')).read()
-    table = src[src.index('    sig = {'):src.index('    for name, (res, args) in sig.items():')]
+    table = src[src.index('def _signatures():'):src.index('SIGNATURES = _signatures()')]
     keys = re.findall(r"^\s+'(aladin_[a-z0-9_]+)':", table, flags=re.M)
     assert len(keys) == len(set(keys)), sorted(k for k in set(keys) if keys.count(k) > 1)
+    assert keys == _lib.SYMBOLS == list(_lib.SIGNATURES)          # one table: the names are its keys

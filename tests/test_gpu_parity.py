@@ -860,7 +860,7 @@ def test_length_bucketed_grid_in_the_swapped_orientation(eval_precision, monkeyp
 def test_long_evaluation_grid_is_one_launch(eval_precision, monkeypatch):
     """A grid whose trimmed sets are past the tile classes is never bucketed: one launch of the long-set kernels, the bits of
     ops._align_forward on the same trimmed sets."""
-    from aladin_amd import eval_grid, ops, synth
+    from aladin_amd import _lib, eval_grid, ops, synth
     im, s, il, sl = synth.alignment_batch(12, 130, 130, 64, seed=130, ragged=True, Bc=20)
     il[0], sl[0] = 120, 110                                         # the longest of each side: trimmed to 121 and 110 positions
     il, sl = [min(v, 120) for v in il], [min(v, 110) for v in sl]
@@ -877,7 +877,7 @@ def test_long_evaluation_grid_is_one_launch(eval_precision, monkeypatch):
     monkeypatch.setattr(ops, 'scores_from_packed', counting)
     a, b = T(im), T(s)
     S = ops.alignment_scores(a, b, il, sl)
-    assert len(launches) == 1 and isinstance(launches[0], ops.LongGeom) and (launches[0].R, launches[0].T) == (121, 110)
+    assert len(launches) == 1 and launches[0].layout == _lib.LAYOUT_LONG and (launches[0].R, launches[0].T) == (121, 110)
     S_ref, _ = ops._align_forward(a[:, :121], b[:, :110], ops.lengths_tensor(il, dev()), ops.lengths_tensor(sl, dev()),
                                   precision=eval_precision, norms=False)
     assert torch.equal(S, S_ref)

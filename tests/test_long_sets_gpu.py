@@ -202,7 +202,7 @@ def test_padding_across_the_old_limit_changes_nothing(mode, exact_backward):
 def test_long_kernel_agrees_with_the_tile_kernels(shape):
     """ops.LONG_PATH_FORCE: the long-set kernels on shapes the tile classes cover (R' = T' = 96 and the headline shape) against
     the tile kernels: <= 2e-6 max|S| with fp16 operands, <= 1e-6 max|S| with split operands."""
-    from aladin_amd import ops
+    from aladin_amd import _lib, ops
     Bi, Bc, R, T_, D = shape
     im, s, il, sl = ragged_batch(Bi, Bc, R, T_, D, seed=11)
     a, b = T(im), T(s)
@@ -212,7 +212,7 @@ def test_long_kernel_agrees_with_the_tile_kernels(shape):
             old = ops.LONG_PATH_FORCE
             ops.LONG_PATH_FORCE = True
             try:
-                assert isinstance(ops._scoring_geometry(Bi, Bc, R, T_, D, 0, 2, precision), ops.LongGeom)
+                assert ops.align_geometry(Bi, Bc, R, T_, D, 0, 2, precision, layout='auto').layout == _lib.LAYOUT_LONG
                 got = ops.alignment_scores(a, b, il, sl, 'MrSw', precision=precision).cpu().numpy()
             finally:
                 ops.LONG_PATH_FORCE = old

@@ -21,6 +21,9 @@ Arg-max table: the sum-of-violations step with the dense table forced, one probl
 otherwise), one case per stage of the alignment backward: the fused triplet step in the three precision modes; the
 sum-of-violations step with the GEMM and with the gather row step; a sparse gradient on the score matrix (fp16 pair kernel at
 R = 65, fp32 fallback at R = 71); a long problem; the small-batch loss heads.
+Long sets (LONG_CASES): scores past the tile classes on either side and at the 512-position limit in fp16 and split precision,
+'MwSr' (the roles swapped), the long kernels forced onto a tile-class shape (ops.LONG_PATH_FORCE: scores and gradients), and
+the hinge step of AlignmentContrastiveLoss with the hardest negative and the sum of violations in two backward precisions.
 """
 import os
 import sys
@@ -54,6 +57,9 @@ SCORE_CASES = (
 )
 # (R, T) at B = 64, D = 256 -> (mrows, rem) of the arg-max kernel's class
 ARGMAX_CASES = (((34, 50), (32, 1)), ((38, 30), (32, 5)), ((51, 38), (48, 2)), ((50, 38), (48, 1)), ((49, 38), (48, 0)), ((58, 38), (64, 0)))
+
+
+LONG_CASES = ((5, 6, 98, 50, 64), (6, 5, 34, 100, 64), (3, 3, 512, 512, 32))
 
 
 def score_body(g):
@@ -188,6 +194,51 @@ def gradient_cases(ops, synth, dev):
     return out
 
 
+def long_cases(ops, synth, dev):
+    """-> {name: tensor}: scores, losses and gradients of long-set problems (and of a tile-class shape sent to the long kernels)."""
+    from aladin_amd.loss import AlignmentContrastiveLoss
+    out = {}
+    T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+
+    def scores(tag, shape, aggregations):
+        Bi, Bc, R, Tn, D = shape
+        im, s, il, sl = synth.alignment_batch(Bi, R, Tn, D, seed=9000 + R + Tn, ragged=True, Bc=Bc)
+        il[0], sl[0] = R, Tn
+        for agg in aggregations:
+            for prec in ('fp16', 'split'):
+                with torch.no_grad():
+                    out['%s-%dx%d-R%d-T%d-D%d-%s-%s' % (tag, Bi, Bc, R, Tn, D, agg, prec)] = \
+                        ops.alignment_scores(T(im), T(s), il, sl, agg, precision=prec).cpu()
+        return im, s, il, sl
+
+    for k, shape in enumerate(LONG_CASES):
+        scores('long', shape, ('MrSw', 'MwSr') if k == 0 else ('MrSw',))
+    old = ops.LONG_PATH_FORCE
+    ops.LONG_PATH_FORCE = True
+    try:
+        im, s, il, sl = scores('forced-long', (8, 8, 34, 50, 64), ('MrSw',))
+        a, b = T(im).requires_grad_(True), T(s).requires_grad_(True)
+        loss = (ops.alignment_scores(a, b, il, sl) * T(np.random.RandomState(6).randn(8, 8).astype(np.float32))).sum()
+        loss.backward()
+        out['forced-long8/loss'], out['forced-long8/d_im'], out['forced-long8/d_s'] = loss.detach().cpu(), a.grad.cpu(), b.grad.cpu()
+    finally:
+        ops.LONG_PATH_FORCE = old
+    im, s, il, sl = synth.alignment_batch(5, 98, 50, 64, seed=9500, ragged=True)
+    try:
+        for mode in ('exact', 'fp16'):
+            ops.set_backward_precision(mode)
+            for max_violation in (True, False):
+                crit = AlignmentContrastiveLoss(margin=0.2, measure='dot', max_violation=max_violation, aggregation='MrSw')
+                a, b = T(im).requires_grad_(True), T(s).requires_grad_(True)
+                loss = crit(a, b, il, sl)
+                loss.backward()
+                tag = 'long-hinge5-%s-%s' % ('max' if max_violation else 'sum', mode)
+                out[tag + '/loss'], out[tag + '/d_im'], out[tag + '/d_s'] = loss.detach().cpu(), a.grad.cpu(), b.grad.cpu()
+    finally:
+        ops.set_backward_precision('exact')
+    return out
+
+
 def adversarial_retrieval(case, n_img, cpi, D, seed):
     """The 'bulk' and 'exact_ties' recipes of tests/test_gpu_parity.py::_adversarial_retrieval."""
     rng = np.random.default_rng(seed)
@@ -311,6 +362,7 @@ def main():
         out.update(score_cases(ops, synth, dev))
         out.update(argmax_cases(ops, synth, dev))
         out.update(gradient_cases(ops, synth, dev))
+        out.update(long_cases(ops, synth, dev))
     if group in ('retrieval', 'all'):
         out.update(retrieval_cases(ops, synth, dev))
     if group in ('eval', 'all'):
