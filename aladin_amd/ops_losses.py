@@ -203,6 +203,72 @@ def dot_scores(im, s):
     return _DotScores.apply(im, s)
 
 
+# ------------------------------------------------------------------------------------------------
+# nearest-neighbour entropy (uniformity) term
+# ------------------------------------------------------------------------------------------------
+def _nn_entropy_raw(img, cap, want_loss):
+    """aladin_nn_entropy_fwd on img (B, D) and cap (B, D) or None -> (loss or None, nn int32 (N,), dist (N,))."""
+    lib = _lib.load()
+    B, D = img.shape
+    N = B * (2 if cap is not None else 1)
+    dev = img.device
+    loss = torch.empty((), dtype=torch.float32, device=dev) if want_loss else None
+    nn = torch.empty(N, dtype=torch.int32, device=dev)
+    dist = torch.empty(N, dtype=torch.float32, device=dev)
+    ws = _workspace(lib.aladin_nn_entropy_workspace_bytes(N), dev)
+    _lib.check(lib.aladin_nn_entropy_fwd(_ptr(img), _ld(img), _ptr(cap), _ld(cap) if cap is not None else 0, B, D, _ptr(loss),
+                                         _ptr(nn), _ptr(dist), _ptr(ws), _stream()), 'nn_entropy_fwd')
+    return loss, nn, dist
+
+
+def _nn_entropy_limit(N):
+    if N > _lib.NN_ENTROPY_MAX_N:
+        raise ValueError('aladin_amd: the nearest-neighbour search covers N <= %d rows, got %d' % (_lib.NN_ENTROPY_MAX_N, N))
+
+
+class _NNEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, cap):
+        a = img if img.stride(1) == 1 else img.contiguous()
+        b = cap if cap.stride(1) == 1 else cap.contiguous()
+        loss, nn, dist = _nn_entropy_raw(a, b, True)
+        ctx.save_for_backward(a, b, nn, dist)
+        ctx.mark_non_differentiable(nn, dist)
+        return loss, nn, dist
+
+    @staticmethod
+    def backward(ctx, g, _g_nn, _g_dist):
+        a, b, nn, dist = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        d_img, d_cap = torch.empty_like(a, memory_format=torch.contiguous_format), torch.empty_like(b, memory_format=torch.contiguous_format)
+        _lib.check(_lib.load().aladin_nn_entropy_bwd(_ptr(a), _ld(a), _ptr(b), _ld(b), a.shape[0], a.shape[1], _ptr(nn), _ptr(dist),
+                                                     _ptr(g), _ptr(d_img), _ptr(d_cap), _stream()), 'nn_entropy_bwd')
+        return d_img, d_cap
+
+
+def nn_entropy_loss(img_emb, cap_emb, return_neighbours=False):
+    """-mean_i log(N * ||x_i - x_nn(i) + 1e-6||) over the N = 2 B rows of cat([img_emb, cap_emb]), nn(i) the other row of largest
+    inner product; replaces the 'entropy' term, reference alad/alad_model.py:410-421.  Ties go to the lowest index; no gradient
+    flows through the neighbour choice.  return_neighbours: also the neighbour indices, int64 (N,)."""
+    _require_gpu(img_emb, cap_emb)
+    if img_emb.dim() != 2 or img_emb.shape != cap_emb.shape or img_emb.shape[0] < 1 or img_emb.shape[1] < 1:
+        raise ValueError('aladin_amd: two non-empty (B, D) embedding matrices of equal shape expected')
+    _nn_entropy_limit(2 * img_emb.shape[0])
+    loss, nn, _ = _NNEntropy.apply(img_emb, cap_emb)
+    return (loss, nn.to(torch.int64)) if return_neighbours else loss
+
+
+def pairwise_nns_inner(x):
+    """Index of every row's nearest other row by inner product, int64 (N,); replaces pairwise_NNs_inner, reference
+    alad/alad_model.py:17-27 (diagonal set to -1, not -inf).  Ties go to the lowest index."""
+    _require_gpu(x)
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError('aladin_amd: a non-empty (N, D) matrix expected')
+    _nn_entropy_limit(x.shape[0])
+    x = x.detach()
+    return _nn_entropy_raw(x if x.stride(1) == 1 else x.contiguous(), None, False)[1].to(torch.int64)
+
+
 class _L2Norm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

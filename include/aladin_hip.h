@@ -407,6 +407,32 @@ ALADIN_API int aladin_sgemm_strided(int M, int N, int K, const float* A, int64_t
                          const float* B, int64_t b_rs, int64_t b_cs, float* C, int64_t ldc, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The 'entropy' loss term (csrc/entropy.hip): nearest-neighbour uniformity of the matching head's embeddings, reference
+ * alad/alad_model.py:17-27 (pairwise_NNs_inner) and :410-421.  Row r of the virtual N x D matrix all_emb is img[r * ld_img + d]
+ * for r < B and cap[(r - B) * ld_cap + d] otherwise, N = 2 B; cap == NULL: img alone, N = B (pairwise_NNs_inner of one matrix).
+ *   nn[i]   = argmax_j (all_emb @ all_emb.T)[i][j] with the diagonal set to -1.0f (not -inf, as the reference: a row whose other
+ *             products are all below -1 is its own neighbour), products in exact fp32 (fma chains in k order).
+ *             TIES GO TO THE LOWEST INDEX, at every level of the reduction (the reference's torch.max leaves them open).
+ *   dist[i] = || all_emb_i - all_emb_nn[i] + 1e-6f ||_2   (nn.PairwiseDistance(2): eps inside the norm)
+ *   loss    = -(1 / N) * sum_i log(N * dist[i])
+ * fwd: loss (1 float, may be NULL: neighbours and distances only), nn (N int32), dist (N floats).
+ * bwd: d_img (B x D) and d_cap (B x D, unused when cap == NULL), contiguous, WRITTEN not accumulated, from fwd's nn and dist:
+ *   with c_i = -*gscale / (N * dist[i]^2) and u_i = all_emb_i - all_emb_nn[i] + 1e-6f, row j receives c_j * u_j minus c_i * u_i of
+ *   every i with nn[i] == j in ascending i (a gather; a self-neighbour row comes out exactly 0, as autograd's).
+ *   gscale: a DEVICE scalar, the upstream gradient -- no host synchronisation.
+ * Limits: B >= 1, D >= 1 (no alignment requirement), N <= ALADIN_NN_ENTROPY_MAX_N -- the workspace holds one (max, index) per row
+ * and 64-column tile, 128 MiB there; beyond it ALADIN_ERR_UNSUPPORTED, checked before any launch.
+ * workspace: aladin_nn_entropy_workspace_bytes(N) (0 outside the limits), the caller's.  Three launches forward, one backward, all
+ * on `stream`; no allocation, no synchronisation, no atomics: deterministic and graph-capturable.
+ * ------------------------------------------------------------------------------------------- */
+#define ALADIN_NN_ENTROPY_MAX_N 32768
+ALADIN_API size_t aladin_nn_entropy_workspace_bytes(int N);
+ALADIN_API int aladin_nn_entropy_fwd(const float* img, int64_t ld_img, const float* cap, int64_t ld_cap, int B, int D, float* loss,
+                          int32_t* nn, float* dist, void* workspace, void* stream);
+ALADIN_API int aladin_nn_entropy_bwd(const float* img, int64_t ld_img, const float* cap, int64_t ld_cap, int B, int D,
+                          const int32_t* nn, const float* dist, const float* gscale, float* d_img, float* d_cap, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Retrieval similarity matrix  sim = img @ cap.T  at evaluation scale (5000 x 25000 x 768) on the
  * 16-bit MFMA path with a hi/lo fp16 split (3 MFMAs per product, ~fp32 accuracy so that ranks
  * agree with the reference; operand rows are kept [hi | lo] and one accumulator chain runs hi.hi, lo.hi, hi.lo).  Replaces ims.mm(caps.t()), reference alad/recall_auxiliary.py:30,51
