@@ -53,15 +53,20 @@ __global__ __launch_bounds__(256) void hinge_stats_kernel(const float* __restric
   int besti = 0x7fffffff, cnt = 0;
   for (int t = threadIdx.x; t < B; t += blockDim.x) {
     const float s = is_row ? S[(int64_t)q * ld + t] : S[(int64_t)t * ld + q];
-    float c = fmaxf(margin + s - diag, 0.f);              // :49 / :52
+    const float x = margin + s - diag;
+    // fmaxf drops a NaN; the reference's clamp / max / sum keep it, so a NaN cost makes the line's statistic NaN.  It rides
+    // the reductions that run anyway: as itself in the sum, as (+inf, index -1) in the arg-max, which beats a true +inf.
+    const bool nan = (x != x) && t != q;
+    float c = nan ? INFINITY : fmaxf(x, 0.f);             // :49 / :52
     if (t == q) c = 0.f;                                  // :55-60
-    if (c > best || (c == best && t < besti)) { best = c; besti = t; }
-    sum += c;
+    const int ti = nan ? -1 : t;
+    if (c > best || (c == best && ti < besti)) { best = c; besti = ti; }
+    sum += nan ? x : c;
     cnt += (c > 0.f);
   }
   if (max_violation) {
     block_argmax(best, besti, redv, redi);
-    if (threadIdx.x == 0) { val[b] = best; arg[b] = besti; }
+    if (threadIdx.x == 0) { val[b] = besti < 0 ? NAN : best; arg[b] = besti < 0 ? 0 : besti; }
   } else {
     sum = block_sum(sum, redv);
     const float fc = block_sum((float)cnt, redv);
@@ -181,7 +186,9 @@ __global__ __launch_bounds__(256) void listnet_finish_kernel(const float* __rest
     const float Pr = expf(t - r[0]) / r[1], Qr = expf(m - r[2]) / r[3];
     const float Pc = expf(t - c[0]) / c[1], Qc = expf(m - c[2]) / c[3];
     const float Wr = Pr * Qr / (Qr + eps), Wc = Pc * Qc / (Qc + eps);
-    dM[e] = k * (Qr * r[4] - Wr + Qc * c[4] - Wc);
+    // the row part and the column part each on its own: summed left to right, a part of size ~1 (P and Q saturated on the same
+    // element) rounds the other one away at 2^-25, which is all there is to the gradient where both softmaxes are one-hot
+    dM[e] = k * (fmaf(Qr, r[4], -Wr) + fmaf(Qc, c[4], -Wc));
   }
 }
 

@@ -25,16 +25,20 @@ namespace {
 __device__ __forceinline__ void hinge_vector_stats(float m, float diag, int q, int B, float margin, int max_violation, int lane,
                                                    float* out) {
   const bool live = lane < B;
-  float c = live ? fmaxf(margin + m - diag, 0.f) : 0.f;
+  const float x = margin + m - diag;
+  float c = live ? fmaxf(x, 0.f) : 0.f;
   if (lane == q) c = 0.f;
+  // fmaxf drops a NaN; the reference's clamp / max / sum keep it: a NaN cost anywhere on the line makes its statistic NaN,
+  // as in hinge_stats_kernel (losses.hip)
+  const bool nan = __ballot(live && lane != q && x != x) != 0;
   if (max_violation) {
     float best = live ? c : -1.f;
     int besti = lane;
     wave_argmax(best, besti);
-    if (lane == 0) { out[0] = best; out[1] = __int_as_float(besti); }
+    if (lane == 0) { out[0] = nan ? NAN : best; out[1] = __int_as_float(besti); }
   } else {
     const float sum = wave_sum(c), cnt = wave_sum(c > 0.f ? 1.f : 0.f);
-    if (lane == 0) { out[0] = sum; out[1] = __int_as_float((int)cnt); }
+    if (lane == 0) { out[0] = nan ? NAN : sum; out[1] = __int_as_float((int)cnt); }
   }
 }
 

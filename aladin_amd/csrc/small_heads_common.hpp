@@ -77,7 +77,7 @@ __device__ __forceinline__ void heads_small_finish_body(int vblock, int nblocks,
       const float Pr = expf(t - r[2]) / r[3], Qr = expf(m - r[4]) / r[5];
       const float Pc = expf(t - c[2]) / c[3], Qc = expf(m - c[4]) / c[5];
       const float Wr = Pr * Qr / (Qr + eps), Wc = Pc * Qc / (Qc + eps);
-      dM_listnet[e] = kk * (Qr * r[6] - Wr + Qc * c[6] - Wc);
+      dM_listnet[e] = kk * (fmaf(Qr, r[6], -Wr) + fmaf(Qc, c[6], -Wc));      // row part + column part, as listnet_finish_kernel
     }
     if ((flags & SB_ALIGN_HINGE) && (dS || pairs)) {
       const float g = in ? hinge_grad(st, 8, S, ld_s, B, i, j, margin, max_violation) : 0.f;

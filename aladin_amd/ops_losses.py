@@ -139,7 +139,7 @@ class _OrderScores(torch.autograd.Function):
         a = im if im.stride(1) == 1 else im.contiguous()
         b = s if s.stride(1) == 1 else s.contiguous()
         out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
-        _lib.check(lib.aladin_order_sim_fwd(_ptr(a), a.stride(0), _ptr(b), b.stride(0), a.shape[0], b.shape[0], a.shape[1],
+        _lib.check(lib.aladin_order_sim_fwd(_ptr(a), _ld(a), _ptr(b), _ld(b), a.shape[0], b.shape[0], a.shape[1],
                                             _ptr(out), out.stride(0), _stream()), 'order_sim_fwd')
         ctx.save_for_backward(a, b, out)
         return out
@@ -149,9 +149,10 @@ class _OrderScores(torch.autograd.Function):
         lib = _lib.load()
         a, b, out = ctx.saved_tensors
         g = g.contiguous()
-        d_im = torch.empty_like(a) if ctx.needs_input_grad[0] else None
-        d_s = torch.empty_like(b) if ctx.needs_input_grad[1] else None
-        _lib.check(lib.aladin_order_sim_bwd(_ptr(a), a.stride(0), _ptr(b), b.stride(0), a.shape[0], b.shape[0], a.shape[1],
+        # fresh row-major outputs: empty_like would keep the arbitrary row stride a single-row view reports
+        d_im = torch.empty(a.shape, dtype=torch.float32, device=a.device) if ctx.needs_input_grad[0] else None
+        d_s = torch.empty(b.shape, dtype=torch.float32, device=b.device) if ctx.needs_input_grad[1] else None
+        _lib.check(lib.aladin_order_sim_bwd(_ptr(a), _ld(a), _ptr(b), _ld(b), a.shape[0], b.shape[0], a.shape[1],
                                             _ptr(g), _ld(g), _ptr(out), out.stride(0), _ptr(d_im),
                                             d_im.stride(0) if d_im is not None else 0, _ptr(d_s),
                                             d_s.stride(0) if d_s is not None else 0, _stream()), 'order_sim_bwd')
@@ -274,7 +275,7 @@ class _L2Norm(torch.autograd.Function):
     def forward(ctx, x):
         x = x if x.stride(1) == 1 else x.contiguous()
         out = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.load().aladin_l2norm_fwd(_ptr(x), x.stride(0), x.shape[0], x.shape[1], _ptr(out), _stream()), 'l2norm_fwd')
+        _lib.check(_lib.load().aladin_l2norm_fwd(_ptr(x), _ld(x), x.shape[0], x.shape[1], _ptr(out), _stream()), 'l2norm_fwd')
         ctx.save_for_backward(x)
         return out
 
@@ -283,7 +284,7 @@ class _L2Norm(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         g = g if g.stride(1) == 1 else g.contiguous()
         dx = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.load().aladin_l2norm_bwd(_ptr(x), x.stride(0), _ptr(g), _ld(g), x.shape[0], x.shape[1], _ptr(dx), _stream()),
+        _lib.check(_lib.load().aladin_l2norm_bwd(_ptr(x), _ld(x), _ptr(g), _ld(g), x.shape[0], x.shape[1], _ptr(dx), _stream()),
                    'l2norm_bwd')
         return dx
 

@@ -260,7 +260,8 @@ ALADIN_API int aladin_normsum_bwd(const float* x, int64_t stride_b, int64_t stri
  * VSE++ hinge loss on a square score matrix -- Contrastive.compute_contrastive_loss,
  * reference alad/loss.py:42-67.  loss: 1 float.  dS (B x B, contiguous) may be NULL; it receives
  * dloss/dS (max_violation: +-1 at the hardest negatives and the diagonal, <= 3B non-zeros).
- * workspace: aladin_hinge_workspace_bytes(B).
+ * A NaN score makes the loss NaN, as the reference's clamp / max / sum do (dS is then unspecified on
+ * the rows and columns holding a NaN cost).  workspace: aladin_hinge_workspace_bytes(B).
  * ------------------------------------------------------------------------------------------- */
 ALADIN_API size_t aladin_hinge_workspace_bytes(int B);
 ALADIN_API int aladin_hinge_fwd_bwd(const float* S, int64_t ldS, int B, float margin, int max_violation,
