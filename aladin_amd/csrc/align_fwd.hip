@@ -1,15 +1,7 @@
 // Alignment scores S[i][j] = sum_w max_r <im^[i,r], s^[j,w]>  ('MrSw', reference
-// alad/loss.py:79-125) for gfx950.
+// alad/loss.py:79-125) for gfx950.  The operands are packed by pack.hip in the format of pack_rows.hpp, which folds every mask of
+// the reference into the data (zero rows, tile-filling copies of region 0): the score kernel is mask-free.
 //
-// pack kernels   fp32 sets -> L2-normalised fp16 MFMA operands.  All masking of the reference
-//                (alad/loss.py:103-116) is folded into the packed data, so the score kernel is
-//                mask-free:
-//                  * padded regions (r >= im_len-1) and padded words (w >= s_len-3) become ZERO
-//                    rows: their dot products are exactly 0, which is what masked_fill_(.., 0)
-//                    leaves in the reference before max / sum;
-//                  * rows that exist only to fill a 32-row MFMA tile are COPIES of the image's
-//                    first region (max is idempotent), never zeros: a zero would wrongly clamp
-//                    the max of an image without padded regions.
 // score kernel   one tile of whole images x whole captions per workgroup: LDS-staged fp16 MFMA GEMM (gemm_core.hpp) with regions
 //                on the MFMA row axis and words on the lane axis, so max-over-regions is an in-lane max over the accumulator
 //                registers plus one or two lane exchanges, and sum-over-words is a 16-lane reduction.  The B x B x R' x T'
@@ -38,6 +30,7 @@
 
 #include "../../include/aladin_hip.h"
 #include "gemm_core.hpp"
+#include "pack_rows.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // geometry
@@ -103,238 +96,9 @@ extern "C" int aladin_align_geometry(int Bi, int Bc, int R, int T, int D, int x_
 }
 
 // ------------------------------------------------------------------------------------------------
-// pack: one wave per destination row
-// ------------------------------------------------------------------------------------------------
-// seg: 0 = one fp16 rounding of the unit vector (Dp halfs per row);
-//      1 / 2 = split precision, max-side / sum-side row (3 * Dp0 halfs, Dp = Dp0): x^ * 2^14 = hi + lo, both fp16.
-//      The scale keeps lo out of the fp16 subnormals for every component above 2^-14 * 2^-3; what is lost
-//      below that is < 2^-39 absolute per component.  The scores come out scaled by 2^28 (a power of two:
-//      max and sum commute with it exactly) and are scaled back after the score kernel.
-#define ALADIN_SPLIT_SCALE 16384.0f
-#define ALADIN_SPLIT_UNSCALE (1.0f / (16384.0f * 16384.0f))
-// len_ptr != nullptr: the row only counts if pos < clamp(*len_ptr - 1 - tail, 0, cap) (the masks of alad/loss.py:103-116);
-// the fast path issues the row's loads BEFORE it knows (the row exists in memory either way), so that the length and the
-// row arrive together instead of one memory latency after the other.
-// inv_out (may be nullptr): receives 1 / max(|x|, 1e-12) of the row -- what the backward's normalise step divides by, so that it
-// need not read the raw fp32 row again (0 for a zero row: such a row never carries a gradient).
-__device__ __forceinline__ void pack_row(const float* __restrict__ src, half_t* __restrict__ dst, int D, int Dp,
-                                         int lane, bool vec4, int seg = 0, const int32_t* __restrict__ len_ptr = nullptr,
-                                         int pos = 0, int tail = 0, int cap = 0, float* __restrict__ inv_out = nullptr) {
-  const int width = seg ? 3 * Dp : Dp;
-  const bool fast = vec4 && !seg && D <= 1024;
-  if (src != nullptr && len_ptr != nullptr && !fast) {
-    int L = *len_ptr - 1 - tail;
-    L = L < 0 ? 0 : (L > cap ? cap : L);
-    if (pos >= L) src = nullptr;
-  }
-  // src == nullptr -> zero row
-  if (src == nullptr) {
-    for (int c = lane * 8; c < width; c += 64 * 8) *reinterpret_cast<half8*>(dst + c) = half8{0, 0, 0, 0, 0, 0, 0, 0};
-    if (inv_out && lane == 0) *inv_out = 0.f;
-    return;
-  }
-  if (fast) {
-    // the whole row in registers (<= 4 float4 per lane): one read of the source, the loads of a row all in flight at once
-    float4 v[4];
-    float ss = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int c = lane * 4 + 256 * k;
-      v[k] = c < D ? *reinterpret_cast<const float4*>(src + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    if (len_ptr != nullptr) {
-      int L = *len_ptr - 1 - tail;
-      L = L < 0 ? 0 : (L > cap ? cap : L);
-      if (pos >= L) {                                   // masked after all: a zero row
-        for (int c = lane * 8; c < width; c += 64 * 8) *reinterpret_cast<half8*>(dst + c) = half8{0, 0, 0, 0, 0, 0, 0, 0};
-        if (inv_out && lane == 0) *inv_out = 0.f;
-        return;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) ss = sumsq4(ss, v[k]);
-    ss = wave_sum(ss);
-    const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-    if (inv_out && lane == 0) *inv_out = inv;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int c = lane * 4 + 256 * k;
-      if (c < Dp) *reinterpret_cast<half4*>(dst + c) = half4{(half_t)(v[k].x * inv), (half_t)(v[k].y * inv), (half_t)(v[k].z * inv), (half_t)(v[k].w * inv)};
-    }
-    return;
-  }
-  float ss = 0.f;
-  if (vec4) {
-    for (int c = lane * 4; c < D; c += 256) {
-      const float4 v = *reinterpret_cast<const float4*>(src + c);
-      ss = sumsq4(ss, v);
-    }
-  } else {
-    for (int c = lane; c < D; c += 64) ss = fmaf(src[c], src[c], ss);
-  }
-  ss = wave_sum(ss);
-  const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);        // F.normalize eps (alad/loss.py:80-81)
-  if (inv_out && lane == 0) *inv_out = inv;
-  if (seg) {
-    half_t* d_lo = dst + (seg == 1 ? Dp : 2 * Dp);          // [hi | lo | hi]  or  [hi | hi | lo]
-    half_t* d_hi2 = dst + (seg == 1 ? 2 * Dp : Dp);
-    for (int c = lane; c < Dp; c += 64) {
-      half_t hi = (half_t)0, lo = (half_t)0;
-      if (c < D) {
-        const float v = src[c] * inv * ALADIN_SPLIT_SCALE;
-        hi = (half_t)v;
-        lo = (half_t)(v - (float)hi);
-      }
-      dst[c] = hi; d_hi2[c] = hi; d_lo[c] = lo;
-    }
-    return;
-  }
-  if (vec4) {
-    for (int c = lane * 4; c < Dp; c += 256) {
-      half4 h = {0, 0, 0, 0};
-      if (c < D) {
-        const float4 v = *reinterpret_cast<const float4*>(src + c);
-        h = half4{(half_t)(v.x * inv), (half_t)(v.y * inv), (half_t)(v.z * inv), (half_t)(v.w * inv)};
-      }
-      *reinterpret_cast<half4*>(dst + c) = h;
-    }
-  } else {
-    for (int c = lane; c < Dp; c += 64) dst[c] = (c < D) ? (half_t)(src[c] * inv) : (half_t)0;
-  }
-}
-
-__global__ __launch_bounds__(256) void pack_images_kernel(const float* __restrict__ im, int64_t sb, int64_t sr,
-                                                          const int32_t* __restrict__ im_len, int Bi, int Rq, int x_tail, int D,
-                                                          int Dp, int mrows, int rem, int64_t xm_rows,
-                                                          int64_t total_rows, half_t* __restrict__ xm,
-                                                          half_t* __restrict__ xe, int vec4, int split, float* __restrict__ rnorm) {
-  const int lane = threadIdx.x & 63;
-  const int64_t d = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (d >= total_rows) return;
-  int i, rho;
-  half_t* dst;
-  if (d < xm_rows) {
-    const int rows_per_img = mrows;
-    i = (int)(d / rows_per_img);
-    rho = (int)(d % rows_per_img);
-    if (rho >= Rq) rho = 0;                       // tile-filling copy of the first region
-    dst = xm + d * Dp;
-  } else {
-    i = (int)((d - xm_rows) / rem);
-    rho = mrows + (int)((d - xm_rows) % rem);     // the leftover region(s)
-    dst = xe + (d - xm_rows) * Dp;
-  }
-  const float* src = nullptr;
-  if (i < Bi) {
-    int Li = im_len[i] - 1 - x_tail;              // alad/loss.py:89
-    Li = Li < 0 ? 0 : (Li > Rq ? Rq : Li);
-    if (rho < Li) src = im + i * sb + (int64_t)(rho + 1) * sr;     // region 0 dropped (alad/loss.py:87)
-  }
-  pack_row(src, dst, D, split ? Dp / 3 : Dp, lane, vec4 != 0, split ? 1 : 0, nullptr, 0, 0, 0, rnorm ? rnorm + d : nullptr);      // rnorm: [xm rows | xe rows | y rows]
-}
-
-__global__ __launch_bounds__(256) void pack_captions_kernel(const float* __restrict__ s, int64_t sb, int64_t st,
-                                                            const int32_t* __restrict__ s_len, int Bc, int Tq, int y_tail, int D,
-                                                            int Dp, int tpad, int64_t total_rows,
-                                                            half_t* __restrict__ y, int vec4, int split, float* __restrict__ rnorm_y) {
-  const int lane = threadIdx.x & 63;
-  const int64_t d = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (d >= total_rows) return;
-  const int j = (int)(d / tpad), w = (int)(d % tpad);
-  const float* src = nullptr;
-  if (j < Bc) {
-    int Lj = s_len[j] - 1 - y_tail;               // alad/loss.py:90
-    Lj = Lj < 0 ? 0 : (Lj > Tq ? Tq : Lj);
-    if (w < Lj) src = s + j * sb + (int64_t)(w + 1) * st;          // token 0 dropped (alad/loss.py:88)
-  }
-  pack_row(src, y + d * Dp, D, split ? Dp / 3 : Dp, lane, vec4 != 0, split ? 2 : 0, nullptr, 0, 0, 0, rnorm_y ? rnorm_y + d : nullptr);
-}
-
-// both operand sets in one launch (rows [0, img_rows) -> images, the rest -> captions)
-__global__ __launch_bounds__(256) void pack_both_kernel(const float* __restrict__ im, int64_t isb, int64_t isr,
-                                                        const int32_t* __restrict__ im_len, const float* __restrict__ s,
-                                                        int64_t ssb, int64_t sst, const int32_t* __restrict__ s_len, int Bi,
-                                                        int Bc, int Rq, int Tq, int x_tail, int y_tail, int D, int Dp, int mrows, int rem, int64_t xm_rows,
-                                                        int64_t img_rows, int64_t total_rows, int tpad,
-                                                        half_t* __restrict__ xm, half_t* __restrict__ xe,
-                                                        half_t* __restrict__ y, int vec_i, int vec_s, int split, float* __restrict__ rnorm) {
-  const int lane = threadIdx.x & 63;
-  const int64_t d = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (d >= total_rows) return;
-  const float* src = nullptr;
-  const int32_t* len_ptr = nullptr;
-  int pos = 0, tail = 0, cap = 0;
-  half_t* dst;
-  bool vec;
-  int seg = 0;
-  if (d < img_rows) {
-    seg = split ? 1 : 0;
-    int i, rho;
-    if (d < xm_rows) {
-      const int rows_per_img = mrows;
-      i = (int)(d / rows_per_img);
-      rho = (int)(d % rows_per_img);
-      if (rho >= Rq) rho = 0;
-      dst = xm + d * Dp;
-    } else {
-      i = (int)((d - xm_rows) / rem);
-      rho = mrows + (int)((d - xm_rows) % rem);
-      dst = xe + (d - xm_rows) * Dp;
-    }
-    if (i < Bi && rho < Rq) { src = im + i * isb + (int64_t)(rho + 1) * isr; len_ptr = im_len + i; pos = rho; tail = x_tail; cap = Rq; }
-    vec = vec_i != 0;
-  } else {
-    const int64_t q = d - img_rows;
-    const int j = (int)(q / tpad), w = (int)(q % tpad);
-    if (j < Bc && w < Tq) { src = s + j * ssb + (int64_t)(w + 1) * sst; len_ptr = s_len + j; pos = w; tail = y_tail; cap = Tq; }
-    dst = y + q * Dp;
-    vec = vec_s != 0;
-    seg = split ? 2 : 0;
-  }
-  pack_row(src, dst, D, split ? Dp / 3 : Dp, lane, vec, seg, len_ptr, pos, tail, cap, rnorm ? rnorm + d : nullptr);          // d runs over [xm | xe | y] rows
-}
-
-static int is_vec4_ok(const void* p, int64_t s0, int64_t s1, int D) {
-  return (D % 4 == 0) && (s0 % 4 == 0) && (s1 % 4 == 0) && (((uintptr_t)p & 15) == 0);
-}
-
-static int set_ok(const aladin_set* v) { return v && v->data && v->len; }
-
-// both sets in ONE launch when both are given (rows [0, img_rows) -> images, the rest -> captions)
-int aladin_internal_pack(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out, hipStream_t st) {
-  if (!g || !out || (!im && !s)) { aladin_set_error("align_pack: null argument"); return ALADIN_ERR_ARG; }
-  if ((im && (!set_ok(im) || !out->xm || (g->rem && !out->xe))) || (s && (!set_ok(s) || !out->y))) { aladin_set_error("align_pack: null argument"); return ALADIN_ERR_ARG; }
-  const int64_t img_rows = g->xm_rows + g->xe_rows;
-  const int rem1 = g->rem > 0 ? g->rem : 1;
-  if (im && s) {
-    const int64_t total = img_rows + g->y_rows;
-    hipLaunchKernelGGL(pack_both_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, st, im->data, im->stride_b, im->stride_r, im->len,
-                       s->data, s->stride_b, s->stride_r, s->len, g->Bi, g->Bc, g->Rq, g->Tq, g->x_tail, g->y_tail, g->D, g->Dp, g->mrows, rem1,
-                       g->xm_rows, img_rows, total, g->trows, (half_t*)out->xm, (half_t*)out->xe, (half_t*)out->y,
-                       is_vec4_ok(im->data, im->stride_b, im->stride_r, g->D), is_vec4_ok(s->data, s->stride_b, s->stride_r, g->D), g->split, out->rnorm);
-    return aladin_check_launch("pack_both_kernel");
-  }
-  if (im) {
-    hipLaunchKernelGGL(pack_images_kernel, dim3((unsigned)((img_rows + 3) / 4)), dim3(256), 0, st, im->data, im->stride_b, im->stride_r, im->len,
-                       g->Bi, g->Rq, g->x_tail, g->D, g->Dp, g->mrows, rem1, g->xm_rows, img_rows, (half_t*)out->xm, (half_t*)out->xe,
-                       is_vec4_ok(im->data, im->stride_b, im->stride_r, g->D), g->split, out->rnorm);
-    return aladin_check_launch("pack_images_kernel");
-  }
-  hipLaunchKernelGGL(pack_captions_kernel, dim3((unsigned)((g->y_rows + 3) / 4)), dim3(256), 0, st, s->data, s->stride_b, s->stride_r, s->len,
-                     g->Bc, g->Tq, g->y_tail, g->D, g->Dp, g->trows, g->y_rows, (half_t*)out->y,
-                     is_vec4_ok(s->data, s->stride_b, s->stride_r, g->D), g->split, out->rnorm ? out->rnorm + img_rows : nullptr);
-  return aladin_check_launch("pack_captions_kernel");
-}
-
-extern "C" int aladin_align_pack(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out,
-                                 void* stream) {
-  return aladin_internal_pack(im, s, g, out, (hipStream_t)stream);
-}
-
-// ------------------------------------------------------------------------------------------------
 // side GEMM: E[i][col] = <last region of image i, word col>   (fp32, xe_rows x y_rows)
 // ------------------------------------------------------------------------------------------------
-// one workgroup tile of E (tile index bid); shared by align_side_gemm_kernel and align_side_pack_kernel (end of the file)
+// one workgroup tile of E (tile index bid); shared by align_side_gemm_kernel and align_side_pack_kernel (below)
 template <int NT, int SWM, int NS>
 __device__ __forceinline__ void side_gemm_tile(const half_t* __restrict__ xe, const half_t* __restrict__ y, float* __restrict__ E,
                                                int64_t ldE, int64_t ldk, int ktiles, int n_nblk, unsigned bid) {
@@ -368,6 +132,81 @@ __global__ __launch_bounds__(256) void align_side_gemm_kernel(const half_t* __re
                                                               int ktiles, int n_nblk) {
   side_gemm_tile<NT, SWM, NS>(xe, y, E, ldE, ldk, ktiles, n_nblk, blockIdx.x);
 }
+
+// ------------------------------------------------------------------------------------------------
+// triplet forward prologue: [side GEMM tiles | blocks that pack the main image rows] in one launch (side_packs_main)
+// ------------------------------------------------------------------------------------------------
+static const int MAIN_PACK_ROWS = 8;        // rows a wave of a pack block has in flight
+struct MainPack {
+  const float* im; int64_t sb, sr; const int32_t* len;      // the raw image set
+  int Bi, Rq, x_tail, D, Dp, mrows;
+  int64_t xm_rows;
+  half_t* xm; float* rnorm;                                 // rnorm may be nullptr
+};
+
+// Rows [0, xm_rows) of the main operand, MAIN_PACK_ROWS at a time per wave: wave w of n_waves takes the batches w, w + n_waves, ...
+// The encoder's fp16 whole-row-in-registers form for each row (pack_rows.hpp: the bits pack_rows_kernel gives these rows), but the
+// loads of all the batch's rows are issued before the first row is reduced.
+__device__ __forceinline__ void pack_main_rows(const MainPack& m, int w, int n_waves) {
+  constexpr int RB = MAIN_PACK_ROWS;
+  const int lane = threadIdx.x & 63;
+  for (int64_t d0 = (int64_t)w * RB; d0 < m.xm_rows; d0 += (int64_t)n_waves * RB) {
+    const int i = (int)(d0 / m.mrows), k0 = (int)(d0 % m.mrows);        // mrows % RB == 0: one image per batch
+    const int L = i < m.Bi ? scored_len(m.len[i], m.x_tail, m.Rq) : 0;  // regions of image i that count (alad/loss.py:89)
+    float4 v[RB][4];
+    int rho[RB];
+    // a row of an image of the batch exists in memory whether its length masks it or not; an image that pads the batch has no columns
+#pragma unroll
+    for (int j = 0; j < RB; ++j) {
+      rho[j] = main_row_region(k0 + j, m.Rq);
+      load_row_regs(v[j], m.im + i * m.sb + (int64_t)(rho[j] + 1) * m.sr, i < m.Bi ? m.D : 0, lane);      // region 0 dropped (alad/loss.py:87)
+    }
+#pragma unroll
+    for (int j = 0; j < RB; ++j) {
+      half_t* dst = m.xm + (d0 + j) * m.Dp;
+      float* slot = m.rnorm ? m.rnorm + d0 + j : nullptr;
+      if (rho[j] >= L) {                         // masked region, or an image that pads the batch: a zero row
+        write_zero_row(dst, m.Dp, lane);
+        write_rnorm(slot, 0.f, lane);
+        continue;
+      }
+      const float inv = inv_norm_regs(v[j]);
+      write_rnorm(slot, inv, lane);
+      write_fp16_regs(dst, v[j], inv, m.Dp, lane);
+    }
+  }
+}
+
+// Grid [n_side side tiles | pack blocks].  No block reads what another block of the launch writes: the side tiles read xe and y
+// (packed by the launch before) and write E; the pack blocks read the raw images and write xm and its rnorm entries.
+// Whether the two overlap or merely run one after the other is decided by two things:
+//   * few, fat pack blocks.  Dynamic LDS is per launch, so a pack block reserves the side tile's 64-120 KB as well and at most two
+//     blocks share a CU; thousands of four-row blocks (pack_rows_kernel's shape) would leave HBM a handful of waves per CU.  So:
+//     about one pack block per CU, each of its four waves with the loads of MAIN_PACK_ROWS rows in flight before it reduces any
+//     (8 rows x 3 float4 a lane at D = 768: 96 VGPRs, ~96 KB in flight per CU), looping over batches when there are more rows;
+//   * side tiles first in block order: they are dispatched first and set the length of the launch, and the pack blocks fill the
+//     second slot of each CU (or the CUs a small grid of three-stage tiles leaves empty).
+// Measured at B = 256, R = 34, T = 50, D = 768 (DESIGN.md 4.2): the launch takes 15.2 us against the side GEMM's 11.8 alone, for
+// 5.3 us of packing taken out of the launch before.  Half as many pack blocks with two batches each, pack blocks first in block
+// order, four rows in flight, a raised wave priority for the side tiles, nontemporal loads and stores: none was faster.
+template <int NT, int SWM, int NS>
+__global__ __launch_bounds__(256) void align_side_pack_kernel(const half_t* __restrict__ xe, const half_t* __restrict__ y,
+                                                              float* __restrict__ E, int64_t ldE, int64_t ldk, int ktiles,
+                                                              int n_nblk, int n_side, MainPack mp) {
+  if ((int)blockIdx.x < n_side) {
+    side_gemm_tile<NT, SWM, NS>(xe, y, E, ldE, ldk, ktiles, n_nblk, blockIdx.x);
+    return;
+  }
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  pack_main_rows(mp, ((int)blockIdx.x - n_side) * 4 + wave, ((int)gridDim.x - n_side) * 4);
+}
+
+// Named first among the kernels of this file on purpose.  The score and arg-max kernels are sensitive to WHERE they lie in the code
+// object (DESIGN_HISTORY.md, "Alignment backward: plain stages ..." and "Packed operands: one row map ..."): when the pack kernels
+// left this file for pack.hip every kernel behind them moved up by 0x3900 bytes and the headline step lost 0.7 %.  This
+// instantiation is 0x3900 bytes long; emitted here, ahead of the others, it puts each of them back at its old address.  It is one
+// of the twelve that aladin_internal_side_with_main_pack (end of the file) launches anyway -- no kernel and no byte is added.
+template __global__ void align_side_pack_kernel<3, 2, 2>(const half_t*, const half_t*, float*, int64_t, int64_t, int, int, int, MainPack);
 
 // Diagnostic build only (the PROBE instantiation of align_scores16_kernel): per-workgroup shader-clock and 100 MHz real-time
 // deltas around the main loop -> in-kernel clock = d(memtime)/d(memrealtime) * 100 MHz.
@@ -768,15 +607,15 @@ __device__ __forceinline__ void argmax16_epilogue(f32x4 (&acc)[Cfg::RT16][Cfg::C
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     Lc[c] = 0;
-    if (cap0 + c < Bc) { int l = s_len[cap0 + c] - 1 - y_tail; Lc[c] = l < 0 ? 0 : (l > Tq ? Tq : l); }
+    if (cap0 + c < Bc) Lc[c] = scored_len(s_len[cap0 + c], y_tail, Tq);
   }
 #pragma unroll
   for (int i0 = 0; i0 < NI; i0 += 2) {
     // regions that count of the pair's images A and B (wave-uniform), and of the one this lane finishes
     const int img_a = (mb * Cfg::WGM + wm) * NI + i0;
     int Li_a = 0, Li_b = 0;
-    if (img_a < Bi) { Li_a = im_len[img_a] - 1 - x_tail; Li_a = Li_a < 0 ? 0 : (Li_a > Rq ? Rq : Li_a); }
-    if (img_a + 1 < Bi) { Li_b = im_len[img_a + 1] - 1 - x_tail; Li_b = Li_b < 0 ? 0 : (Li_b > Rq ? Rq : Li_b); }
+    if (img_a < Bi) Li_a = scored_len(im_len[img_a], x_tail, Rq);
+    if (img_a + 1 < Bi) Li_b = scored_len(im_len[img_a + 1], x_tail, Rq);
     const int img = img_a + half, Li = half ? Li_b : Li_a;
     const float* e = HAS_E ? E + (int64_t)img * rem * ldE + (int64_t)nb * Cfg::BN + wn * Cfg::WCOLS + l4 : nullptr;
     // region r with accumulator or side value v, of an image with L valid regions, as a candidate
@@ -1011,13 +850,12 @@ static SideCfg select_side(const aladin_align_geom* g) {
 }
 
 // The triplet forward's prologue (aladin_align_triplet_fwd): pack [xe | y], then ONE launch of [side tiles | blocks that pack xm]
-// (align_side_pack_kernel, end of the file) instead of pack everything, then the side GEMM.  xm is first read by the score kernel,
+// (align_side_pack_kernel, beside the side GEMM above) instead of pack everything, then the side GEMM.  xm is first read by the score kernel,
 // so nothing orders its packing before the side GEMM; the side tiles are bound by their L2 -> LDS fill, the packing by HBM.
 // Every class with side rows takes it: 32 and 48 main rows (65 regions = 64 + 1 is not a class of the pair kernel), rem 1..8, all
 // caption classes -- the side tile is select_side's, whatever it is.  Kept in the old order: problems without side rows (there
 // is no launch to pack beside), split precision, and image views that float4 loads cannot address (the batched packer has only
-// pack_row's whole-row-in-registers path: D % 4 == 0, D <= 1024, 16-byte aligned rows).
-static const int MAIN_PACK_ROWS = 8;        // rows a wave of a pack block has in flight
+// the encoder's whole-row-in-registers form: D % 4 == 0, D <= 1024, 16-byte aligned rows).
 static bool side_packs_main(const aladin_set* im, const aladin_align_geom* g) {
   return g->rem > 0 && !g->split && g->D <= 1024 && is_vec4_ok(im->data, im->stride_b, im->stride_r, g->D) &&
          g->mrows % MAIN_PACK_ROWS == 0;      // a batch of rows never leaves its image
@@ -1192,95 +1030,9 @@ extern "C" int aladin_align_scores(const aladin_packed* p, const aladin_align_ge
   return aladin_internal_scores(p->xm, p->xe, p->y, g, e_scratch, S, ldS, flags, stream);
 }
 
-// ------------------------------------------------------------------------------------------------
-// triplet forward prologue: [side GEMM tiles | blocks that pack the main image rows] in one launch (side_packs_main)
-// ------------------------------------------------------------------------------------------------
-struct MainPack {
-  const float* im; int64_t sb, sr; const int32_t* len;      // the raw image set
-  int Bi, Rq, x_tail, D, Dp, mrows;
-  int64_t xm_rows;
-  half_t* xm; float* rnorm;                                 // rnorm may be nullptr
-};
-
-// Rows [0, xm_rows) of the main operand, MAIN_PACK_ROWS at a time per wave: wave w of n_waves takes the batches w, w + n_waves, ...
-// pack_row's fp16 whole-row path for each row -- same loads, same sumsq4 chain over the four float4 of a lane, wave_sum,
-// 1 / max(sqrt, 1e-12), one rounding per element, zero rows and the tile-filling copies of region 0 as pack_both_kernel places
-// them -- but the loads of all the batch's rows are issued before the first row is reduced.
-__device__ __forceinline__ void pack_main_rows(const MainPack& m, int w, int n_waves) {
-  constexpr int RB = MAIN_PACK_ROWS;
-  const int lane = threadIdx.x & 63;
-  for (int64_t d0 = (int64_t)w * RB; d0 < m.xm_rows; d0 += (int64_t)n_waves * RB) {
-    const int i = (int)(d0 / m.mrows), rho0 = (int)(d0 % m.mrows);      // mrows % RB == 0: one image per batch
-    int L = 0;                                                          // regions of image i that count (alad/loss.py:89)
-    if (i < m.Bi) {
-      L = m.len[i] - 1 - m.x_tail;
-      L = L < 0 ? 0 : (L > m.Rq ? m.Rq : L);
-    }
-    float4 v[RB][4];
-#pragma unroll
-    for (int j = 0; j < RB; ++j) {
-      int rho = rho0 + j;
-      if (rho >= m.Rq) rho = 0;                                         // tile-filling copy of the first region
-      const float* src = m.im + i * m.sb + (int64_t)(rho + 1) * m.sr;   // region 0 dropped (alad/loss.py:87)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int c = lane * 4 + 256 * k;
-        // a row of an image of the batch exists in memory whether its length masks it or not
-        v[j][k] = (i < m.Bi && c < m.D) ? *reinterpret_cast<const float4*>(src + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < RB; ++j) {
-      int rho = rho0 + j;
-      if (rho >= m.Rq) rho = 0;
-      half_t* dst = m.xm + (d0 + j) * m.Dp;
-      if (rho >= L) {                                                   // masked region, or an image that pads the batch: a zero row
-        for (int c = lane * 8; c < m.Dp; c += 64 * 8) *reinterpret_cast<half8*>(dst + c) = half8{0, 0, 0, 0, 0, 0, 0, 0};
-        if (m.rnorm && lane == 0) m.rnorm[d0 + j] = 0.f;
-        continue;
-      }
-      float ss = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ss = sumsq4(ss, v[j][k]);
-      ss = wave_sum(ss);
-      const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-      if (m.rnorm && lane == 0) m.rnorm[d0 + j] = inv;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int c = lane * 4 + 256 * k;
-        if (c < m.Dp) *reinterpret_cast<half4*>(dst + c) = half4{(half_t)(v[j][k].x * inv), (half_t)(v[j][k].y * inv), (half_t)(v[j][k].z * inv), (half_t)(v[j][k].w * inv)};
-      }
-    }
-  }
-}
-
-// Grid [n_side side tiles | pack blocks].  No block reads what another block of the launch writes: the side tiles read xe and y
-// (packed by the launch before) and write E; the pack blocks read the raw images and write xm and its rnorm entries.
-// Whether the two overlap or merely run one after the other is decided by two things:
-//   * few, fat pack blocks.  Dynamic LDS is per launch, so a pack block reserves the side tile's 64-120 KB as well and at most two
-//     blocks share a CU; thousands of four-row blocks (pack_both_kernel's shape) would leave HBM a handful of waves per CU.  So:
-//     about one pack block per CU, each of its four waves with the loads of MAIN_PACK_ROWS rows in flight before it reduces any
-//     (8 rows x 3 float4 a lane at D = 768: 96 VGPRs, ~96 KB in flight per CU), looping over batches when there are more rows;
-//   * side tiles first in block order: they are dispatched first and set the length of the launch, and the pack blocks fill the
-//     second slot of each CU (or the CUs a small grid of three-stage tiles leaves empty).
-// Measured at B = 256, R = 34, T = 50, D = 768 (DESIGN.md 4.2): the launch takes 15.2 us against the side GEMM's 11.8 alone, for
-// 5.3 us of packing taken out of the launch before.  Half as many pack blocks with two batches each, pack blocks first in block
-// order, four rows in flight, a raised wave priority for the side tiles, nontemporal loads and stores: none was faster.
-template <int NT, int SWM, int NS>
-__global__ __launch_bounds__(256) void align_side_pack_kernel(const half_t* __restrict__ xe, const half_t* __restrict__ y,
-                                                              float* __restrict__ E, int64_t ldE, int64_t ldk, int ktiles,
-                                                              int n_nblk, int n_side, MainPack mp) {
-  if ((int)blockIdx.x < n_side) {
-    side_gemm_tile<NT, SWM, NS>(xe, y, E, ldE, ldk, ktiles, n_nblk, blockIdx.x);
-    return;
-  }
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  pack_main_rows(mp, ((int)blockIdx.x - n_side) * 4 + wave, ((int)gridDim.x - n_side) * 4);
-}
-
 static const int MAIN_PACK_BLOCKS = 256;      // one per CU of the MI355X
 
-static int check_prologue(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out) {
+int aladin_internal_check_prologue(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out) {
   if (!g || !out || !set_ok(im) || !set_ok(s) || !out->xm || !out->xe || !out->y) { aladin_set_error("align_pack: null argument"); return ALADIN_ERR_ARG; }
   if (!side_packs_main(im, g)) { aladin_set_error("align_pack: not a problem whose side launch packs the main rows"); return ALADIN_ERR_UNSUPPORTED; }
   return ALADIN_OK;
@@ -1288,24 +1040,10 @@ static int check_prologue(const aladin_set* im, const aladin_set* s, const aladi
 
 bool aladin_internal_side_packs_main(const aladin_set* im, const aladin_align_geom* g) { return set_ok(im) && g && side_packs_main(im, g); }
 
-// rows [xm_rows, xm_rows + xe_rows + y_rows) of the [xm | xe | y] row space: pack_both_kernel on the same problem without its
-// main rows (row 0 of the launch is the first side row), so xe, y and their rnorm entries get the bits aladin_internal_pack gives
-int aladin_internal_pack_side_operands(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out,
-                                       hipStream_t st) {
-  if (int rc = check_prologue(im, s, g, out)) return rc;
-  const int64_t total = g->xe_rows + g->y_rows;
-  hipLaunchKernelGGL(pack_both_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, st, im->data, im->stride_b, im->stride_r, im->len,
-                     s->data, s->stride_b, s->stride_r, s->len, g->Bi, g->Bc, g->Rq, g->Tq, g->x_tail, g->y_tail, g->D, g->Dp, g->mrows, g->rem,
-                     (int64_t)0, g->xe_rows, total, g->trows, (half_t*)out->xm, (half_t*)out->xe, (half_t*)out->y,
-                     is_vec4_ok(im->data, im->stride_b, im->stride_r, g->D), is_vec4_ok(s->data, s->stride_b, s->stride_r, g->D), 0,
-                     out->rnorm ? out->rnorm + g->xm_rows : nullptr);
-  return aladin_check_launch("pack_both_kernel");
-}
-
 // the side GEMM of packed xe and y into E, with the main rows of `im` packed by the blocks behind its tiles
 int aladin_internal_side_with_main_pack(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out,
                                         float* E, hipStream_t st) {
-  if (int rc = check_prologue(im, s, g, out)) return rc;
+  if (int rc = aladin_internal_check_prologue(im, s, g, out)) return rc;
   if (!E) { aladin_set_error("align_side_pack: null side scratch"); return ALADIN_ERR_ARG; }
   const MainPack mp = {im->data, im->stride_b, im->stride_r, im->len, g->Bi, g->Rq, g->x_tail, g->D, g->Dp, g->mrows, g->xm_rows,
                        (half_t*)out->xm, out->rnorm};

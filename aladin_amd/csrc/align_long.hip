@@ -3,9 +3,9 @@
 // (32 / 48 / 64 / 96 region rows, a caption inside one 96-column strip) are the limit of those kernels; this file holds the
 // path beside them, and nothing the shorter shapes launch lives here.
 //
-// packing        the packers of align_fwd.hip (aladin_align_pack) on an ALADIN_LAYOUT_LONG geometry: mrows =
+// packing        the pack kernel of pack.hip (aladin_align_pack) on an ALADIN_LAYOUT_LONG geometry: mrows =
 //                round_up(R', 32) rows per max-side sample (rows past R' repeat position 1: max is idempotent), no side rows,
-//                trows = round_up(T', 16) rows per sum-side sample; the masking conventions of align_fwd.hip carry over
+//                trows = round_up(T', 16) rows per sum-side sample; the masking conventions of pack_rows.hpp carry over
 //                (masked positions are zero rows, so the zero fill takes part in the max of a shorter sample).
 // score kernel   one workgroup = one max-side sample x cap_unit whole sum-side samples (<= 512 columns, 32 column tiles of
 //                16 words over 4 waves).  A wave walks ALL 32-row region tiles of its sample with v_mfma_f32_16x16x32_f16,
@@ -149,7 +149,7 @@ int aladin_internal_long_scores(const aladin_packed* p, const aladin_align_geom*
   if (!p || !p->xm || !p->y || !S) { aladin_set_error("align_scores: null argument"); return ALADIN_ERR_ARG; }
   if (!long_geom_ok(g)) { aladin_set_error("align_scores: not a long-set geometry of aladin_align_geometry"); return ALADIN_ERR_ARG; }
   if (ldS < g->Bc) { aladin_set_error("align_scores: ldS %lld < Bc %d", (long long)ldS, g->Bc); return ALADIN_ERR_ARG; }
-  const float scale = g->split ? 1.0f / (16384.0f * 16384.0f) : 1.0f;       // split operands carry 2^14 each (align_fwd.hip)
+  const float scale = g->split ? ALADIN_SPLIT_UNSCALE : 1.0f;       // split operands carry 2^14 each
   hipLaunchKernelGGL(long_scores_kernel, dim3((unsigned)(g->Bc_pad / g->cap_unit), (unsigned)g->Bi), dim3(256), 0, (hipStream_t)stream,
                      (const half_t*)p->xm, (const half_t*)p->y, g->mrows, g->trows, g->Dp, g->Bc, g->cap_unit, S, ldS, scale);
   return aladin_check_launch("long_scores_kernel");

@@ -5,6 +5,7 @@
 #pragma once
 #include "../../include/aladin_hip.h"
 #include "common.hpp"
+#include "pack_rows.hpp"      // set_ok
 
 // One alignment-backward problem, as every host stage sees it.
 struct BwdProblem {
@@ -15,7 +16,6 @@ struct BwdProblem {
   hipStream_t st;
 };
 
-static inline bool set_ok(const aladin_set* v) { return v && v->data && v->len; }
 static inline bool grad_ok(const aladin_set_grad* v) { return v && v->data && v->stride_b >= 1 && v->stride_r >= 1; }
 
 // align_bwd.hip: zero the workspace's counter block and list the non-zero pairs of dS (bwd_compact_kernel); `entry` names the

@@ -26,13 +26,15 @@ int aladin_reserve_lds(const void* kernel, int bytes, unsigned long long* done, 
 struct aladin_align_geom;
 struct aladin_set;
 struct aladin_packed;
-// align_fwd.hip: arg-max table of every pair from the split-precision tile kernel (see there)
+// pack.hip: rows of the [xm | xe | y] row space from the fp32 sets (all of them; [xe | y] for the triplet prologue)
 int aladin_internal_pack(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out, hipStream_t st);
+int aladin_internal_pack_side_operands(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out, hipStream_t st);
+// align_fwd.hip: scores of packed operands; the arg-max table of every pair from the split-precision tile kernel (see there)
 int aladin_internal_scores(const void* xm, const void* xe, const void* y, const aladin_align_geom* g, void* e_scratch, float* S,
                            int64_t ldS, int flags, void* stream);
 // align_fwd.hip: the triplet forward's prologue where the side GEMM launch also packs the main image rows (side_packs_main there)
 bool aladin_internal_side_packs_main(const aladin_set* im, const aladin_align_geom* g);
-int aladin_internal_pack_side_operands(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out, hipStream_t st);
+int aladin_internal_check_prologue(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out);
 int aladin_internal_side_with_main_pack(const aladin_set* im, const aladin_set* s, const aladin_align_geom* g, const aladin_packed* out, float* E,
                                         hipStream_t st);
 int aladin_internal_align_argmax(const aladin_align_geom* g, const void* xm, const void* xe, const void* y, float* E,

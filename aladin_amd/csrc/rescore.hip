@@ -27,13 +27,13 @@
 // the arg-max the score throws away -- per word the best region, per region the best word (rescore_map_epilogue).
 #include "../../include/aladin_hip.h"
 
+#include "pack_rows.hpp"
 #include "sim_common.hpp"
 
 constexpr int RESCORE_MAX_K = 256;
 constexpr int RESCORE_MAX_COUNT = 96;                     // the tile classes' limit: six 16-row tiles per side
 constexpr int RESCORE_TILES = RESCORE_MAX_COUNT / 16;
 constexpr int RESCORE_LDS_LIMIT = 160 * 1024;
-constexpr float RESCORE_SPLIT_UNSCALE = 1.0f / (16384.0f * 16384.0f);      // split rows carry 2^14 each (store.hip, align_fwd.hip)
 
 struct RescoreSide {
   const half_t* rows;
@@ -91,7 +91,7 @@ __device__ __forceinline__ void rescore_map_epilogue(const f32x4 (&acc)[RESCORE_
   if (slot >= k) return;
   const int64_t pair = (int64_t)q * k + slot;
   const int row0 = 4 * (lane >> 4), col0 = lane & 15;
-  const float unscale = split ? RESCORE_SPLIT_UNSCALE : 1.0f;                    // exact: a power of two
+  const float unscale = split ? ALADIN_SPLIT_UNSCALE : 1.0f;                    // exact: a power of two
   int32_t* const w_idx = o.word_region ? o.word_region + pair * o.word_ld : nullptr;
   float* const w_cos = o.word_region ? o.word_cos + pair * o.word_ld : nullptr;
   int32_t* const r_idx = o.region_word ? o.region_word + pair * o.region_ld : nullptr;
@@ -135,7 +135,7 @@ __device__ __forceinline__ void rescore_map_epilogue(const f32x4 (&acc)[RESCORE_
         w_cos[w] = v * unscale;
       }
     }
-    if (split) total *= RESCORE_SPLIT_UNSCALE;
+    if (split) total *= ALADIN_SPLIT_UNSCALE;
     if (o.score && lane == 0) o.score[pair] = total;
   }
 
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(512) void rescore_kernel(RescoreSide x, RescoreSide
         const float wv = ct * 16 + (lane & 15) < cnt_y ? m : 0.0f;
         total += row16_sum(wv);
       }
-      if (split) total *= RESCORE_SPLIT_UNSCALE;                                 // exact: a power of two
+      if (split) total *= ALADIN_SPLIT_UNSCALE;                                 // exact: a power of two
     }
     if (lane == 0) out[(int64_t)q * k + slot] = total;
   }

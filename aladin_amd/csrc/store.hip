@@ -8,12 +8,12 @@
 // so a 25 000-caption set of ~12 scored words is 0.46 GB instead of 5.4 GB, and building the MFMA
 // operands of any sub-grid is a pure 16-byte row copy (no normalisation, half the bytes read).
 // Scores from a store are bit-identical to scores from the fp32 sets.
-#include "common.hpp"
-#include "../../include/aladin_hip.h"
+#include "pack_rows.hpp"
 
 namespace {
 
-// one wave per destination row; src fp32 row (or none -> nothing written)
+// one wave per destination row; src fp32 row (or none -> nothing written).  The encoder of pack_rows.hpp: a row's bits are those
+// pack_rows_kernel gives it
 __global__ __launch_bounds__(256) void store_append_kernel(const float* __restrict__ src, int64_t sb, int64_t sr,
                                                            const int32_t* __restrict__ lens, int B, int L, int D, int Dp,
                                                            int tail, const int64_t* __restrict__ offsets,
@@ -22,51 +22,17 @@ __global__ __launch_bounds__(256) void store_append_kernel(const float* __restri
   const int64_t d = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);        // (sample, position) over B x (L - 1)
   if (d >= (int64_t)B * (L - 1)) return;
   const int k = (int)(d / (L - 1)), p = (int)(d % (L - 1));               // position p + 1 of the set
-  int cnt = lens[k] - 1 - tail;
-  cnt = cnt < 0 ? 0 : (cnt > L - 1 ? L - 1 : cnt);
-  if (p >= cnt) return;
+  if (p >= scored_len(lens[k], tail, L - 1)) return;
   const float* x = src + k * sb + (int64_t)(p + 1) * sr;
   half_t* dst = rows + (offsets[k] + p) * (split ? 2 * Dp : Dp);
-  float ss = 0.f;
-  if (vec4) {
-    for (int c = lane * 4; c < D; c += 256) {
-      const float4 v = *reinterpret_cast<const float4*>(x + c);
-      ss = sumsq4(ss, v);
-    }
-  } else {
-    for (int c = lane; c < D; c += 64) ss = fmaf(x[c], x[c], ss);
-  }
-  ss = wave_sum(ss);
-  const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);                     // same arithmetic as pack_row (align_fwd.hip)
-  if (split) {                                                           // [hi | lo] of x^ * 2^14, as pack_row's split branch
-    for (int c = lane; c < Dp; c += 64) {
-      half_t hi = (half_t)0, lo = (half_t)0;
-      if (c < D) {
-        const float v = x[c] * inv * 16384.0f;
-        hi = (half_t)v;
-        lo = (half_t)(v - (float)hi);
-      }
-      dst[c] = hi; dst[Dp + c] = lo;
-    }
-    return;
-  }
-  if (vec4) {
-    for (int c = lane * 4; c < Dp; c += 256) {
-      half4 h = {0, 0, 0, 0};
-      if (c < D) {
-        const float4 v = *reinterpret_cast<const float4*>(x + c);
-        h = half4{(half_t)(v.x * inv), (half_t)(v.y * inv), (half_t)(v.z * inv), (half_t)(v.w * inv)};
-      }
-      *reinterpret_cast<half4*>(dst + c) = h;
-    }
-  } else {
-    for (int c = lane; c < Dp; c += 64) dst[c] = (c < D) ? (half_t)(x[c] * inv) : (half_t)0;
-  }
+  const float inv = inv_norm_mem(x, D, lane, vec4 != 0);
+  if (split) write_split(dst, nullptr, dst + Dp, x, inv, D, Dp, lane);   // [hi | lo]
+  else write_fp16_mem(dst, x, inv, D, Dp, lane, vec4 != 0);
 }
 
 __device__ __forceinline__ void copy_row(const half_t* __restrict__ src, half_t* __restrict__ dst, int Dp, int lane) {
   if (src == nullptr) {
-    for (int c = lane * 8; c < Dp; c += 512) *reinterpret_cast<half8*>(dst + c) = half8{0, 0, 0, 0, 0, 0, 0, 0};
+    write_zero_row(dst, Dp, lane);
   } else {
     for (int c = lane * 8; c < Dp; c += 512) *reinterpret_cast<half8*>(dst + c) = *reinterpret_cast<const half8*>(src + c);
   }
@@ -83,40 +49,32 @@ __device__ __forceinline__ void copy_row_split(const half_t* __restrict__ src, h
   }
 }
 
-// max-side operand (xm / xe) from a store: same row map as pack_images_kernel
+// a sample's scored row `pos` in the store (k = ids[sample], or the sample itself), or nullptr: a masked position
+__device__ __forceinline__ const half_t* store_row(const half_t* __restrict__ rows, const int64_t* __restrict__ offsets,
+                                                   const int32_t* __restrict__ counts, const int32_t* __restrict__ ids, int sample,
+                                                   int pos, int cap, int Dp, int split) {
+  const int k = ids ? ids[sample] : sample;
+  const int n = counts[k] > cap ? cap : counts[k];
+  return pos < n ? rows + (offsets[k] + pos) * (split ? 2 * (Dp / 3) : Dp) : nullptr;
+}
+
+// max-side operand (xm / xe) from a store: d over [xm rows | xe rows]
 __global__ __launch_bounds__(256) void store_pack_x_kernel(const half_t* __restrict__ rows, const int64_t* __restrict__ offsets,
                                                            const int32_t* __restrict__ counts,
-                                                           const int32_t* __restrict__ ids, int Bi, int Rq, int Dp, int mrows, int rem,
-                                                           int64_t xm_rows, int64_t total_rows, half_t* __restrict__ xm,
+                                                           const int32_t* __restrict__ ids, int Bi, int Dp, MaxSideMap map,
+                                                           int64_t total_rows, half_t* __restrict__ xm,
                                                            half_t* __restrict__ xe, int split) {
   const int lane = threadIdx.x & 63;
   const int64_t d = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (d >= total_rows) return;
-  int i, rho;
-  half_t* dst;
-  if (d < xm_rows) {
-    const int rows_per_img = mrows;
-    i = (int)(d / rows_per_img);
-    rho = (int)(d % rows_per_img);
-    if (rho >= Rq) rho = 0;
-    dst = xm + d * Dp;
-  } else {
-    i = (int)((d - xm_rows) / rem);
-    rho = mrows + (int)((d - xm_rows) % rem);
-    dst = xe + (d - xm_rows) * Dp;
-  }
-  const half_t* src = nullptr;
-  if (i < Bi) {
-    const int k = ids ? ids[i] : i;
-    int Li = counts[k];
-    Li = Li > Rq ? Rq : Li;
-    if (rho < Li) src = rows + (offsets[k] + rho) * (split ? 2 * (Dp / 3) : Dp);
-  }
+  const MaxSideRow r = max_side_row(d, map);
+  half_t* dst = (r.side ? xe : xm) + r.row * Dp;
+  const half_t* src = r.i < Bi ? store_row(rows, offsets, counts, ids, r.i, r.rho, map.Rq, Dp, split) : nullptr;
   if (split) copy_row_split(src, dst, Dp / 3, lane, 1);
   else copy_row(src, dst, Dp, lane);
 }
 
-// sum-side operand (y): same row map as pack_captions_kernel
+// sum-side operand (y): d over the y rows
 __global__ __launch_bounds__(256) void store_pack_y_kernel(const half_t* __restrict__ rows, const int64_t* __restrict__ offsets,
                                                            const int32_t* __restrict__ counts,
                                                            const int32_t* __restrict__ ids, int Bc, int Tq, int Dp, int tpad,
@@ -124,14 +82,8 @@ __global__ __launch_bounds__(256) void store_pack_y_kernel(const half_t* __restr
   const int lane = threadIdx.x & 63;
   const int64_t d = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (d >= total_rows) return;
-  const int j = (int)(d / tpad), w = (int)(d % tpad);
-  const half_t* src = nullptr;
-  if (j < Bc) {
-    const int k = ids ? ids[j] : j;
-    int Lj = counts[k];
-    Lj = Lj > Tq ? Tq : Lj;
-    if (w < Lj) src = rows + (offsets[k] + w) * (split ? 2 * (Dp / 3) : Dp);
-  }
+  const SumSideRow r = sum_side_row(d, tpad);
+  const half_t* src = r.j < Bc ? store_row(rows, offsets, counts, ids, r.j, r.w, Tq, Dp, split) : nullptr;
   if (split) copy_row_split(src, y + d * Dp, Dp / 3, lane, 2);
   else copy_row(src, y + d * Dp, Dp, lane);
 }
@@ -159,9 +111,8 @@ extern "C" int aladin_store_append(const float* sets, int64_t stride_b, int64_t 
   const int Dp = store_row_width_fp16(D);
   if (Dp < D) return ALADIN_ERR_ARG;
   const int64_t total = (int64_t)B * (L - 1);
-  const int vec4 = (D % 4 == 0) && (stride_b % 4 == 0) && (stride_r % 4 == 0) && (((uintptr_t)sets & 15) == 0);
   hipLaunchKernelGGL(store_append_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream, sets, stride_b,
-                     stride_r, lens, B, L, D, Dp, tail, offsets, (half_t*)rows, vec4, precision == ALADIN_PRECISION_SPLIT);
+                     stride_r, lens, B, L, D, Dp, tail, offsets, (half_t*)rows, is_vec4_ok(sets, stride_b, stride_r, D), precision == ALADIN_PRECISION_SPLIT);
   return aladin_check_launch("store_append_kernel");
 }
 
@@ -171,7 +122,7 @@ extern "C" int aladin_align_pack_store_x(const void* rows, const int64_t* offset
   if (g->layout == ALADIN_LAYOUT_LONG) { aladin_set_error("align_pack_store_x: the store packers cover the tile classes, not a long-set geometry"); return ALADIN_ERR_ARG; }
   const int64_t total = g->xm_rows + g->xe_rows;
   hipLaunchKernelGGL(store_pack_x_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                     (const half_t*)rows, offsets, counts, ids, g->Bi, g->Rq, g->Dp, g->mrows, g->rem > 0 ? g->rem : 1, g->xm_rows, total, (half_t*)xm,
+                     (const half_t*)rows, offsets, counts, ids, g->Bi, g->Dp, MaxSideMap{g->mrows, g->rem > 0 ? g->rem : 1, g->Rq, g->xm_rows}, total, (half_t*)xm,
                      (half_t*)xe, g->split);
   return aladin_check_launch("store_pack_x_kernel");
 }

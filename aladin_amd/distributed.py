@@ -555,6 +555,8 @@ def sharded_alignment_loss_fast(im_set, s_seq, im_len, s_len, margin=0.2, max_vi
         raise ValueError("aladin_amd.distributed: exchange must be 'auto', 'sparse' or 'dense'")
     from . import ops
     im_len_t, s_len_t = ops._check_sets(im_set, s_seq, im_len, s_len)
+    if torch.is_grad_enabled() and (im_set.requires_grad or s_seq.requires_grad):
+        ops._check_backward_supported(im_set, s_seq, 0, 2)      # an unsupported D fails here, not inside loss.backward()
     return _ShardedTriplet.apply(im_set, s_seq, im_len_t, s_len_t, margin, max_violation, group, exchange)
 
 

@@ -240,6 +240,7 @@ def _check_backward_supported(im, s, x_tail, y_tail):
 def pack_sets(im, s, im_len_t, s_len_t, geom, norms=True):
     """Both sets in one launch -> Packed(geom, xm, xe, y, rnorm), the `packed` the score and backward functions take
     (rnorm None when norms=False or the operands are split)."""
+    im, s = _rows_inner_contig(im), _rows_inner_contig(s)
     dev = im.device
     xm = torch.empty(geom.xm_bytes // 2, dtype=torch.float16, device=dev)
     xe = torch.empty(max(geom.xe_bytes // 2, 8), dtype=torch.float16, device=dev)
@@ -259,7 +260,7 @@ def _align_forward(im, s, im_len_t, s_len_t, x_tail=0, y_tail=2, precision=None,
     if D != D2:
         raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (D, D2))
     geom = align_geometry(Bi, Bc, R, T, D, x_tail, y_tail, precision, layout='auto')
-    packed = Packed(*pack_sets(_rows_inner_contig(im), _rows_inner_contig(s), im_len_t, s_len_t, geom, norms=norms))
+    packed = Packed(*pack_sets(im, s, im_len_t, s_len_t, geom, norms=norms))
     return scores_from_packed(packed.xm, packed.xe, packed.y, geom), packed
 
 

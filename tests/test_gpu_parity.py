@@ -2139,6 +2139,18 @@ def test_sharded_sparse_exchange_compact_backward_emulated(W, mv):
                                      sl_all[r * B:(r + 1) * B].contiguous(), blk.index_select(0, need).contiguous())
         d_im_all.index_add_(0, need, gi)
         d_caps.append(gs)
+        if r == 0:
+            # the compact problem packed again, as the pair-driven backward of the sharded node packs it (ops.pack_sets), with the
+            # caption block a view whose feature axis is not contiguous: the gradients of the contiguous run, bit for bit
+            im_need, il_need = im_all.index_select(0, need), il_all.index_select(0, need)
+            s_blk, sl_blk, dS_need = s_all[:B], sl_all[:B].contiguous(), blk.index_select(0, need).contiguous()
+            s_view = s_blk.transpose(1, 2).contiguous().transpose(1, 2)
+            assert s_view.stride(2) != 1 and torch.equal(s_view, s_blk)
+            g_need = ops.align_geometry(need.numel(), B, R, Tn, D)
+            assert ops._pair_kernel_covers(g_need)
+            got = [ops._align_backward(im_need, sv, il_need, sl_blk, dS_need, packed=ops.pack_sets(im_need, sv, il_need, sl_blk, g_need))
+                   for sv in (s_blk, s_view)]
+            assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])
     if mv:
         assert touched < W * W * B * 0.8            # the exchange really is sparse
     scale = float(a.grad.abs().max())
@@ -2189,6 +2201,9 @@ def test_sharded_fast_path_under_rccl_world1(bwd_mode):
         assert_grads_close(b3.grad, ds, bwd_mode)
         with pytest.raises(ValueError):
             sharded_alignment_loss_fast(T(im[:10]), T(s[:10]), il[:10], sl[:10])
+        # a feature width the backward does not take fails at the forward, as on the single-device path
+        with pytest.raises(ValueError, match='differentiable alignment scores need D <= 1024'):
+            sharded_alignment_loss_fast(T(im[:2, :, :66]).requires_grad_(True), T(s[:2, :, :66]).requires_grad_(True), il[:2], sl[:2])
     finally:
         if created:
             dist.destroy_process_group()

@@ -21,6 +21,10 @@ Arg-max table: the sum-of-violations step with the dense table forced, one probl
 otherwise), one case per stage of the alignment backward: the fused triplet step in the three precision modes; the
 sum-of-violations step with the GEMM and with the gather row step; a sparse gradient on the score matrix (fp16 pair kernel at
 R = 65, fp32 fallback at R = 71); a long problem; the small-batch loss heads.
+`save FILE pack` saves the packed operands themselves (PACK_CASES, the shapes of tests/test_pack_gpu.py, ragged with lengths 0, 1
+and past the maximum; fp16, and split where the table says): xm, xe and y as raw 16-bit patterns and rnorm as 32-bit patterns,
+packed jointly, as images alone + captions alone and -- where the fused triplet forward covers the shape -- through its prologue;
+the rows of evaluation stores of the same sets and the operands built from them under a shuffled ids.
 Long sets (LONG_CASES): scores past the tile classes on either side and at the 512-position limit in fp16 and split precision,
 'MwSr' (the roles swapped), the long kernels forced onto a tile-class shape (ops.LONG_PATH_FORCE: scores and gradients), and
 the hinge step of AlignmentContrastiveLoss with the hardest negative and the sum of violations in two backward precisions.
@@ -57,6 +61,15 @@ SCORE_CASES = (
 )
 # (R, T) at B = 64, D = 256 -> (mrows, rem) of the arg-max kernel's class
 ARGMAX_CASES = (((34, 50), (32, 1)), ((38, 30), (32, 5)), ((51, 38), (48, 2)), ((50, 38), (48, 1)), ((49, 38), (48, 0)), ((58, 38), (64, 0)))
+
+
+# (R, T, D) at Bi = 3, Bc = 2 -> (mrows, rem, trows), also in split precision?
+PACK_CASES = (
+    ((34, 50, 64), (32, 1, 48), True), ((51, 38, 768), (48, 2, 40), True), ((20, 11, 64), (32, 0, 8), False),
+    ((42, 27, 128), (48, 0, 24), False), ((41, 50, 64), (32, 8, 48), False), ((66, 50, 64), (64, 1, 48), False),
+    ((71, 71, 64), (96, 0, 96), False), ((34, 50, 66), (32, 1, 48), False), ((34, 50, 1088), (32, 1, 48), True),
+    ((100, 20, 64), (128, 0, 32), False), ((34, 100, 64), (64, 0, 112), False),
+)
 
 
 LONG_CASES = ((5, 6, 98, 50, 64), (6, 5, 34, 100, 64), (3, 3, 512, 512, 32))
@@ -239,6 +252,54 @@ def long_cases(ops, synth, dev):
     return out
 
 
+def pack_cases(ops, synth, dev):
+    """-> {name: bit patterns} of the packed operands of PACK_CASES, every way the library packs them."""
+    from aladin_amd import _lib, eval_grid
+    from aladin_amd.store import PackedSetStore
+    out = {}
+    T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+
+    def keep(tag, g, xm, xe, y, rnorm):
+        out[tag + '/xm'], out[tag + '/y'] = xm[:g.xm_bytes // 2].view(torch.int16).cpu(), y[:g.y_bytes // 2].view(torch.int16).cpu()
+        if g.xe_bytes:
+            out[tag + '/xe'] = xe[:g.xe_bytes // 2].view(torch.int16).cpu()
+        if rnorm is not None:
+            out[tag + '/rnorm'] = rnorm[:g.rnorm_bytes // 4].view(torch.int32).cpu()
+
+    for (R, Tn, D), cls, split in PACK_CASES:
+        im, s, il, sl = synth.alignment_batch(3, R, Tn, D, seed=8800 + R + Tn + D, ragged=True, Bc=2)
+        il, sl = [R - 5, 0, R + 3], [Tn - 4, 1]
+        a, b = T(im), T(s)
+        ilt, slt = ops.lengths_tensor(il, dev), ops.lengths_tensor(sl, dev)
+        for prec in ('fp16', 'split') if split else ('fp16',):
+            g = ops.align_geometry(3, 2, R, Tn, D, precision=prec, layout='auto')
+            assert (g.mrows, g.rem, g.trows) == cls, ((R, Tn, D), g.mrows, g.rem, g.trows)
+            tag = 'pack-R%d-T%d-D%d-%s' % (R, Tn, D, prec)
+            pk = ops.pack_sets(a, b, ilt, slt, g)
+            keep(tag + '/joint', g, pk.xm, pk.xe, pk.y, pk.rnorm)
+            rn = torch.zeros(g.rnorm_bytes // 4, device=dev)
+            xm, xe = ops.pack_images(a, ilt, g, rnorm=rn)
+            keep(tag + '/single', g, xm, xe, ops.pack_captions(b, slt, g, rnorm=rn), rn)
+            if g.layout == _lib.LAYOUT_LONG:
+                continue
+            si, sc = PackedSetStore(D, 0, dev, precision=prec), PackedSetStore(D, 2, dev, precision=prec)
+            for k in (2, 0, 1):
+                si.append(a[k:k + 1], il[k:k + 1])
+            for k in (1, 0):
+                sc.append(b[k:k + 1], sl[k:k + 1])
+            out[tag + '/store/x'], out[tag + '/store/y'] = si.rows[:si.n_rows].view(torch.int16).cpu(), sc.rows[:sc.n_rows].view(torch.int16).cpu()
+            xm, xe = eval_grid.StoreSide(si.view([1, 2, 0])).pack_max(g)
+            keep(tag + '/store-ids', g, xm, xe, eval_grid.StoreSide(sc.view([1, 0])).pack_sum(g, 0, 2), None)
+        # the triplet forward's prologue on the square problem of the same shape, where the fused call covers it
+        im, s, il3, sl3 = synth.alignment_batch(3, R, Tn, D, seed=8900 + R + Tn + D, ragged=True)
+        fused = ops._triplet_forward(T(im), T(s), ops.lengths_tensor(il3, dev), ops.lengths_tensor(sl3, dev), 0.2)
+        if fused is not None:
+            saved = fused[2]
+            pk = ops.Packed.from_buf(saved.tensors()[4], saved.geom, saved.offs)
+            keep('pack-R%d-T%d-D%d-fp16/prologue' % (R, Tn, D), saved.geom, pk.xm, pk.xe, pk.y, pk.rnorm)
+    return out
+
+
 def adversarial_retrieval(case, n_img, cpi, D, seed):
     """The 'bulk' and 'exact_ties' recipes of tests/test_gpu_parity.py::_adversarial_retrieval."""
     rng = np.random.default_rng(seed)
@@ -353,7 +414,7 @@ def main():
     dev = torch.device('cuda:0')
     out = {}
     group = sys.argv[3] if len(sys.argv) > 3 else 'alignment'
-    assert group in ('alignment', 'retrieval', 'eval', 'all'), group
+    assert group in ('alignment', 'retrieval', 'eval', 'pack', 'all'), group
     if group in ('alignment', 'all'):
         for tag, ragged, seed in (('full', False, 1234), ('ragged', True, 99)):
             im, s, il, sl = synth.alignment_batch(256, 34, 50, 768, seed=seed, ragged=ragged)
@@ -367,6 +428,8 @@ def main():
         out.update(retrieval_cases(ops, synth, dev))
     if group in ('eval', 'all'):
         out.update(eval_cases(ops, synth, dev))
+    if group in ('pack', 'all'):
+        out.update(pack_cases(ops, synth, dev))
     torch.save(out, sys.argv[2])
     print('saved', sys.argv[2], {k: float(v.double().sum()) for k, v in out.items()})
 
