@@ -15,6 +15,7 @@ PRECISION_FP16, PRECISION_SPLIT = 0, 1      # ALADIN_PRECISION_* of include/alad
 LAYOUT_AUTO, LAYOUT_TILES, LAYOUT_TILES_WHOLE, LAYOUT_LONG = -1, 0, 1, 2      # ALADIN_LAYOUT_*
 TILE_MAX_SCORED = 96                        # ALADIN_TILE_MAX_SCORED
 NN_ENTROPY_MAX_N = 32768                    # ALADIN_NN_ENTROPY_MAX_N
+XENT_MAX_B = 32768                          # ALADIN_XENT_MAX_B
 BWD_PARTNERS_FP16, BWD_DENSE, BWD_DENSE_GATHER, TRIPLET_BWD_BASE_WORKSPACE, BWD_OWN_ROW_FP16 = 1, 2, 4, 8, 16      # ALADIN_BWD_*, ALADIN_TRIPLET_BWD_BASE_WORKSPACE
 
 class AlignGeom(C.Structure):
@@ -106,6 +107,8 @@ def _signatures():
         'aladin_nn_entropy_workspace_bytes': (sz, [i32]),
         'aladin_nn_entropy_fwd': (C.c_int, [p, i64, p, i64, i32, i32, p, p, p, p, p]),
         'aladin_nn_entropy_bwd': (C.c_int, [p, i64, p, i64, i32, i32, p, p, p, p, p, p]),
+        'aladin_xent_workspace_bytes': (sz, [i32]),
+        'aladin_xent_fwd_bwd': (C.c_int, [p, i64, i32, p, p, p, p, p, p]),
     }
 
 

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .loss import AlignmentContrastiveLoss, ContrastiveLoss, DistillationLoss, dot_sim
+from .loss import AlignmentContrastiveLoss, ContrastiveLoss, CrossEntropyCriterion, DistillationLoss, dot_sim
 
 
 def pairwise_NNs_inner(x):
@@ -51,12 +51,12 @@ class ALADModel(nn.Module):
         training = config['training']
         self.losses_types = training['loss-type'].split('-')          # :265
         self.losses_weights = training['loss-weights']                # :266
+        dev = 'cuda' if torch.cuda.is_available() else 'cpu'
         if isinstance(self.losses_weights, list):                     # :267-270
             assert len(self.losses_types) == len(self.losses_weights)
             self.losses_weights = {k: v for k, v in zip(self.losses_types, self.losses_weights)}
             self.auto_weight = False
         else:                                                         # :271-273 ('auto': unregistered parameters)
-            dev = 'cuda' if torch.cuda.is_available() else 'cpu'
             self.losses_weights = {k: nn.Parameter(-2.3 * torch.ones(1)).to(dev) for k in self.losses_types}
             self.auto_weight = True
         if 'distillation' in self.losses_types:                       # :275-276
@@ -70,6 +70,10 @@ class ALADModel(nn.Module):
                 max_violation=training['max-violation'], aggregation=training['alignment-mode'])
         self.matching_criterion = ContrastiveLoss(                    # :289-292 (the `if` there is always true)
             margin=training['margin'], measure=training['measure'], max_violation=training['max-violation'])
+        if 'crossentropy' in self.losses_types:
+            # an opt-in term the reference's forward_loss has no branch for (it ignores unknown tokens): its own
+            # CrossEntropyCriterion (alad/loss.py:190-201) on the matching head's embeddings, temperature learnable
+            self.crossentropy_criterion = CrossEntropyCriterion().to(dev)
         self.Eiters = 0
         self.config = config
         self._logger = None
@@ -164,6 +168,11 @@ class ALADModel(nn.Module):
             loss_uniform = ops.nn_entropy_loss(img_emb, cap_emb)
             losses['entropy'] = loss_uniform
             logged.append(('entropy-uniform-loss', loss_uniform, img_emb.size(0)))
+
+        if 'crossentropy' in self.losses_types:                       # not in the reference's forward_loss: see __init__
+            crossentropy_loss = self.crossentropy_criterion(img_emb, cap_emb)
+            losses['crossentropy'] = crossentropy_loss
+            logged.append(('crossentropy_loss', crossentropy_loss, img_emb.size(0)))
 
         if 'regularizehidden' in self.losses_types:                   # :423-425
             losses['regularizehidden'] = reg_loss

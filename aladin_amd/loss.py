@@ -5,11 +5,14 @@
     ContrastiveLoss           <- alad/loss.py:162-186
     DistillationLoss          <- alad/loss.py:359-447
     Contrastive               <- alad/loss.py:29-67 (shared hinge)
+    CrossEntropyCriterion     <- alad/loss.py:190-201
+    AlignmentCrossEntropyLoss    (not in the reference: the same criterion on the alignment head's scores)
 
 None of them holds parameters or buffers, except DistillationLoss(mode='mse') whose learnable pair
-`wb` the reference has too (:366) -- state dicts saved by the reference load unchanged (SURVEY.md
-section 5, checkpoint row).  Every aggregation / distillation mode / measure of the reference is
-computed by HIP kernels; nothing falls back to eager PyTorch.
+`wb` the reference has too (:366) and the cross-entropy criteria's `temperature` (:193) -- state dicts
+saved by the reference load unchanged (checkpoint row).  Every aggregation /
+distillation mode / measure of the reference is computed by HIP kernels; nothing falls back to eager
+PyTorch.
 """
 import torch
 from torch import nn
@@ -55,6 +58,32 @@ class Contrastive(nn.Module):
         return ops.hinge_loss(scores, self.margin, self.max_violation)
 
 
+ALIGNMENT_AGGREGATIONS = ('MrSw', 'MrAVGw', 'MwSr', 'symm', 'sum', 'mean', 'scan-sentences')
+
+
+def _check_aggregation(aggregation):
+    if aggregation not in ALIGNMENT_AGGREGATIONS:
+        # the reference leaves aggr_similarity unbound and dies with a NameError (:151-159)
+        raise ValueError("aladin_amd: unknown alignment aggregation %r (supported: 'MrSw', 'MrAVGw', 'MwSr', "
+                         "'symm', 'sum', 'mean', 'scan-sentences')" % (aggregation,))
+
+
+def alignment_similarity(aggregation, im_set, s_seq, im_len, s_len):
+    """The differentiable (Bi, Bc) score matrix of an alignment aggregation, reference alad/loss.py:120-149."""
+    if aggregation == 'scan-sentences':
+        aggr_similarity = ops.alignment_scan_scores(im_set, s_seq, im_len, s_len)
+    elif aggregation in ('sum', 'mean'):
+        aggr_similarity = ops.alignment_sum_scores(im_set, s_seq, im_len, s_len, mean=(aggregation == 'mean'))
+    elif aggregation in ('MwSr', 'symm'):
+        aggr_similarity = ops.alignment_scores(im_set, s_seq, im_len, s_len, aggregation)
+    else:
+        aggr_similarity = ops.alignment_scores(im_set, s_seq, im_len, s_len)
+    if aggregation == 'MrAVGw':
+        lens = ops.lengths_tensor(s_len, aggr_similarity.device).to(torch.float32) - 3.0
+        aggr_similarity = aggr_similarity / lens.unsqueeze(0)
+    return aggr_similarity
+
+
 class AlignmentContrastiveLoss(Contrastive):
     """reference alad/loss.py:70-159.  aggregation: 'MrSw' (all shipped configs), 'MrAVGw' (= MrSw
     divided by the caption length, :126-129), 'MwSr' / 'symm' (the MrSw kernels with the sets'
@@ -66,26 +95,13 @@ class AlignmentContrastiveLoss(Contrastive):
         self.aggregation = aggregation
 
     def forward(self, im_set, s_seq, im_len, s_len, return_loss=True, return_similarity_mat=False):
-        if self.aggregation not in ('MrSw', 'MrAVGw', 'MwSr', 'symm', 'sum', 'mean', 'scan-sentences'):
-            # the reference leaves aggr_similarity unbound and dies with a NameError (:151-159)
-            raise ValueError("aladin_amd: unknown alignment aggregation %r (supported: 'MrSw', 'MrAVGw', 'MwSr', "
-                             "'symm', 'sum', 'mean', 'scan-sentences')" % (self.aggregation,))
+        _check_aggregation(self.aggregation)
         if return_loss and self.aggregation == 'MrSw':
             # fused scores + hinge node; both outputs are differentiable, as the reference's (ops.alignment_triplet_loss)
             loss, aggr_similarity = ops.alignment_triplet_loss(im_set, s_seq, im_len, s_len, self.margin,
                                                                self.max_violation)
             return (loss, aggr_similarity) if return_similarity_mat else loss
-        if self.aggregation == 'scan-sentences':
-            aggr_similarity = ops.alignment_scan_scores(im_set, s_seq, im_len, s_len)
-        elif self.aggregation in ('sum', 'mean'):
-            aggr_similarity = ops.alignment_sum_scores(im_set, s_seq, im_len, s_len, mean=(self.aggregation == 'mean'))
-        elif self.aggregation in ('MwSr', 'symm'):
-            aggr_similarity = ops.alignment_scores(im_set, s_seq, im_len, s_len, self.aggregation)
-        else:
-            aggr_similarity = ops.alignment_scores(im_set, s_seq, im_len, s_len)
-        if self.aggregation == 'MrAVGw':
-            lens = ops.lengths_tensor(s_len, aggr_similarity.device).to(torch.float32) - 3.0
-            aggr_similarity = aggr_similarity / lens.unsqueeze(0)
+        aggr_similarity = alignment_similarity(self.aggregation, im_set, s_seq, im_len, s_len)
         if return_loss:
             loss = self.compute_contrastive_loss(aggr_similarity)
         if return_loss and return_similarity_mat:
@@ -132,3 +148,38 @@ class DistillationLoss(nn.Module):
             return ops.listnet_loss(teacher_scores, student_scores, temperature=6.0, eps=1e-10)
         return ops.distillation_loss(teacher_scores, student_scores, self.mode, self.margin, self.threshold,
                                      self.stride, wb=self.wb if self.mode == 'mse' else None)
+
+
+class CrossEntropyCriterion(nn.Module):
+    """reference alad/loss.py:190-201: the symmetric cross-entropy (InfoNCE) of im @ s.T * exp(temperature), `temperature` a
+    learnable (1,) parameter starting at 0 -- a reference state dict (['temperature']) loads unchanged."""
+
+    def __init__(self):
+        super().__init__()
+        self.temperature = nn.Parameter(torch.zeros(1), requires_grad=True)       # :193
+
+    def forward(self, im, s):
+        return ops.match_cross_entropy(im, s, self.temperature)
+
+
+class AlignmentCrossEntropyLoss(nn.Module):
+    """NOT in the reference: CrossEntropyCriterion's loss on the alignment head's score matrix (FILIP-style training of the
+    fine-grained head) -- the (B, B) matrix AlignmentContrastiveLoss(aggregation=...) scores, times exp(temperature), through the
+    symmetric cross-entropy.  It has its own learnable `temperature` (1,), initial value 0.  The default 'MrAVGw' keeps the
+    scores in [-1, 1] whatever the caption length.  The score functions are AlignmentContrastiveLoss's; their backward here is the
+    dense-dS one (every pair carries a gradient), several times the cost of the hardest-negative triplet step."""
+
+    def __init__(self, aggregation='MrAVGw'):
+        super().__init__()
+        _check_aggregation(aggregation)
+        self.aggregation = aggregation
+        self.temperature = nn.Parameter(torch.zeros(1), requires_grad=True)
+
+    def forward(self, im_set, s_seq, im_len, s_len, return_similarity_mat=False):
+        _check_aggregation(self.aggregation)
+        if im_set.shape[0] != s_seq.shape[0]:
+            raise ValueError('aladin_amd: the cross-entropy criterion needs a square score matrix: one caption per image set, '
+                             'got %d image sets and %d captions' % (im_set.shape[0], s_seq.shape[0]))
+        aggr_similarity = alignment_similarity(self.aggregation, im_set, s_seq, im_len, s_len)
+        loss = ops.cross_entropy_scores(aggr_similarity, self.temperature)
+        return (loss, aggr_similarity) if return_similarity_mat else loss

@@ -9,7 +9,7 @@ from . import _lib
 from ._ops_common import _stream, _ptr, _require_gpu, _rows_inner_contig, _ld, _workspace
 from .ops import (AlignSaved, _align_forward, _align_head_forward, _caption_fill, _check_backward_supported, _check_sets,
                   _pad_features, _pair_kernel_covers, _set_view, is_long)
-from .ops_losses import _hinge_raw, _sgemm, dot_scores
+from .ops_losses import _hinge_raw, _sgemm, _xent_limit, _xent_raw, _xent_scale, _xent_temperature, dot_scores
 
 
 # ------------------------------------------------------------------------------------------------
@@ -325,6 +325,66 @@ def match_hinge(im, s, margin, max_violation):
         loss, _, M = _SmallMatchDistill.apply(im, s, None, margin, max_violation, True, 6.0, 1e-10)
         return loss, M
     return _MatchHinge.apply(im, s, margin, max_violation)
+
+
+class _MatchCrossEntropy(torch.autograd.Function):
+    """(cross-entropy loss on M, M) with M = im @ s.T (alad/loss.py:196-200) as ONE autograd node, built like _MatchHinge: forward = the
+    exact-fp32 GEMM + aladin_xent_fwd_bwd, backward = aladin_grad_combine (the upstream gradient times the saved dM and
+    d log_temperature, one launch) + two GEMMs.  Both outputs are differentiable."""
+
+    @staticmethod
+    def forward(ctx, im, s, log_t):
+        a = im if im.stride(1) == 1 else im.contiguous()
+        b = s if s.stride(1) == 1 else s.contiguous()
+        B = a.shape[0]
+        M = torch.empty((B, B), dtype=torch.float32, device=a.device)
+        _sgemm(B, B, a.shape[1], a, a.stride(0), a.stride(1), b, b.stride(1), b.stride(0), M)
+        ctx.want_dt = ctx.needs_input_grad[2]
+        loss, grads = _xent_raw(M, log_t, any(ctx.needs_input_grad), ctx.want_dt)
+        ctx.save_for_backward(a, b, grads)
+        ctx.t_shape = log_t.shape
+        ctx.set_materialize_grads(False)
+        return loss, M
+
+    @staticmethod
+    def backward(ctx, g_loss, g_M):
+        a, b, grads = ctx.saved_tensors
+        if (g_loss is None or grads is None) and g_M is None:
+            return None, None, None
+        B, D = a.shape
+        n = B * B
+        C_tot = d_t = None
+        if g_loss is not None and grads is not None:
+            out = _xent_scale(grads, g_loss.to(torch.float32).contiguous(), n + (1 if ctx.want_dt else 0))
+            C_tot = out[:n].view(B, B)
+            d_t = out[n:].view(ctx.t_shape) if ctx.want_dt else None
+        if g_M is not None:
+            C_tot = g_M.contiguous() if C_tot is None else C_tot + g_M
+        d_a = d_b = None
+        if ctx.needs_input_grad[0]:
+            d_a = torch.empty((B, D), dtype=torch.float32, device=a.device)
+            _sgemm(B, D, B, C_tot, C_tot.stride(0), 1, b, b.stride(0), b.stride(1), d_a)          # C @ cap
+        if ctx.needs_input_grad[1]:
+            d_b = torch.empty((B, D), dtype=torch.float32, device=a.device)
+            _sgemm(B, D, B, C_tot, 1, C_tot.stride(0), a, a.stride(0), a.stride(1), d_b)          # C.T @ img
+        return d_a, d_b, d_t
+
+
+def match_cross_entropy(im, s, log_temperature, return_scores=False):
+    """CrossEntropyCriterion (reference alad/loss.py:190-201) from the embeddings in one autograd node: M = im @ s.T in exact fp32,
+    then the symmetric cross-entropy of M * exp(log_temperature).  log_temperature: a one-element float32 GPU tensor (the module's
+    parameter; it gets a gradient) or a Python float.  -> loss, or (loss, M) with return_scores; both are differentiable."""
+    for t in (im, s):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('aladin_amd: expected a torch.Tensor, got %r' % type(t))
+    if im.dim() != 2 or s.dim() != 2 or im.shape != s.shape or im.shape[0] < 1 or im.shape[1] < 1:
+        raise ValueError('aladin_amd: the cross-entropy criterion needs a square score matrix: two (B, D) embedding matrices of equal '
+                         'shape (the reference fails in F.cross_entropy, alad/loss.py:198-199); got %s and %s'
+                         % (tuple(im.shape), tuple(s.shape)))
+    _require_gpu(im, s)
+    _xent_limit(im.shape[0])
+    loss, M = _MatchCrossEntropy.apply(im, s, _xent_temperature(log_temperature, im.device))
+    return (loss, M) if return_scores else loss
 
 
 def small_batch_match_distill(im, s, teacher, margin, max_violation, want_hinge=True, temperature=6.0, eps=1e-10):

@@ -1,5 +1,6 @@
 """Score-matrix losses and the exact-fp32 products over the C ABI: the VSE++ hinge, ListNet and the other distillation modes,
-order / dot similarities, l2norm (reference alad/loss.py:8-67, 359-447, alad/utils.py:134-139).  Autograd plumbing only."""
+the symmetric cross-entropy criterion, order / dot similarities, l2norm (reference alad/loss.py:8-67, 190-201, 359-447,
+alad/utils.py:134-139).  Autograd plumbing only."""
 import ctypes as C
 
 import torch
@@ -268,6 +269,87 @@ def pairwise_nns_inner(x):
     _nn_entropy_limit(x.shape[0])
     x = x.detach()
     return _nn_entropy_raw(x if x.stride(1) == 1 else x.contiguous(), None, False)[1].to(torch.int64)
+
+
+# ------------------------------------------------------------------------------------------------
+# symmetric cross-entropy (InfoNCE) with a learnable temperature
+# ------------------------------------------------------------------------------------------------
+def _xent_limit(B):
+    if B > _lib.XENT_MAX_B:
+        raise ValueError('aladin_amd: the cross-entropy criterion covers B <= %d, got %d' % (_lib.XENT_MAX_B, B))
+
+
+def _xent_temperature(log_temperature, device):
+    """-> the one-element float32 device tensor the kernels read: the caller's (it gets the gradient) or a constant made here"""
+    if isinstance(log_temperature, torch.Tensor):
+        _require_gpu(log_temperature)
+        if log_temperature.numel() != 1:
+            raise ValueError('aladin_amd: log_temperature is one element, got shape %s' % (tuple(log_temperature.shape),))
+        return log_temperature
+    return torch.full((1,), float(log_temperature), dtype=torch.float32, device=device)       # a fill: no host wait
+
+
+def _xent_raw(scores, log_t, want_grad, want_dt):
+    """aladin_xent_fwd_bwd on a square matrix with unit column stride -> (loss, grads or None): grads is ONE (B * B + 1,) buffer,
+    dS row-major followed by d log_temperature, so that the backward scales both in one aladin_grad_combine launch."""
+    lib = _lib.load()
+    B = scores.shape[0]
+    dev = scores.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    grads = torch.empty(B * B + 1, dtype=torch.float32, device=dev) if want_grad else None
+    ws = _workspace(lib.aladin_xent_workspace_bytes(B), dev)
+    dt = C.c_void_p(grads.data_ptr() + 4 * B * B) if (want_grad and want_dt) else C.c_void_p(0)
+    _lib.check(lib.aladin_xent_fwd_bwd(_ptr(scores), _ld(scores), B, _ptr(log_t), _ptr(loss), _ptr(grads), dt, _ptr(ws), _stream()),
+               'xent_fwd_bwd')
+    return loss, grads
+
+
+def _xent_scale(grads, g, n):
+    """g * grads[:n] in one launch (g: the upstream gradient, a device scalar)"""
+    out = torch.empty(n, dtype=torch.float32, device=grads.device)
+    _lib.check(_lib.load().aladin_grad_combine(n, _ptr(g), 1.0, _ptr(grads), 0.0, _ptr(None), _ptr(out), 0.0, _ptr(None), _stream()),
+               'grad_combine')
+    return out
+
+
+class _CrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, log_t):
+        B = scores.shape[0]
+        sc = scores if (scores.stride(1) == 1 and (B == 1 or scores.stride(0) >= B)) else scores.contiguous()
+        ctx.want_dt = ctx.needs_input_grad[1]
+        loss, grads = _xent_raw(sc, log_t, ctx.needs_input_grad[0] or ctx.want_dt, ctx.want_dt)
+        ctx.save_for_backward(grads)
+        ctx.B, ctx.t_shape = B, log_t.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grads,) = ctx.saved_tensors
+        if grads is None:
+            return None, None
+        n = ctx.B * ctx.B
+        out = _xent_scale(grads, g.to(torch.float32).contiguous(), n + (1 if ctx.want_dt else 0))
+        return (out[:n].view(ctx.B, ctx.B) if ctx.needs_input_grad[0] else None), (out[n:].view(ctx.t_shape) if ctx.want_dt else None)
+
+
+def _check_square(scores):
+    if not isinstance(scores, torch.Tensor):
+        raise TypeError('aladin_amd: expected a torch.Tensor, got %r' % type(scores))
+    if scores.dim() != 2 or scores.shape[0] != scores.shape[1] or scores.shape[0] < 1:
+        raise ValueError('aladin_amd: the cross-entropy criterion needs a square score matrix, got %s '
+                         '(the reference fails in F.cross_entropy, alad/loss.py:198-199)' % (tuple(scores.shape),))
+
+
+def cross_entropy_scores(scores, log_temperature):
+    """Symmetric cross-entropy (InfoNCE) of a square score matrix: with L = scores * exp(log_temperature), the mean of
+    cross_entropy(L, arange) and cross_entropy(L.T, arange) -- what CrossEntropyCriterion (reference alad/loss.py:190-201) computes
+    from its logits.  log_temperature: a one-element float32 GPU tensor (it gets a gradient) or a Python float (a constant).
+    One autograd node, two launches forward; the backward scales the saved gradients by the upstream one in one launch."""
+    _check_square(scores)
+    _require_gpu(scores)
+    _xent_limit(scores.shape[0])
+    return _CrossEntropy.apply(scores, _xent_temperature(log_temperature, scores.device))
 
 
 class _L2Norm(torch.autograd.Function):

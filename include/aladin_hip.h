@@ -434,6 +434,26 @@ ALADIN_API int aladin_nn_entropy_bwd(const float* img, int64_t ld_img, const flo
                           const int32_t* nn, const float* dist, const float* gscale, float* d_img, float* d_cap, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Symmetric cross-entropy (InfoNCE) with a learnable temperature on a B x B score matrix -- CrossEntropyCriterion, reference
+ * alad/loss.py:190-201 (csrc/xent.hip).  With t = *log_temperature and L = S * e^t:
+ *   loss = 1/(2B) [ sum_i (LSE_j L_ij - L_ii) + sum_j (LSE_i L_ij - L_jj) ]
+ *   dS   = e^t (softmax_j L + softmax_i L - 2 I) / (2B)                 (B x B contiguous, WRITTEN; may be NULL)
+ *   d_log_temperature = sum_ij dL_ij L_ij, dL = dS / e^t               (1 float; may be NULL)
+ * Both gradients are those of an upstream gradient of 1.  log_temperature is a DEVICE scalar, read by the kernels: no host
+ * synchronisation, and a replayed graph follows its current value.  The log-sum-exps are max-subtracted in fp32 (L of order
+ * +-5000 is handled like L of order 1); the diagonal of dS is formed from each softmax's off-diagonal mass, so it is not rounded
+ * away where both softmaxes are one-hot.  A NaN score makes the loss NaN (dS is then unspecified on its row and column); a
+ * non-finite e^t propagates.  B = 1: loss, dS and d_log_temperature are exactly 0.
+ * Limits: 1 <= B <= ALADIN_XENT_MAX_B (beyond it ALADIN_ERR_UNSUPPORTED), ldS >= B; checked before any launch.
+ * workspace: aladin_xent_workspace_bytes(B) bytes (0 outside the limits), 16-byte aligned, the caller's.  Two launches on
+ * `stream`; no allocation, no atomics, every sum in a fixed order: deterministic and graph-capturable.
+ * ------------------------------------------------------------------------------------------- */
+#define ALADIN_XENT_MAX_B 32768
+ALADIN_API size_t aladin_xent_workspace_bytes(int B);
+ALADIN_API int aladin_xent_fwd_bwd(const float* S, int64_t ldS, int B, const float* log_temperature, float* loss, float* dS,
+                        float* d_log_temperature, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Retrieval similarity matrix  sim = img @ cap.T  at evaluation scale (5000 x 25000 x 768) on the
  * 16-bit MFMA path with a hi/lo fp16 split (3 MFMAs per product, ~fp32 accuracy so that ranks
  * agree with the reference; operand rows are kept [hi | lo] and one accumulator chain runs hi.hi, lo.hi, hi.lo).  Replaces ims.mm(caps.t()), reference alad/recall_auxiliary.py:30,51
