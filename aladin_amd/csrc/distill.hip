@@ -17,6 +17,9 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
+// clamp(min=0) / relu as torch computes them: a NaN stays a NaN (fmaxf would drop it), and then rides the sums that run anyway
+__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
+
 // sum over a 256-thread block, result in every thread; `red` holds 4 doubles
 __device__ __forceinline__ double block_sum_f64(double v, double* red) {
   v = wave_sum_f64(v);
@@ -113,10 +116,12 @@ __global__ __launch_bounds__(256) void tcon_loss_kernel(const float* __restrict_
     const float cj = (float)col_count[j];
     const float a = margin + s - dk;                                   // cost_s[k][j]
     const float b = margin + s - M[(int64_t)j * ldm + j];              // cost_im[k][j]
-    lsum += (double)(cj * fmaxf(a, 0.f)) + (double)(rk * fmaxf(b, 0.f));
+    // a column no row picked / a row no column picked is never index_selected (:418 / :421): its NaN must not become 0 * NaN
+    lsum += (double)(cj != 0.f ? cj * relu_keep_nan(a) : 0.f) + (double)(rk != 0.f ? rk * relu_keep_nan(b) : 0.f);
     const float ga = (a > 0.f) ? cj : 0.f, gb = (b > 0.f) ? rk : 0.f;
+    if (j == k) continue;                                              // (k,k): S_kk enters its own cost twice, +1 and -1
     neg += ga;                                                         // -> d S_kk from row k
-    if (dM && j != k) dM[(int64_t)k * B + j] = ga + gb;
+    if (dM) dM[(int64_t)k * B + j] = ga + gb;
     // column k, element (j, k): cost_im[j][k] = m + S_jk - S_kk pulls on S_kk with weight r_j
     const float bc = margin + M[(int64_t)j * ldm + k] - dk;
     neg += (bc > 0.f) ? (float)row_count[j] : 0.f;
@@ -125,8 +130,8 @@ __global__ __launch_bounds__(256) void tcon_loss_kernel(const float* __restrict_
   neg = block_sum_f64(neg, red);
   if (threadIdx.x == 0) {
     part[k] = lsum;
-    // (k,k) itself: a = b = margin, its +c_k and +r_k cancel against the same terms inside `neg`
-    if (dM) dM[(int64_t)k * B + k] = (float)((margin > 0.f ? (double)col_count[k] + (double)row_count[k] : 0.0) - neg);
+    // (k,k) itself is left out of `neg`: whether float32 margin + S_kk - S_kk is positive or not, its gradient cancels exactly
+    if (dM) dM[(int64_t)k * B + k] = (float)(0.0 - neg);
   }
 }
 
@@ -183,7 +188,7 @@ __global__ __launch_bounds__(256) void ordinal_line_kernel(const float* __restri
     unsigned char a = 0;
     if (p + stride < B && key[p + stride] >= threshold) {            // :382 / :393
       const float v = margin + so[p] - so[p + stride];                // :380 / :391
-      lsum += (double)fmaxf(v, 0.f);
+      lsum += (double)relu_keep_nan(v);
       cnt += 1.0;
       a = v > 0.f;
     }
@@ -247,7 +252,7 @@ __global__ __launch_bounds__(256) void order_fwd_kernel(const float* __restrict_
       const float sv = c[tj][d];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        const float v = fmaxf(sv - a[ti + 8 * u][d], 0.f);
+        const float v = relu_keep_nan(sv - a[ti + 8 * u][d]);
         acc[u] = fmaf(v, v, acc[u]);
       }
     }

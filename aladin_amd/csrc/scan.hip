@@ -17,6 +17,13 @@
 //   dW = g (A / (a m) - k t);  dZ = W (dW - <W, dW>);  dP = (dZ - N <N, dZ>_col) / c
 //   dA = g W / (a m) + dP [A > 0];   H_j += g sum_r k_r W_r^T W_r
 //   d i = dA s,   d s = dA^T i - H s,   then the normalisation's backward.
+// a = max(|i_r|, 1e-8) of F.cosine_similarity is taken on the NORMALISED region, as the reference does:
+// 1 for every region whose norm reaches F.normalize's eps, |x| 1e12 below it, and 1e-8 for a zero
+// vector inside the valid range (its score is 0; its gradient is g att_r / (1e-8 m) through the 1e12
+// of the normalisation's backward, finite in fp32, as the oracle's).
+// LDS: forward and backward take the same (3 R'T' + T'^2 + T' + 3 R') floats, 146 KiB at the 96 x 96
+// bound, so the backward accepts every shape the forward does: dW / dZ overwrite t = W G element by
+// element (each is read once, by the thread that writes it) and H_j accumulates in its global slot.
 #include "common.hpp"
 #include "../../include/aladin_hip.h"
 
@@ -25,25 +32,26 @@ namespace {
 constexpr int SCAN_MAX = 96;      // R', T' bound of aladin_align_geometry
 
 struct ScanWs {
-  float *xn, *yn, *xinv, *yinv, *A, *G, *dA, *H, *dxn, *dyn;
+  float *xn, *yn, *xinv, *yinv, *xa, *A, *G, *dA, *H, *dxn, *dyn;
 };
 
 size_t scan_layout(int Bi, int Bc, int Rq, int Tq, int D, bool bwd, char* base, ScanWs* w) {
   size_t off = 0;
   auto take = [&](size_t n) { float* p = base ? (float*)(base + off) : nullptr; off += (n * 4 + 255) / 256 * 256; return p; };
   const size_t M = (size_t)Bi * Rq, N = (size_t)Bc * Tq;
-  float* xn = take(M * D); float* yn = take(N * D); float* xinv = take(M); float* yinv = take(N);
+  float* xn = take(M * D); float* yn = take(N * D); float* xinv = take(M); float* yinv = take(N); float* xa = take(M);
   float* A = take(M * N); float* G = take((size_t)Bc * Tq * Tq);
   float *dA = nullptr, *H = nullptr, *dxn = nullptr, *dyn = nullptr;
   if (bwd) { dA = take(M * N); H = take((size_t)Bc * Tq * Tq); dxn = take(M * D); dyn = take(N * D); }
-  if (w) *w = ScanWs{xn, yn, xinv, yinv, A, G, dA, H, dxn, dyn};
+  if (w) *w = ScanWs{xn, yn, xinv, yinv, xa, A, G, dA, H, dxn, dyn};
   return off;
 }
 
-// one wave per (sample, position): normalised row (zero beyond the true length) and 1 / max(norm, eps)
+// one wave per (sample, position): normalised row (zero beyond the true length), 1 / max(norm, eps) and, for the image
+// side (na != nullptr), max(|normalised row|, 1e-8): the region's factor of the cosine's denominator
 __global__ __launch_bounds__(256) void scan_prep_kernel(const float* __restrict__ x, int64_t sb, int64_t sr,
                                                         const int32_t* __restrict__ lens, int B, int Q, int tail, int D,
-                                                        float* __restrict__ xn, float* __restrict__ inv) {
+                                                        float* __restrict__ xn, float* __restrict__ inv, float* __restrict__ na) {
   const int lane = threadIdx.x & 63;
   const int64_t d = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (d >= (int64_t)B * Q) return;
@@ -53,7 +61,7 @@ __global__ __launch_bounds__(256) void scan_prep_kernel(const float* __restrict_
   float* dst = xn + d * D;
   if (p >= L) {
     for (int c = lane; c < D; c += 64) dst[c] = 0.f;
-    if (lane == 0) inv[d] = 0.f;
+    if (lane == 0) { inv[d] = 0.f; if (na) na[d] = 0.f; }
     return;
   }
   const float* src = x + k * sb + (int64_t)(p + 1) * sr;
@@ -62,7 +70,10 @@ __global__ __launch_bounds__(256) void scan_prep_kernel(const float* __restrict_
   ss = wave_sum(ss);
   const float iv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
   for (int c = lane; c < D; c += 64) dst[c] = src[c] * iv;
-  if (lane == 0) inv[d] = iv;
+  if (lane == 0) {
+    inv[d] = iv;
+    if (na) na[d] = (iv < 1e12f) ? 1.0f : fmaxf(sqrtf(ss) * iv, 1e-8f);   // the norm reached eps: a unit vector
+  }
 }
 
 // G[j] = yn_j yn_j^T  (Tq x Tq), one block per caption, D walked in 32-wide slabs
@@ -103,11 +114,11 @@ __global__ __launch_bounds__(256) void scan_gram_kernel(const float* __restrict_
 
 // ---- per-pair evaluation, shared by forward and backward --------------------------------------
 // LDS per block (floats): a[Rq*Tq] block of A, w[Rq*Tq] softmax weights, g[Tq*Tq] Gram matrix,
-// t[Rq*Tq] = W G, c[Tq] column norms, cosv/mv/kv[Rq] row results.
+// t[Rq*Tq] = W G, c[Tq] column norms, cosv/mv/kv[Rq] row results.  dw (backward: dW, then dZ) is t itself.
 struct PairLds {
   float *a, *w, *g, *t, *c, *cosv, *mv, *kv, *dw;
 };
-__device__ __forceinline__ PairLds pair_lds(char* dyn, int Rq, int Tq, bool bwd) {
+__device__ __forceinline__ PairLds pair_lds(char* dyn, int Rq, int Tq) {
   float* p = reinterpret_cast<float*>(dyn);
   PairLds l;
   l.a = p; p += Rq * Tq;
@@ -117,17 +128,17 @@ __device__ __forceinline__ PairLds pair_lds(char* dyn, int Rq, int Tq, bool bwd)
   l.c = p; p += Tq;
   l.cosv = p; p += Rq;
   l.mv = p; p += Rq;
-  l.kv = p; p += Rq;
-  l.dw = bwd ? p : nullptr;
+  l.kv = p;
+  l.dw = l.t;
   return l;
 }
-static size_t pair_lds_bytes(int Rq, int Tq, bool bwd) {
-  return (size_t)((bwd ? 4 : 3) * Rq * Tq + Tq * Tq + Tq + 3 * Rq) * 4;
+static size_t pair_lds_bytes(int Rq, int Tq) {
+  return (size_t)(3 * Rq * Tq + Tq * Tq + Tq + 3 * Rq) * 4;
 }
 
 // Evaluates one pair whose A block and G are already in LDS; fills w, t, c, cosv, mv, kv and returns
-// sum_r cos_r to every thread.  xinv_i[r] > 0 <=> region r is a non-zero vector (|i_r| = 1).
-__device__ __forceinline__ float pair_eval(const PairLds& l, int Tq, int Li, int Lj, const float* __restrict__ xinv_i,
+// sum_r cos_r to every thread.  xa_i[r] = max(|i_r|, 1e-8) of the normalised region (scan_prep_kernel).
+__device__ __forceinline__ float pair_eval(const PairLds& l, int Tq, int Li, int Lj, const float* __restrict__ xa_i,
                                            float* red) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
   for (int w = threadIdx.x; w < Lj; w += blockDim.x) {                    // :137-138 column norms over regions
@@ -159,7 +170,7 @@ __device__ __forceinline__ float pair_eval(const PairLds& l, int Tq, int Li, int
     q = wave_sum(q);
     if (lane == 0) {
       const float n = sqrtf(fmaxf(q, 0.f));
-      const float a = (xinv_i[r] > 0.f) ? 1.0f : 1e-8f;                   // max(|i_r|, 1e-8), F.cosine_similarity
+      const float a = xa_i[r];                                            // max(|i_r|, 1e-8), F.cosine_similarity
       const float m = fmaxf(n, 1e-8f);
       const float cs = u / (a * m);
       l.cosv[r] = cs;
@@ -192,7 +203,7 @@ __device__ __forceinline__ int clip_len(int v, int tail, int Q) {
 
 // forward: one block per pair
 __global__ __launch_bounds__(256) void scan_pair_fwd_kernel(const float* __restrict__ A, const float* __restrict__ G,
-                                                            const float* __restrict__ xinv, const int32_t* __restrict__ im_len,
+                                                            const float* __restrict__ xa, const int32_t* __restrict__ im_len,
                                                             const int32_t* __restrict__ s_len, int Bc, int Rq, int Tq,
                                                             float* __restrict__ S, int64_t ldS) {
   extern __shared__ __attribute__((aligned(16))) char dyn[];
@@ -203,17 +214,17 @@ __global__ __launch_bounds__(256) void scan_pair_fwd_kernel(const float* __restr
     if (threadIdx.x == 0) S[(int64_t)i * ldS + j] = (Li > 0) ? NAN : 0.f;   // empty softmax rows are NaN in the reference
     return;
   }
-  const PairLds l = pair_lds(dyn, Rq, Tq, false);
+  const PairLds l = pair_lds(dyn, Rq, Tq);
   load_block(l.a, A + ((int64_t)i * Rq) * ((int64_t)Bc * Tq) + (int64_t)j * Tq, (int64_t)Bc * Tq, Li, Tq, Tq);
   load_block(l.g, G + (int64_t)j * Tq * Tq, Tq, Lj, Tq, Tq);
   __syncthreads();
-  const float tot = pair_eval(l, Tq, Li, Lj, xinv + (int64_t)i * Rq, red);
+  const float tot = pair_eval(l, Tq, Li, Lj, xa + (int64_t)i * Rq, red);
   if (threadIdx.x == 0) S[(int64_t)i * ldS + j] = tot;
 }
 
 // backward: one block per caption j walks the images with dS[i][j] != 0 in order (deterministic H_j)
 __global__ __launch_bounds__(256) void scan_pair_bwd_kernel(const float* __restrict__ A, const float* __restrict__ G,
-                                                            const float* __restrict__ xinv, const int32_t* __restrict__ im_len,
+                                                            const float* __restrict__ xa, const int32_t* __restrict__ im_len,
                                                             const int32_t* __restrict__ s_len, const float* __restrict__ dS,
                                                             int64_t ld_dS, const float* __restrict__ gscale, int Bi, int Bc,
                                                             int Rq, int Tq, float* __restrict__ dA, float* __restrict__ H) {
@@ -221,8 +232,12 @@ __global__ __launch_bounds__(256) void scan_pair_bwd_kernel(const float* __restr
   __shared__ float red[4];
   const int j = blockIdx.x;
   const int Lj = clip_len(s_len[j], 2, Tq);
-  const PairLds l = pair_lds(dyn, Rq, Tq, true);
-  float* hacc = l.dw + Rq * Tq;                                            // Tq*Tq accumulator behind dw
+  const PairLds l = pair_lds(dyn, Rq, Tq);
+  // H_j accumulates in this block's own global slot.  The zero fill below is written by OTHER threads than those that later add to
+  // an element (fill: e % blockDim; add: (w * Lj + v) % blockDim), so it relies on the __syncthreads() pair that every live
+  // iteration of the image loop runs before its first add (the skip condition is block-uniform); the adds themselves stay on one
+  // thread per element across images.  Keep a barrier between this fill and the first add if the loop is restructured.
+  float* hacc = H + (int64_t)j * Tq * Tq;
   for (int e = threadIdx.x; e < Tq * Tq; e += blockDim.x) hacc[e] = 0.f;
   if (Lj > 0) load_block(l.g, G + (int64_t)j * Tq * Tq, Tq, Lj, Tq, Tq);
   const float gs = gscale ? gscale[0] : 1.f;
@@ -236,7 +251,7 @@ __global__ __launch_bounds__(256) void scan_pair_bwd_kernel(const float* __restr
     const float* Ablk = A + ((int64_t)i * Rq) * ldA + (int64_t)j * Tq;
     load_block(l.a, Ablk, ldA, Li, Tq, Tq);
     __syncthreads();
-    pair_eval(l, Tq, Li, Lj, xinv + (int64_t)i * Rq, red);
+    pair_eval(l, Tq, Li, Lj, xa + (int64_t)i * Rq, red);
     // dW and the softmax backward, row by row
     for (int r = wave; r < Li; r += nw) {
       const float iam = 1.0f / l.mv[r], k = l.kv[r];
@@ -271,8 +286,6 @@ __global__ __launch_bounds__(256) void scan_pair_bwd_kernel(const float* __restr
       hacc[w * Tq + v] = fmaf(g, h, hacc[w * Tq + v]);
     }
   }
-  __syncthreads();
-  for (int e = threadIdx.x; e < Tq * Tq; e += blockDim.x) H[(int64_t)j * Tq * Tq + e] = hacc[e];
 }
 
 // d yn_j -= H_j yn_j   (one block per caption; thread per feature column)
@@ -317,9 +330,9 @@ int scan_common(const float* im, int64_t im_sb, int64_t im_sr, const int32_t* im
                 int64_t s_st, const int32_t* s_len, int Bi, int Bc, int R, int T, int D, const ScanWs& w, hipStream_t st) {
   const int Rq = R - 1, Tq = T - 3;
   hipLaunchKernelGGL(scan_prep_kernel, dim3((unsigned)(((int64_t)Bi * Rq + 3) / 4)), dim3(256), 0, st, im, im_sb, im_sr, im_len,
-                     Bi, Rq, 0, D, w.xn, w.xinv);
+                     Bi, Rq, 0, D, w.xn, w.xinv, w.xa);
   hipLaunchKernelGGL(scan_prep_kernel, dim3((unsigned)(((int64_t)Bc * Tq + 3) / 4)), dim3(256), 0, st, s, s_sb, s_st, s_len, Bc,
-                     Tq, 2, D, w.yn, w.yinv);
+                     Tq, 2, D, w.yn, w.yinv, (float*)nullptr);
   int rc = aladin_check_launch("scan_prep_kernel");
   if (rc) return rc;
   // A = xn yn^T  (Bi*Rq x Bc*Tq), exact fp32
@@ -366,10 +379,10 @@ extern "C" int aladin_scan_fwd(const float* im, int64_t im_sb, int64_t im_sr, co
   hipStream_t st = (hipStream_t)stream;
   rc = scan_common(im, im_sb, im_sr, im_len, s, s_sb, s_st, s_len, Bi, Bc, R, T, D, w, st);
   if (rc) return rc;
-  const size_t lds = pair_lds_bytes(Rq, Tq, false);
+  const size_t lds = pair_lds_bytes(Rq, Tq);
   rc = set_lds((const void*)scan_pair_fwd_kernel, lds, "scan_fwd");
   if (rc) return rc;
-  hipLaunchKernelGGL(scan_pair_fwd_kernel, dim3(Bc, Bi), dim3(256), lds, st, w.A, w.G, w.xinv, im_len, s_len, Bc, Rq, Tq, S, ldS);
+  hipLaunchKernelGGL(scan_pair_fwd_kernel, dim3(Bc, Bi), dim3(256), lds, st, w.A, w.G, w.xa, im_len, s_len, Bc, Rq, Tq, S, ldS);
   return aladin_check_launch("scan_pair_fwd_kernel");
 }
 
@@ -388,10 +401,10 @@ extern "C" int aladin_scan_bwd(const float* im, int64_t im_sb, int64_t im_sr, co
   if (rc) return rc;
   const int64_t M = (int64_t)Bi * Rq, N = (int64_t)Bc * Tq;
   if (hipMemsetAsync(w.dA, 0, (size_t)M * N * 4, st) != hipSuccess) { aladin_set_error("scan_bwd: memset failed"); return ALADIN_ERR_HIP; }
-  const size_t lds = pair_lds_bytes(Rq, Tq, true) + (size_t)Tq * Tq * 4;
+  const size_t lds = pair_lds_bytes(Rq, Tq);
   rc = set_lds((const void*)scan_pair_bwd_kernel, lds, "scan_bwd");
   if (rc) return rc;
-  hipLaunchKernelGGL(scan_pair_bwd_kernel, dim3(Bc), dim3(256), lds, st, w.A, w.G, w.xinv, im_len, s_len, dS, ld_dS, gscale, Bi,
+  hipLaunchKernelGGL(scan_pair_bwd_kernel, dim3(Bc), dim3(256), lds, st, w.A, w.G, w.xa, im_len, s_len, dS, ld_dS, gscale, Bi,
                      Bc, Rq, Tq, w.dA, w.H);
   rc = aladin_check_launch("scan_pair_bwd_kernel");
   if (rc) return rc;

@@ -567,6 +567,8 @@ def _check_sets(im_set, s_seq, im_len, s_len):
         raise ValueError('aladin_amd: im_set (B,R,D) and s_seq (B,T,D) expected')
     if len(im_len) != im_set.shape[0] or len(s_len) != s_seq.shape[0]:
         raise ValueError('aladin_amd: one length per sample expected')
+    if im_set.shape[2] != s_seq.shape[2]:
+        raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (im_set.shape[2], s_seq.shape[2]))
     return lengths_tensor(im_len, im_set.device), lengths_tensor(s_len, im_set.device)
 
 

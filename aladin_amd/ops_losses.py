@@ -133,6 +133,9 @@ def distillation_loss(teacher_scores, student_scores, mode, margin=0.2, threshol
     return _DistillMode.apply(teacher_scores.detach(), student_scores, wb, mode, margin, threshold, stride)
 
 
+ORDER_BWD_PARTNERS = 16384        # order_bwd_kernel keeps one weight per partner row in 64 KiB of LDS
+
+
 class _OrderScores(torch.autograd.Function):
     @staticmethod
     def forward(ctx, im, s):
@@ -165,6 +168,10 @@ def order_scores(im, s):
     _require_gpu(im, s)
     if im.dim() != 2 or s.dim() != 2 or im.shape[1] != s.shape[1]:
         raise ValueError('aladin_amd: (Bi,D) and (Bc,D) embeddings expected')
+    if torch.is_grad_enabled() and (im.requires_grad or s.requires_grad) and max(im.shape[0], s.shape[0]) > ORDER_BWD_PARTNERS:
+        # the limit of aladin_order_sim_bwd (distill.hip), reported here and not inside loss.backward()
+        raise ValueError('aladin_amd: differentiable order scores support at most %d rows per side (got %d x %d); score under '
+                         'torch.no_grad()' % (ORDER_BWD_PARTNERS, im.shape[0], s.shape[0]))
     return _OrderScores.apply(im, s)
 
 

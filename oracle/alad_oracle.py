@@ -291,7 +291,10 @@ def distill_contrastive(teacher, student, margin=0.2, return_grad=False):
     diag = np.diag(M)
     a = margin + M - diag[:, None]
     b = margin + M - diag[None, :]
-    loss = np.float32(np.sum(col_count[None, :] * np.maximum(a, 0)) + np.sum(row_count[:, None] * np.maximum(b, 0)))
+    # a column no row picked / a row no column picked is never index_selected: a NaN there does not reach the loss (no 0 * NaN)
+    with np.errstate(invalid='ignore'):
+        loss = np.float32(np.sum(np.where(col_count[None, :] > 0, col_count[None, :] * np.maximum(a, 0), 0.0))
+                          + np.sum(np.where(row_count[:, None] > 0, row_count[:, None] * np.maximum(b, 0), 0.0)))
     if not return_grad:
         return loss
     ga = col_count[None, :] * (a > 0)
