@@ -32,8 +32,7 @@
 #include "../../include/aladin_hip.h"
 #include "bwd_common.hpp"
 #include "gemm_core.hpp"
-#include "hinge_common.hpp"
-#include "small_heads_common.hpp"
+#include "matrix_losses.hpp"
 
 #define NO_GRAD 255
 
@@ -250,36 +249,39 @@ extern "C" __attribute__((visibility("default"))) int aladin_debug_read_pair_pro
 #define PAIR_STAMP(k) do { } while (0)
 #endif
 
-// SRC == 0: the pairs come from a list (hinge_finish / bwd_compact).
-// SRC == 1: MERGED with the second pass of the hardest-negative hinge.  The pairs follow from the hinge's row / column
-//   statistics directly -- (q, q), (q, argmax_j of row q), (argmax_i of column q, q), each if its term is active -- so the
-//   argmax table no longer waits for hinge_finish: workgroups [0, n_pair_blocks) recompute pairs, the rest run
-//   hinge_finish_body (loss, dense dloss/dS for the row kernel).  One launch less per step, and the element-wise pass
-//   runs under the pair workgroups.
-struct PairHinge {
-  const float* S; int64_t ld; float margin; const float* val; const int* arg; float* loss; float* dS; int B; int n_pair_blocks;
-  float* dST;
+// Where the pair kernel's pairs come from.
+// PairList: a list (hinge_finish / bwd_compact), every workgroup of the grid walks it.
+struct PairList {
+  const int* counter; const int* pairs; int Bc;
+  static constexpr bool merged = false;
+  __device__ __forceinline__ int count() const { return *counter; }
+  __device__ __forceinline__ bool pair_at(int p, int* i, int* j) const { *i = pairs[p] / Bc; *j = pairs[p] % Bc; return true; }
 };
-// SRC == 2: the same merge for the small-batch loss heads (B <= 64): statistics from heads_small_stats_kernel
-//   (st[v][8..9] = value, arg of the alignment hinge), element-wise pass = heads_small_finish_body.
-template <int SRC>
+// PairStats: MERGED with the second pass of the hardest-negative hinge.  The pairs follow from the hinge's row / column
+//   statistics directly (hinge_pair_at), so the argmax table no longer waits for the finish pass: workgroups
+//   [0, n_pair_blocks) recompute pairs, the rest run the finish pass `Fin` (loss, dense dloss/dS for the row kernel): HingeFin
+//   after hinge_stats_kernel, SmallFin after heads_small_stats_kernel (B <= 64).  One launch less per step, and the
+//   element-wise pass runs under the pair workgroups.
+struct PairStats {
+  HingeStats st; int B; int n_pair_blocks;
+  static constexpr bool merged = true;
+  __device__ __forceinline__ int count() const { return 3 * B; }
+  // sample q's three candidates are neighbours in p: (q, q) and (q, j*) share image q's panel in one L2
+  __device__ __forceinline__ bool pair_at(int p, int* i, int* j) const { return hinge_pair_at(st, B, p, i, j); }
+};
+struct NoFin { __device__ __forceinline__ void run(int, int) const {} };
+template <class Src, class Fin>
 __global__ __launch_bounds__(256) void bwd_pair_argmax16_kernel(
     const half_t* __restrict__ xm, const half_t* __restrict__ xe, const half_t* __restrict__ y, int Dp, int mrows, int rem,
     int tpad, int xe_rows, int y_rows, const float* __restrict__ im, int64_t im_sb, int64_t im_sr,
     const int32_t* __restrict__ im_len, const float* __restrict__ s, int64_t s_sb, int64_t s_st,
-    const int32_t* __restrict__ s_len, int Bc, int Rq, int Tq, int D, const int* __restrict__ counter,
-    const int* __restrict__ pairs, uint8_t* __restrict__ table, int tstride, int x_tail,
-    int y_tail, PairHinge hf, SmallFin sf) {
-  if constexpr (SRC == 2) {
-    if ((int)blockIdx.x >= hf.n_pair_blocks) {
-      heads_small_finish_body((int)blockIdx.x - hf.n_pair_blocks, (int)gridDim.x - hf.n_pair_blocks, sf);
-      return;
-    }
-  }
-  if constexpr (SRC == 1) {
-    if ((int)blockIdx.x >= hf.n_pair_blocks) {
-      hinge_finish_body((int)blockIdx.x - hf.n_pair_blocks, (int)gridDim.x - hf.n_pair_blocks, hf.S, hf.ld, hf.B, hf.margin, 1,
-                        hf.val, hf.arg, hf.loss, hf.dS, nullptr, nullptr, hf.dST);
+    const int32_t* __restrict__ s_len, int Bc, int Rq, int Tq, int D, uint8_t* __restrict__ table, int tstride, int x_tail,
+    int y_tail, Src src, Fin fin) {
+  int stride = (int)gridDim.x;
+  if constexpr (Src::merged) {
+    stride = src.n_pair_blocks;
+    if ((int)blockIdx.x >= stride) {
+      fin.run((int)blockIdx.x - stride, (int)gridDim.x - stride);
       return;
     }
   }
@@ -301,8 +303,7 @@ __global__ __launch_bounds__(256) void bwd_pair_argmax16_kernel(
   const int h = lane >> 5, l5 = lane & 31;
   const int wm = wave >> 1, wn = wave & 1;
   PAIR_STAMP(0);
-  const int count = SRC != 0 ? 3 * hf.B : *counter;
-  const int stride = SRC != 0 ? hf.n_pair_blocks : (int)gridDim.x;
+  const int count = src.count();
   // The pair list groups the pairs of one image (hinge_finish / bwd_compact emit row chunks), and blocks
   // are dealt round-robin over the 8 XCDs: give each XCD a CONTIGUOUS eighth of the list so that pairs
   // sharing an image panel meet in the same L2.
@@ -311,23 +312,7 @@ __global__ __launch_bounds__(256) void bwd_pair_argmax16_kernel(
     const int p = (b & 7) * per_xcd + (b >> 3);
     if (p >= count) continue;                          // uniform per workgroup
     int i, j;
-    if constexpr (SRC != 0) {
-      // sample q's three candidates are neighbours in p: (q, q) and (q, j*) share image q's panel in one L2
-      const int q = p / 3, t = p - 3 * q, B = hf.B;
-      auto row_val = [&](int v) { return SRC == 1 ? hf.val[v] : sf.st[(int64_t)v * SB_ST + 8]; };            // v in [0, 2B): rows, columns
-      auto row_arg = [&](int v) { return SRC == 1 ? hf.arg[v] : __float_as_int(sf.st[(int64_t)v * SB_ST + 9]); };
-      const float vr = row_val(q), vc = row_val(B + q);
-      bool active;
-      if (t == 0) { i = q; j = q; active = vr > 0.f || vc > 0.f; }
-      else if (t == 1) { i = q; j = row_arg(q); active = vr > 0.f; }
-      else {
-        i = q; j = q; active = vc > 0.f;
-        if (active) { i = row_arg(B + q); active = !(row_val(i) > 0.f && row_arg(i) == q); }   // else already listed as image i's row pair
-      }
-      if (!active) continue;                           // uniform per workgroup
-    } else {
-      i = pairs[p] / Bc; j = pairs[p] % Bc;
-    }
+    if (!src.pair_at(p, &i, &j)) continue;             // uniform per workgroup
     int Li = im_len[i] - 1 - x_tail; Li = Li < 0 ? 0 : (Li > Rq ? Rq : Li);
     int Lj = s_len[j] - 1 - y_tail; Lj = Lj < 0 ? 0 : (Lj > Tq ? Tq : Lj);
     __syncthreads();                                   // everyone is done with the previous pair's blk
@@ -790,17 +775,15 @@ int aladin_internal_compact_pairs(const float* dS, int64_t ld, int Bi, int Bc, i
   return aladin_check_launch("bwd_compact_kernel");
 }
 
-// the one launch of the fp16 pair kernel: SRC 0 walks (counter, pairs); SRC 1 / 2 derive the pairs from hf / sf and run the
-// element-wise pass in the workgroups past hf.n_pair_blocks
-template <int SRC>
-static int launch_pair16(const BwdProblem& pr, const int* counter, const int* pairs, uint8_t* table, int grid, const PairHinge& hf,
-                         const SmallFin& sf, const char* what) {
+// the one launch of the fp16 pair kernel: `grid` workgroups, those past a PairStats' n_pair_blocks run the finish pass
+template <class Src, class Fin>
+static int launch_pair16(const BwdProblem& pr, uint8_t* table, int grid, const Src& src, const Fin& fin, const char* what) {
   const aladin_align_geom* g = pr.g;
-  hipLaunchKernelGGL(bwd_pair_argmax16_kernel<SRC>, dim3(grid), dim3(256), (size_t)PAIR_STAGES * PairCfg::STAGE_BYTES, pr.st,
+  hipLaunchKernelGGL((bwd_pair_argmax16_kernel<Src, Fin>), dim3(grid), dim3(256), (size_t)PAIR_STAGES * PairCfg::STAGE_BYTES, pr.st,
                      (const half_t*)pr.pk->xm, (const half_t*)pr.pk->xe, (const half_t*)pr.pk->y, g->Dp, g->mrows, g->rem, g->trows,
                      (int)g->xe_rows, (int)g->y_rows, pr.im.data, pr.im.stride_b, pr.im.stride_r, pr.im.len, pr.s.data, pr.s.stride_b,
-                     pr.s.stride_r, pr.s.len, g->Bc, bwd_Rq(g), bwd_Tq(g), g->D, counter, pairs, table, table_stride(bwd_Tq(g)), g->x_tail,
-                     g->y_tail, hf, sf);
+                     pr.s.stride_r, pr.s.len, g->Bc, bwd_Rq(g), bwd_Tq(g), g->D, table, table_stride(bwd_Tq(g)), g->x_tail, g->y_tail,
+                     src, fin);
   return aladin_check_launch(what);
 }
 
@@ -815,25 +798,24 @@ static int hinge_table_check(const BwdProblem& pr, const float* S, int64_t ldS, 
   if (!pr.pair16) { aladin_set_error("hinge_argmax: needs the packed fp16 operands of a class the fp16 pair kernel covers (R' <= 64, <= 64 padded words)"); return ALADIN_ERR_UNSUPPORTED; }
   return ALADIN_OK;
 }
-// small-batch heads: their own statistics kernel ran already (SRC 2)
+// small-batch heads: their own statistics kernel ran already
 static int table_from_small_heads(const BwdProblem& pr, SmallFin sf, const BwdWs& ws) {
   const int B = pr.g->Bc, npb = (3 * B + 7) / 8 * 8;
-  const PairHinge hf = {nullptr, 0, 0.f, nullptr, nullptr, nullptr, nullptr, B, npb, nullptr};
   sf.dST = (float*)ws.pairs;
-  return launch_pair16<2>(pr, nullptr, nullptr, ws.table, npb + cdiv(B * B, 256), hf, sf, "bwd_pair_argmax16_kernel<small heads>");
+  const PairStats src = {hinge_stats_small(sf.st, SB_ST_ALIGN), B, npb};
+  return launch_pair16(pr, ws.table, npb + cdiv(B * B, 256), src, sf, "bwd_pair_argmax16_kernel<small heads>");
 }
-// hardest-negative hinge: statistics, then ONE launch of [pair arg-max | hinge element-wise pass] (SRC 1).  The list region of
+// hardest-negative hinge: statistics, then ONE launch of [pair arg-max | hinge element-wise pass].  The list region of
 // the workspace is free in these stages: it carries dS^T for the row step.
 static int table_from_hinge(const BwdProblem& pr, const float* S, int64_t ldS, float margin, float* loss, float* dS, void* hinge_ws,
                             const BwdWs& ws) {
   const int B = pr.g->Bc;
   if (int rc = aladin_internal_hinge_stats(S, ldS, B, margin, 1, hinge_ws, nullptr, pr.st)) return rc;
-  const float* val = (const float*)hinge_ws;
-  const int* arg = (const int*)(val + 2 * (size_t)B);
   int npb = (3 * B + 7) / 8 * 8; if (npb > 2048) npb = 2048;
   const int nfin = B < 1024 ? B : 1024;
-  const PairHinge hf = {S, ldS, margin, val, arg, loss, dS, B, npb, (float*)ws.pairs};
-  return launch_pair16<1>(pr, nullptr, nullptr, ws.table, npb + nfin, hf, SmallFin{}, "bwd_pair_argmax16_kernel<hinge>");
+  const HingeStats stats = hinge_stats_dense(hinge_ws, B);
+  const HingeFin fin = {S, ldS, B, margin, stats, loss, dS, (float*)ws.pairs};
+  return launch_pair16(pr, ws.table, npb + nfin, PairStats{stats, B, npb}, fin, "bwd_pair_argmax16_kernel<hinge>");
 }
 
 // ---- stage: table from a pair list --------------------------------------------------------------------------------------------------
@@ -842,7 +824,7 @@ static int table_from_list(const BwdProblem& pr, const int* counter, const int* 
   const aladin_align_geom* g = pr.g;
   const int64_t n = (int64_t)g->Bi * g->Bc;
   const int grid = (int)(n < 2048 ? n : 2048);
-  if (pr.pair16) return launch_pair16<0>(pr, counter, pairs, table, grid, PairHinge{}, SmallFin{}, "bwd_pair_argmax16_kernel");
+  if (pr.pair16) return launch_pair16(pr, table, grid, PairList{counter, pairs, g->Bc}, NoFin{}, "bwd_pair_argmax16_kernel");
   hipLaunchKernelGGL(bwd_pair_argmax_kernel, dim3(grid), dim3(256), 0, pr.st, pr.im.data, pr.im.stride_b, pr.im.stride_r, pr.im.len,
                      pr.s.data, pr.s.stride_b, pr.s.stride_r, pr.s.len, g->Bc, bwd_Rq(g), bwd_Tq(g), g->D, counter, pairs, table,
                      table_stride(bwd_Tq(g)), g->x_tail, g->y_tail);

@@ -111,6 +111,55 @@ __device__ __forceinline__ void wave_argmax(float& v, int& idx) {
   ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 1), __builtin_amdgcn_update_dpp(0, idx, 0x121, 0xF, 0xF, false));
 }
 
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Reductions over a 256-thread workgroup (4 waves), result in every thread, fixed order; `red` holds four entries.
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  float t = 0.f;
+  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
+  return t;
+}
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+  v = wave_sum_f64(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
+  return t;
+}
+__device__ __forceinline__ float block_max(float v, float* red) {
+  v = wave_max(v);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  float t = red[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) t = fmaxf(t, red[w]);
+  return t;
+}
+// (max value, smallest index attaining it): wave_argmax, then the four waves' results meet in LDS (redv / redi: four entries
+// each).  One barrier inside; another must pass before the next call.
+__device__ __forceinline__ void block_argmax(float& v, int& idx, float* redv, int* redi) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  wave_argmax(v, idx);
+  if (lane == 0) { redv[wave] = v; redi[wave] = idx; }
+  __syncthreads();
+  v = redv[0]; idx = redi[0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w)
+    if (redv[w] > v || (redv[w] == v && redi[w] < idx)) { v = redv[w]; idx = redi[w]; }
+}
+
 // Sum of squares accumulated with an explicit fma chain.  The packed operands of a row must not depend on WHICH kernel
 // normalised it (dense pack, evaluation store): left as `ss += x*x + y*y + ...` the compiler contracts each site on its own,
 // and two sites agreed bit for bit only by luck.

@@ -11,25 +11,8 @@
 
 namespace {
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // clamp(min=0) / relu as torch computes them: a NaN stays a NaN (fmaxf would drop it), and then rides the sums that run anyway
 __device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
-
-// sum over a 256-thread block, result in every thread; `red` holds 4 doubles
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-  v = wave_sum_f64(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
-  return t;
-}
 
 // ------------------------------------------------------------------------------------------------ mse
 constexpr int MSE_BLOCKS = 256;
@@ -91,14 +74,8 @@ __global__ __launch_bounds__(256) void tcon_pick_kernel(const float* __restrict_
     if (t == q) v = 0.f;
     if (v > best || (v == best && t < besti)) { best = v; besti = t; }
   }
-  wave_argmax(best, besti);
-  if ((threadIdx.x & 63) == 0) { redv[threadIdx.x >> 6] = best; redi[threadIdx.x >> 6] = besti; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w)
-      if (redv[w] > best || (redv[w] == best && redi[w] < besti)) { best = redv[w]; besti = redi[w]; }
-    atomicAdd(is_row ? &col_count[besti] : &row_count[besti], 1);      // integer counts: order-independent
-  }
+  block_argmax(best, besti, redv, redi);
+  if (threadIdx.x == 0) atomicAdd(is_row ? &col_count[besti] : &row_count[besti], 1);      // integer counts: order-independent
 }
 
 // block k: row k (loss share, d student off the diagonal) and column k (the diagonal's share)

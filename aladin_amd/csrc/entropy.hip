@@ -17,7 +17,6 @@
 // Every sum runs in a fixed order and nothing is accumulated with atomics: the same input gives the same bits.
 #include "../../include/aladin_hip.h"
 #include "common.hpp"
-#include "hinge_common.hpp"
 #include "sgemm_tile.hpp"
 
 // No contraction below this line: the backward adds c * u to a row and subtracts c * u from its neighbour's row as separately rounded

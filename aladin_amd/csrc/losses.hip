@@ -6,38 +6,11 @@
 //            its two backward products)
 #include "../../include/aladin_hip.h"
 #include "common.hpp"
-#include "hinge_common.hpp"
+#include "matrix_losses.hpp"
 #include "sgemm_tile.hpp"
 
 // ------------------------------------------------------------------------------------------------
-// block-wide reductions (256 threads = 4 waves)
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max(v);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float t = red[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) t = fmaxf(t, red[w]);
-  return t;
-}
-// (max value, smallest index attaining it)
-__device__ __forceinline__ void block_argmax(float& v, int& idx, float* redv, int* redi) {
-  wave_argmax(v, idx);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) { redv[wave] = v; redi[wave] = idx; }
-  __syncthreads();
-  v = redv[0]; idx = redi[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); ++w)
-    if (redv[w] > v || (redv[w] == v && redi[w] < idx)) { v = redv[w]; idx = redi[w]; }
-}
-
-// ------------------------------------------------------------------------------------------------
-// hinge: stats[b] for rows (b < B) and columns (b >= B)
-//   max_violation: val = max_j cost, arg = argmax          (alad/loss.py:63-65)
-//   sum mode     : val = sum_j cost, arg = #(cost > 0)     (alad/loss.py:67)
+// hinge: the statistics of line b (HingeStats, matrix_losses.hpp), rows (b < B) then columns, as val[2B] | arg[2B]
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void hinge_stats_kernel(const float* __restrict__ S, int64_t ld, int B, float margin,
                                                           int max_violation, float* __restrict__ val,
@@ -53,12 +26,11 @@ __global__ __launch_bounds__(256) void hinge_stats_kernel(const float* __restric
   int besti = 0x7fffffff, cnt = 0;
   for (int t = threadIdx.x; t < B; t += blockDim.x) {
     const float s = is_row ? S[(int64_t)q * ld + t] : S[(int64_t)t * ld + q];
-    const float x = margin + s - diag;
-    // fmaxf drops a NaN; the reference's clamp / max / sum keep it, so a NaN cost makes the line's statistic NaN.  It rides
-    // the reductions that run anyway: as itself in the sum, as (+inf, index -1) in the arg-max, which beats a true +inf.
-    const bool nan = (x != x) && t != q;
-    float c = nan ? INFINITY : fmaxf(x, 0.f);             // :49 / :52
-    if (t == q) c = 0.f;                                  // :55-60
+    const float x = hinge_x(margin, s, diag);
+    // a NaN cost rides the reductions that run anyway: as itself in the sum, as (+inf, index -1) in the arg-max, which beats a
+    // true +inf
+    const bool nan = hinge_cost_is_nan(x, t == q);
+    const float c = nan ? INFINITY : hinge_cost(x, t == q);
     const int ti = nan ? -1 : t;
     if (c > best || (c == best && ti < besti)) { best = c; besti = ti; }
     sum += nan ? x : c;
@@ -75,11 +47,11 @@ __global__ __launch_bounds__(256) void hinge_stats_kernel(const float* __restric
 }
 
 __global__ __launch_bounds__(256) void hinge_finish_kernel(const float* __restrict__ S, int64_t ld, int B, float margin,
-                                                           int max_violation, const float* __restrict__ val,
-                                                           const int* __restrict__ arg, float* __restrict__ loss,
-                                                           float* __restrict__ dS, int* __restrict__ pairs,
-                                                           int* __restrict__ pair_count) {
-  hinge_finish_body((int)blockIdx.x, (int)gridDim.x, S, ld, B, margin, max_violation, val, arg, loss, dS, pairs, pair_count);
+                                                           int max_violation, const void* __restrict__ stats,
+                                                           float* __restrict__ loss, float* __restrict__ dS,
+                                                           int* __restrict__ pairs, int* __restrict__ pair_count) {
+  hinge_finish_body((int)blockIdx.x, (int)gridDim.x, S, ld, B, margin, max_violation, hinge_stats_dense(stats, B), loss, dS, pairs,
+                    pair_count);
 }
 
 extern "C" size_t aladin_hinge_workspace_bytes(int B) { return (size_t)(B > 0 ? B : 0) * 16 + 256; }
@@ -95,14 +67,12 @@ int aladin_internal_hinge_stats(const float* S, int64_t ldS, int B, float margin
 static int hinge_impl(const float* S, int64_t ldS, int B, float margin, int max_violation, float* loss, float* dS,
                       int32_t* pairs, int32_t* pair_count, void* workspace, void* stream) {
   if (!S || !loss || !workspace || B < 1 || ldS < B || (pairs && !pair_count)) { aladin_set_error("hinge: bad argument (B=%d ldS=%lld)", B, (long long)ldS); return ALADIN_ERR_ARG; }
-  float* val = (float*)workspace;
-  int* arg = (int*)(val + 2 * (size_t)B);
   hipStream_t st = (hipStream_t)stream;
   int rc = aladin_internal_hinge_stats(S, ldS, B, margin, max_violation, workspace, pairs ? pair_count : nullptr, st);
   if (rc) return rc;
   const int grid = (dS || pairs) ? (B < 2048 ? B : 2048) : 1;
-  hipLaunchKernelGGL(hinge_finish_kernel, dim3(grid < 1 ? 1 : grid), dim3(256), 0, st, S, ldS, B, margin, max_violation, val,
-                     arg, loss, dS, pairs, pair_count);
+  hipLaunchKernelGGL(hinge_finish_kernel, dim3(grid < 1 ? 1 : grid), dim3(256), 0, st, S, ldS, B, margin, max_violation,
+                     workspace, loss, dS, pairs, pair_count);
   return aladin_check_launch("hinge_finish_kernel");
 }
 
@@ -117,9 +87,7 @@ extern "C" int aladin_hinge_fused(const float* S, int64_t ldS, int B, float marg
 }
 
 // ------------------------------------------------------------------------------------------------
-// listnet.  stats[b][6] = {t_max, t_sumexp, s_max, s_sumexp, W_sum, loss_term}, rows then columns.
-//   P = softmax(T), Q = softmax(tau*M), loss_term = -sum P log(Q + eps), W = P Q / (Q + eps)
-//   dM = (tau / B) [ Q^r Wsum^r - W^r + Q^c Wsum^c - W^c ]           
+// listnet.  stats[b][6] = the ListnetLine of line b (matrix_losses.hpp), rows then columns.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void listnet_stats_kernel(const float* __restrict__ T, int64_t ldt,
                                                             const float* __restrict__ M, int64_t ldm, int B, float tau,
@@ -146,21 +114,18 @@ __global__ __launch_bounds__(256) void listnet_stats_kernel(const float* __restr
   }
   tsum = block_sum(tsum, red);
   ssum = block_sum(ssum, red);
+  ListnetLine line = {tmax, tsum, smax, ssum, 0.f, 0.f};
   float wsum = 0.f, lterm = 0.f;
   for (int t = threadIdx.x; t < B; t += blockDim.x) {
     const int64_t ot = is_row ? (int64_t)q * ldt + t : (int64_t)t * ldt + q;
     const int64_t om = is_row ? (int64_t)q * ldm + t : (int64_t)t * ldm + q;
-    const float P = expf(T[ot] - tmax) / tsum;
-    const float Q = expf(tau * M[om] - smax) / ssum;
-    lterm -= P * logf(Q + eps);
-    wsum += P * Q / (Q + eps);
+    const ListnetElem e = listnet_elem(T[ot], tau * M[om], line, eps);
+    lterm -= listnet_plogq(e, eps);
+    wsum += e.W;
   }
-  lterm = block_sum(lterm, red);
-  wsum = block_sum(wsum, red);
-  if (threadIdx.x == 0) {
-    float* s = stats + (size_t)b * 6;
-    s[0] = tmax; s[1] = tsum; s[2] = smax; s[3] = ssum; s[4] = wsum; s[5] = lterm;
-  }
+  line.loss_term = block_sum(lterm, red);
+  line.w_sum = block_sum(wsum, red);
+  if (threadIdx.x == 0) listnet_line_store(stats + (size_t)b * 6, line);
 }
 
 __global__ __launch_bounds__(256) void listnet_finish_kernel(const float* __restrict__ T, int64_t ldt,
@@ -173,22 +138,15 @@ __global__ __launch_bounds__(256) void listnet_finish_kernel(const float* __rest
     for (int t = threadIdx.x; t < B; t += blockDim.x) { rs += stats[(size_t)t * 6 + 5]; cs += stats[(size_t)(B + t) * 6 + 5]; }
     rs = block_sum(rs, red);
     cs = block_sum(cs, red);
-    if (threadIdx.x == 0) *loss = cs / (float)B + rs / (float)B;       // im_cost + s_cost (alad/loss.py:445)
+    if (threadIdx.x == 0) *loss = listnet_loss(rs, cs, B);
   }
   if (dM == nullptr) return;
   const int64_t n = (int64_t)B * B;
   const float k = tau / (float)B;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
     const int i = (int)(e / B), j = (int)(e % B);
-    const float t = T[(int64_t)i * ldt + j], m = tau * M[(int64_t)i * ldm + j];
-    const float* r = stats + (size_t)i * 6;
-    const float* c = stats + (size_t)(B + j) * 6;
-    const float Pr = expf(t - r[0]) / r[1], Qr = expf(m - r[2]) / r[3];
-    const float Pc = expf(t - c[0]) / c[1], Qc = expf(m - c[2]) / c[3];
-    const float Wr = Pr * Qr / (Qr + eps), Wc = Pc * Qc / (Qc + eps);
-    // the row part and the column part each on its own: summed left to right, a part of size ~1 (P and Q saturated on the same
-    // element) rounds the other one away at 2^-25, which is all there is to the gradient where both softmaxes are one-hot
-    dM[e] = k * (fmaf(Qr, r[4], -Wr) + fmaf(Qc, c[4], -Wc));
+    dM[e] = listnet_grad_at(T[(int64_t)i * ldt + j], tau * M[(int64_t)i * ldm + j], listnet_line(stats + (size_t)i * 6),
+                            listnet_line(stats + (size_t)(B + j) * 6), k, eps);
   }
 }
 
@@ -213,16 +171,15 @@ extern "C" int aladin_listnet_fwd_bwd(const float* teacher, int64_t ld_t, const 
 
 // ------------------------------------------------------------------------------------------------
 // The weighted sum of the loss terms (alad_model.py:450-453) and its backward without element-wise glue launches:
-//   loss_total      total = sum_k w_k * term_k over up to three device scalars (NULL = absent), separate mul / add
+//   loss_total      total = sum_k w_k * term_k over up to three device scalars (NULL = absent; loss_total_add, matrix_losses.hpp)
 //   grad_combine    out[e] = *g * (wa * A[e] + wb * B[e])  (A, B: the dLoss/dM matrices of the matching hinge and of
 //                   ListNet; either may be NULL) and *scale_out = *g * w_scale (the alignment backward's gscale)
 // ------------------------------------------------------------------------------------------------
 __global__ void loss_total_kernel(const float* a, float wa, const float* b, float wb, const float* c, float wc, float* total) {
   float acc = 0.f;
-  // a zero weight drops the term (logged-only, alad_model.py:442-444): 0 * NaN must not reach the total
-  if (a && wa != 0.f) acc = __fadd_rn(acc, __fmul_rn(*a, wa));
-  if (b && wb != 0.f) acc = __fadd_rn(acc, __fmul_rn(*b, wb));
-  if (c && wc != 0.f) acc = __fadd_rn(acc, __fmul_rn(*c, wc));
+  if (a) acc = loss_total_add(acc, *a, wa);
+  if (b) acc = loss_total_add(acc, *b, wb);
+  if (c) acc = loss_total_add(acc, *c, wc);
   *total = acc;
 }
 

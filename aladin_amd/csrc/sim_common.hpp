@@ -150,19 +150,6 @@ __device__ __forceinline__ int row16_imin(int t) {
   return t;
 }
 
-// (max value, smallest index attaining it) over the 256 threads of a workgroup, in every thread: wave_argmax, then the four waves'
-// results meet in LDS (redv / redi: four entries each).  One barrier inside; another must pass before the next call.
-__device__ __forceinline__ void block_argmax(float& v, int& idx, float* redv, int* redi) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  wave_argmax(v, idx);
-  if (lane == 0) { redv[wave] = v; redi[wave] = idx; }
-  __syncthreads();
-  v = redv[0]; idx = redi[0];
-#pragma unroll
-  for (int w = 1; w < 4; ++w)
-    if (redv[w] > v || (redv[w] == v && redi[w] < idx)) { v = redv[w]; idx = redi[w]; }
-}
-
 // The k selection rounds of a 256-thread workgroup over val[0, n_c) in LDS: larger score first, lower position on equal scores.  A NaN
 // slot is RETIRED (live scores are never NaN: the callers map NaN to -inf when they fill the array).  Thread t owns the positions
 // c = t mod 256 and touches no others: it keeps the best of them, every round is a workgroup-wide arg-max of those, and the winner's owner

@@ -14,23 +14,20 @@
 //   backward 2B workgroups: row i of d(img_emb) = sum_j c[i][j] cap_emb[j], row j of d(cap_emb) = sum_i c[i][j]
 //            img_emb[i], c = g_h w_h dM_hinge + g_l w_l dM_listnet + g_M with the upstream gradients read on the
 //            device; it also leaves g * w_align on the device as the scale of the alignment backward.
-// Same formulas as losses.hip's big-batch kernels; every sum runs in a fixed order (deterministic).
+// The formulas are those of losses.hip's big-batch kernels (matrix_losses.hpp); every sum runs in a fixed order (deterministic).
 #include "../../include/aladin_hip.h"
 #include "common.hpp"
-#include "small_heads_common.hpp"
+#include "matrix_losses.hpp"
 
 namespace {
 
-// VSE++ hinge statistics of one row / column vector held a lane per element (alad/loss.py:49-67)
+// VSE++ hinge statistics of one row / column vector held a lane per element (alad/loss.py:49-67): out[0] = value, out[1] = arg
 __device__ __forceinline__ void hinge_vector_stats(float m, float diag, int q, int B, float margin, int max_violation, int lane,
                                                    float* out) {
   const bool live = lane < B;
-  const float x = margin + m - diag;
-  float c = live ? fmaxf(x, 0.f) : 0.f;
-  if (lane == q) c = 0.f;
-  // fmaxf drops a NaN; the reference's clamp / max / sum keep it: a NaN cost anywhere on the line makes its statistic NaN,
-  // as in hinge_stats_kernel (losses.hip)
-  const bool nan = __ballot(live && lane != q && x != x) != 0;
+  const float x = hinge_x(margin, m, diag);
+  const float c = live ? hinge_cost(x, lane == q) : 0.f;
+  const bool nan = __ballot(live && hinge_cost_is_nan(x, lane == q)) != 0;
   if (max_violation) {
     float best = live ? c : -1.f;
     int besti = lane;
@@ -42,7 +39,7 @@ __device__ __forceinline__ void hinge_vector_stats(float m, float diag, int q, i
   }
 }
 
-// st[v][0..1] hinge(M) (val, arg) | [2..7] listnet {t_max, t_sumexp, s_max, s_sumexp, W_sum, loss_term} | [8..9] hinge(S)
+// st[v]: the SB_ST floats of line v (matrix_losses.hpp)
 __global__ __launch_bounds__(256) void heads_small_stats_kernel(const float* __restrict__ img, int64_t ld_i,
                                                                 const float* __restrict__ cap, int64_t ld_c,
                                                                 const float* __restrict__ S, int64_t ld_s, int B, int D,
@@ -114,22 +111,23 @@ __global__ __launch_bounds__(256) void heads_small_stats_kernel(const float* __r
   const float m = (need_m && live) ? mvec[lane] : 0.f;
   float sv = 0.f;
   if ((flags & (SB_ALIGN_HINGE | SB_LISTNET)) && live) sv = is_row ? S[(int64_t)q * ld_s + lane] : S[(int64_t)lane * ld_s + q];
-  if (flags & SB_MATCH_HINGE) hinge_vector_stats(m, mvec[q], q, B, margin, max_violation, lane, out);
-  if (flags & SB_ALIGN_HINGE) hinge_vector_stats(sv, S[(int64_t)q * ld_s + q], q, B, margin, max_violation, lane, out + 8);
+  if (flags & SB_MATCH_HINGE) hinge_vector_stats(m, mvec[q], q, B, margin, max_violation, lane, out + SB_ST_MATCH);
+  if (flags & SB_ALIGN_HINGE) hinge_vector_stats(sv, S[(int64_t)q * ld_s + q], q, B, margin, max_violation, lane, out + SB_ST_ALIGN);
   if (flags & SB_LISTNET) {
     const float t = live ? sv : -INFINITY, sm = live ? tau * m : -INFINITY;
     const float tmax = wave_max(t), smax = wave_max(sm);
     const float te = live ? expf(t - tmax) : 0.f, se = live ? expf(sm - smax) : 0.f;
     const float tsum = wave_sum(te), ssum = wave_sum(se);
-    const float P = te / tsum, Q = se / ssum;
-    const float lterm = wave_sum(live ? -P * logf(Q + eps) : 0.f);
-    const float wsum = wave_sum(live ? P * Q / (Q + eps) : 0.f);
-    if (lane == 0) { out[2] = tmax; out[3] = tsum; out[4] = smax; out[5] = ssum; out[6] = wsum; out[7] = lterm; }
+    ListnetLine line = {tmax, tsum, smax, ssum, 0.f, 0.f};
+    const ListnetElem e = listnet_elem(t, sm, line, eps);
+    line.loss_term = wave_sum(live ? -listnet_plogq(e, eps) : 0.f);
+    line.w_sum = wave_sum(live ? e.W : 0.f);
+    if (lane == 0) listnet_line_store(out + SB_ST_LISTNET, line);
   }
 }
 
 __global__ __launch_bounds__(256) void heads_small_finish_kernel(SmallFin f) {
-  heads_small_finish_body((int)blockIdx.x, (int)gridDim.x, f);
+  f.run((int)blockIdx.x, (int)gridDim.x);
 }
 
 // one workgroup per output row: rows [0, B) of d_img, then rows [0, B) of d_cap

@@ -22,7 +22,6 @@
 #include <float.h>
 #include "../../include/aladin_hip.h"
 #include "common.hpp"
-#include "hinge_common.hpp"
 
 // No contraction: lse_merge must give both partners of a butterfly step the same bits (a * b + c * d contracted is not symmetric).
 #pragma clang fp contract(off)

@@ -1,5 +1,5 @@
 """Inputs and numpy references of the score-matrix tier's tests (tests/test_matrix_losses_cpu.py, tests/test_matrix_losses_gpu.py):
-the VSE++ hinge and ListNet (csrc/losses.hip, hinge_common.hpp), the strided fp32 GEMM behind dot_scores (sgemm_tile.hpp), l2norm
+the VSE++ hinge and ListNet (csrc/losses.hip, matrix_losses.hpp), the strided fp32 GEMM behind dot_scores (sgemm_tile.hpp), l2norm
 (csrc/pool.hip) and the B <= 64 fused heads (csrc/small_batch.hip).
 
 Both tiers build every input HERE, from (kind, shape) alone, so that what the CPU tier proves about an input (exactness in fp32,

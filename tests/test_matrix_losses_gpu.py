@@ -1,5 +1,5 @@
 """GPU tier (-m gpu) of the exact-fp32 score-matrix ops against the oracle and float64 numpy at every edge of their kernels: the
-VSE++ hinge and ListNet (csrc/losses.hip, hinge_common.hpp), aladin_sgemm_strided behind ops.dot_scores (sgemm_tile.hpp), l2norm
+VSE++ hinge and ListNet (csrc/losses.hip, matrix_losses.hpp), aladin_sgemm_strided behind ops.dot_scores (sgemm_tile.hpp), l2norm
 (csrc/pool.hip), order_scores' single-row strides and the B <= 64 fused heads (csrc/small_batch.hip).
 
 Inputs come from tests/helpers/matrix_losses_numpy.py; tests/test_matrix_losses_cpu.py proves what is relied on here:

@@ -28,6 +28,11 @@ the rows of evaluation stores of the same sets and the operands built from them 
 Long sets (LONG_CASES): scores past the tile classes on either side and at the 512-position limit in fp16 and split precision,
 'MwSr' (the roles swapped), the long kernels forced onto a tile-class shape (ops.LONG_PATH_FORCE: scores and gradients), and
 the hinge step of AlignmentContrastiveLoss with the hardest negative and the sum of violations in two backward precisions.
+`save FILE losses` saves the loss heads on the score matrices at the smallest sizes where a kernel's structure changes: the hinge in
+both modes at B = 1, 63, 64, 65, 257 (loss, dS, the pair count and the sorted pair list of the fused call) and the loss bits of a
+B = 65 matrix with a NaN off the diagonal (dS is unspecified there); ListNet at B = 1, 63, 257; the small-batch heads
+(ops.small_batch_match_distill) in both modes at (B, D) = (1, 8), (33, 30), (64, 768); the contrastive distillation mode at B = 2,
+257; the weighted total and the gradient combine through the B > 64 loss heads at B = 65.
 """
 import os
 import sys
@@ -300,6 +305,50 @@ def pack_cases(ops, synth, dev):
     return out
 
 
+def losses_cases(ops, synth, dev):
+    """-> {name: tensor}: the loss heads on B x B score matrices, general path and B <= 64 path."""
+    from aladin_amd import ops_losses
+    out = {}
+    T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    for mv in (True, False):
+        mode = 'max' if mv else 'sum'
+        for B in (1, 63, 64, 65, 257):
+            loss, dS, (pairs, count) = ops_losses._hinge_raw(T(synth.normal((B, B), 7000 + B)), 0.2, mv, True, want_pairs=True)
+            tag = 'hinge-%s-B%d' % (mode, B)
+            out[tag + '/loss'], out[tag + '/dS'], out[tag + '/pair_count'] = loss.cpu(), dS.cpu(), count.cpu()
+            out[tag + '/pairs'] = pairs[:int(count)].sort().values.cpu()
+        S = synth.normal((65, 65), 7100)
+        S[3, 40] = np.nan
+        out['hinge-%s-B65-nan/loss_bits' % mode] = ops_losses._hinge_raw(T(S), 0.2, mv, False)[0].view(torch.int32).cpu()
+        for B, D in ((1, 8), (33, 30), (64, 768)):
+            ge, gc = synth.global_embeddings(B, D, seed=7300 + B, noise=1.0)
+            e, c = T(ge).requires_grad_(True), T(gc).requires_grad_(True)
+            h, l, M = ops.small_batch_match_distill(e, c, T(synth.normal((B, B), 7400 + B)), 0.2, mv)
+            (h + l).backward()
+            tag = 'small-%s-B%d-D%d' % (mode, B, D)
+            out[tag + '/hinge'], out[tag + '/listnet'], out[tag + '/M'] = h.detach().cpu(), l.detach().cpu(), M.detach().cpu()
+            out[tag + '/d_img'], out[tag + '/d_cap'] = e.grad.cpu(), c.grad.cpu()
+    for B in (1, 63, 257):
+        m = T(synth.normal((B, B), 7200 + B)).requires_grad_(True)
+        loss = ops.listnet_loss(T(synth.normal((B, B), 7250 + B)), m)
+        loss.backward()
+        out['listnet-B%d/loss' % B], out['listnet-B%d/dM' % B] = loss.detach().cpu(), m.grad.cpu()
+    for B in (2, 257):
+        m = T(synth.normal((B, B), 7500 + B)).requires_grad_(True)
+        loss = ops.distillation_loss(T(synth.normal((B, B), 7550 + B)), m, 'contrastive', margin=0.2)
+        loss.backward()
+        out['tcon-B%d/loss' % B], out['tcon-B%d/d_student' % B] = loss.detach().cpu(), m.grad.cpu()
+    im, s, il, sl = synth.structured_alignment_batch(65, 34, 50, 64, seed=7600, noise=3.0, ragged=True)
+    ge, gc = synth.global_embeddings(65, 64, seed=7601, noise=1.0)
+    a, b, e, c = (T(x).requires_grad_(True) for x in (im, s, ge, gc))
+    total, terms, _, _ = ops.loss_heads(e, c, a, b, il, sl, 0.2, True, ('matching', 'alignment', 'distillation'),
+                                        {'matching': 0.1, 'alignment': 1.0, 'distillation': 0.75})
+    total.backward()
+    out['heads65/total'], out['heads65/terms'] = total.detach().cpu(), terms.detach().cpu()
+    out['heads65/d_im'], out['heads65/d_s'], out['heads65/d_img'], out['heads65/d_cap'] = a.grad.cpu(), b.grad.cpu(), e.grad.cpu(), c.grad.cpu()
+    return out
+
+
 def adversarial_retrieval(case, n_img, cpi, D, seed):
     """The 'bulk' and 'exact_ties' recipes of tests/test_gpu_parity.py::_adversarial_retrieval."""
     rng = np.random.default_rng(seed)
@@ -408,13 +457,15 @@ def main():
                 continue
             same = torch.equal(a[k], b[k])
             ok &= same
-            print('%-34s %s  max |diff| %.3g' % (k, 'bit-identical' if same else 'DIFFERENT', float((a[k].double() - b[k].double()).abs().max())))
+            comparable = a[k].shape == b[k].shape and a[k].numel() > 0          # not: an empty pair list, two lists of different length
+            diff = float((a[k].double() - b[k].double()).abs().max()) if comparable else float('nan')
+            print('%-34s %s  max |diff| %.3g' % (k, 'bit-identical' if same else 'DIFFERENT', diff))
         sys.exit(0 if ok else 1)
     from aladin_amd import ops, synth
     dev = torch.device('cuda:0')
     out = {}
     group = sys.argv[3] if len(sys.argv) > 3 else 'alignment'
-    assert group in ('alignment', 'retrieval', 'eval', 'pack', 'all'), group
+    assert group in ('alignment', 'retrieval', 'eval', 'pack', 'losses', 'all'), group
     if group in ('alignment', 'all'):
         for tag, ragged, seed in (('full', False, 1234), ('ragged', True, 99)):
             im, s, il, sl = synth.alignment_batch(256, 34, 50, 768, seed=seed, ragged=ragged)
@@ -430,6 +481,8 @@ def main():
         out.update(eval_cases(ops, synth, dev))
     if group in ('pack', 'all'):
         out.update(pack_cases(ops, synth, dev))
+    if group in ('losses', 'all'):
+        out.update(losses_cases(ops, synth, dev))
     torch.save(out, sys.argv[2])
     print('saved', sys.argv[2], {k: float(v.double().sum()) for k, v in out.items()})
 
