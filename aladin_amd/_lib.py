@@ -98,6 +98,10 @@ def _signatures():
         'aladin_recall_ranks': (C.c_int, [p, i64, i32, i32, i32, p, p, p, p, p, p]),
         'aladin_search_workspace_bytes': (sz, [i32, i32, i32, i32, i32]),
         'aladin_search_topk': (C.c_int, [p, i64, p, i64, i32, i32, i32, i32, i32, p, p, p, p]),
+        'aladin_search_index_bytes': (sz, [i32, i32]),
+        'aladin_search_index_build': (C.c_int, [p, i64, i32, i32, p, p]),
+        'aladin_search_index_workspace_bytes': (sz, [i32, i32, i32, i32, i32]),
+        'aladin_search_index_topk': (C.c_int, [p, i32, i32, p, i64, i32, i32, i32, p, p, p, p]),
         'aladin_align_rescore': (C.c_int, [p, p, p, p, i32, i32, p, p, p, p, i32, i32, i32, i32, i32, i32, p, i32, p, p]),
         'aladin_rerank_order': (C.c_int, [p, p, i32, i32, p, p, p]),
         'aladin_align_pair_map': (C.c_int, [p, p, p, p, i32, i32, p, p, p, p, i32, i32, i32, i32, i32, i32, i32, p, i32, p, p, p, i64, p, p, i64,

@@ -92,6 +92,44 @@ struct SimFusedPrep {
 // sim_pack.hip: scale search + split-fp16 packing of both operands into `workspace` (aladin_sim_workspace_bytes); fused: null except
 // for the fused retrieval.  Returns ALADIN_OK or the error of a launch.
 int sim_prepare(const SimIn& in, void* workspace, hipStream_t st, SimPacked* out, SimFusedPrep* fused);
+// sim_pack.hip: ONE operand on its own (the gallery index of search.hip and the queries of a search against it).  The n rows of x are
+// packed [hi | lo] into dst, rows [n, rows_p) zero; the power-of-two scale of x's absmax goes to scale[slot] and, where other_scale is
+// not null, the scale another call left on the device is copied to scale[1 - slot], so a kernel finds the pair where sim_prepare puts
+// it.  The same functions (row_absmax, sim_scale_of, sim_pack_row) as sim_prepare: the same bits for the same matrix.
+struct SimOperand {
+  const float* x;          // n x D, row stride rs floats
+  int64_t rs;
+  int n, rows_p, D;
+  half_t* dst;             // rows_p x 2 Dp
+  float* scale;
+  int slot;                // 0: the operand is the images, 1: the captions
+  const float* other_scale;
+};
+// any n: sim_absmax_kernel into partial (2 x SIM_ABS_BLOCKS floats), then a grid over the rows
+int sim_pack_operand(const SimOperand& op, float* partial, hipStream_t st);
+// n <= 32 (the queries of a small batch): one workgroup finds the absmax and packs -- one launch
+int sim_pack_operand_small(const SimOperand& op, hipStream_t st);
+
+// One segment of a pair's chain from [hi | lo] rows staged in LDS: nblk 32-deep K blocks in K order, fragment reads batched four blocks
+// ahead of their MFMAs (32-bit offsets).
+__device__ __forceinline__ void sim_chain_lds(const half_t* __restrict__ ap, const half_t* __restrict__ bp, int nblk, f32x4& acc) {
+  int k = 0;
+  for (; k + 4 <= nblk; k += 4) {
+    half8 af[4], bf[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      af[u] = *reinterpret_cast<const half8*>(ap + (k + u) * 32);
+      bf[u] = *reinterpret_cast<const half8*>(bp + (k + u) * 32);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[u], bf[u], acc, 0, 0, 0);
+  }
+  for (; k < nblk; ++k) {
+    const half8 af = *reinterpret_cast<const half8*>(ap + k * 32);
+    const half8 bf = *reinterpret_cast<const half8*>(bp + k * 32);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, acc, 0, 0, 0);
+  }
+}
 
 // recall.hip: for each of n_q queries the k best of its n_c <= TOPK_MAX_CAND scores M[q * q_stride + c * c_stride], as aladin_topk
 // (arguments already checked)

@@ -185,25 +185,8 @@ static int sim_pg_group(int cpi, int Dp, size_t* lds_bytes) {
   return G;
 }
 
-// sim_chain_global<4> (retrieval.hip) with 32-bit offsets; kept apart: calling that one changes sim_pack_gt_kernel's instruction text
-__device__ __forceinline__ void sim_chain_lds(const half_t* __restrict__ ap, const half_t* __restrict__ bp, int nblk, f32x4& acc) {
-  int k = 0;
-  for (; k + 4 <= nblk; k += 4) {
-    half8 af[4], bf[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      af[u] = *reinterpret_cast<const half8*>(ap + (k + u) * 32);
-      bf[u] = *reinterpret_cast<const half8*>(bp + (k + u) * 32);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[u], bf[u], acc, 0, 0, 0);
-  }
-  for (; k < nblk; ++k) {
-    const half8 af = *reinterpret_cast<const half8*>(ap + k * 32);
-    const half8 bf = *reinterpret_cast<const half8*>(bp + k * 32);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, acc, 0, 0, 0);
-  }
-}
+// the chain runs through sim_chain_lds (sim_common.hpp): sim_chain_global<4> (retrieval.hip) with 32-bit offsets; kept apart: calling
+// that one changes sim_pack_gt_kernel's instruction text
 
 __global__ __launch_bounds__(256) void sim_pack_gt_kernel(const float* __restrict__ img, int64_t img_rs, int n_img, int Mp,
                                                           const float* __restrict__ cap, int64_t cap_rs, int n_cap, int Np, int D, int Dp,
@@ -311,4 +294,61 @@ int sim_prepare(const SimIn& in, void* workspace, hipStream_t st, SimPacked* out
                      in.cap, in.cap_rs, in.n_cap, p.Np, in.D, p.Dp, ws.partial, ws.scale, ws.a, ws.b, ws.na, ws.nb, f.zero[0], f.nz[0], f.zero[1],
                      f.nz[1], f.zero[2], f.nz[2]);
   return aladin_check_launch("sim_pack_kernel");
+}
+
+// ---- one operand on its own (sim_pack_operand / sim_pack_operand_small, sim_common.hpp) ------------------------------------------------------
+// sim_pack_one_kernel: after sim_absmax_kernel ran with x in the image slot (no captions: their partials are 0), a block packs
+// 4 waves x SIM_PACK_RPW rows of [0, rows_p); rows past n come out zero.  Block 0 publishes the scale pair.
+__global__ __launch_bounds__(256) void sim_pack_one_kernel(const float* __restrict__ x, int64_t rs, int n, int rows_p, int D, int Dp,
+                                                           const float* __restrict__ partial, half_t* __restrict__ dst,
+                                                           float* __restrict__ scale_out, int slot, const float* __restrict__ other_scale) {
+  __shared__ float red[2][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float sc, sc_none;
+  sim_block_scales(partial, red, sc, sc_none);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    scale_out[slot] = sc;
+    if (other_scale) scale_out[1 - slot] = other_scale[0];
+  }
+  const bool vec = (D % 4 == 0) && (rs % 4 == 0) && (((uintptr_t)x & 15) == 0);
+  const int64_t r_first = ((int64_t)blockIdx.x * 4 + wave) * SIM_PACK_RPW;
+  for (int q = 0; q < SIM_PACK_RPW; ++q) {
+    const int64_t r = r_first + q;
+    if (r >= rows_p) return;
+    sim_pack_row(x, rs, r, n, D, Dp, sc, lane, vec, dst + r * 2 * Dp, nullptr);
+  }
+}
+
+// sim_pack_small_kernel: a handful of rows (the queries of a small-batch search): ONE workgroup finds the absmax, the scale and
+// packs the rows -- two launches and 1024 blocks of sim_absmax_kernel saved where the call's whole budget is a few launches.
+__global__ __launch_bounds__(256) void sim_pack_small_kernel(const float* __restrict__ x, int64_t rs, int n, int rows_p, int D, int Dp,
+                                                             half_t* __restrict__ dst, float* __restrict__ scale_out, int slot,
+                                                             const float* __restrict__ other_scale) {
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool vec = (D % 4 == 0) && (rs % 4 == 0) && (((uintptr_t)x & 15) == 0);
+  float m = 0.f;
+  for (int r = wave; r < n; r += 4) m = fmaxf(m, row_absmax(x + (int64_t)r * rs, D, lane, vec));
+  const float sc = sim_scale_of(block_max(m, red));                    // a maximum does not depend on the order it was taken in
+  if (threadIdx.x == 0) {
+    scale_out[slot] = sc;
+    if (other_scale) scale_out[1 - slot] = other_scale[0];
+  }
+  for (int r = wave; r < rows_p; r += 4) sim_pack_row(x, rs, r, n, D, Dp, sc, lane, vec, dst + (int64_t)r * 2 * Dp, nullptr);
+}
+
+int sim_pack_operand_small(const SimOperand& op, hipStream_t st) {
+  hipLaunchKernelGGL(sim_pack_small_kernel, dim3(1), dim3(256), 0, st, op.x, op.rs, op.n, op.rows_p, op.D, round_up(op.D, 64), op.dst, op.scale,
+                     op.slot, op.other_scale);
+  return aladin_check_launch("sim_pack_small_kernel");
+}
+
+int sim_pack_operand(const SimOperand& op, float* partial, hipStream_t st) {
+  hipLaunchKernelGGL(sim_absmax_kernel, dim3(SIM_ABS_BLOCKS), dim3(256), 0, st, op.x, op.rs, op.n, (const float*)nullptr, (int64_t)op.D, 0, op.D,
+                     partial);
+  if (int rc = aladin_check_launch("sim_absmax_kernel")) return rc;
+  const int rows_per_block = 4 * SIM_PACK_RPW;
+  hipLaunchKernelGGL(sim_pack_one_kernel, dim3((op.rows_p + rows_per_block - 1) / rows_per_block), dim3(256), 0, st, op.x, op.rs, op.n, op.rows_p,
+                     op.D, round_up(op.D, 64), (const float*)partial, op.dst, op.scale, op.slot, op.other_scale);
+  return aladin_check_launch("sim_pack_one_kernel");
 }

@@ -183,14 +183,66 @@ def compute_sim_matrix(img, cap, img_len=None, cap_len=None, mode='matching', pr
     raise ValueError("mode must be 'matching' or 'alignment'")
 
 
+class GalleryIndex:
+    """A matching-head gallery prepared once and searched many times (ops.build_search_index): GalleryIndex(gallery, side) with
+    side = 'captions' (image queries, direction 'i2t') or 'images' (caption queries, 't2i').  gallery: an (n, D) array or tensor
+    of embeddings, or a PackedSetStore / StoreView -- then its .glob rows are indexed and the store is kept (.store) for the
+    re-scoring of search_rerank / search_explain.  .search(queries, k) -> (indices, scores), search_topk's; len() = the gallery
+    size.  search_topk / search_rerank / search_explain take it in the gallery position.  The index is a snapshot: it does not
+    follow a store that is appended to afterwards, and it cannot be extended -- build a new one."""
+
+    SIDES = {'captions': ('i2t', 1), 'images': ('t2i', 0)}
+
+    def __init__(self, gallery, side):
+        if side not in self.SIDES:
+            raise ValueError("GalleryIndex: side must be 'captions' or 'images'")
+        self.side = side
+        self.direction, self.dim = self.SIDES[side]
+        self.store = gallery if _is_packed_store(gallery) else None
+        dev = _device()
+        rows = gallery.glob if self.store is not None else gallery
+        with torch.no_grad():
+            self.index = ops.build_search_index(torch.as_tensor(rows).to(dev, torch.float32))
+
+    def __len__(self):
+        return len(self.index)
+
+    def search(self, queries, k=50):
+        """(indices, scores) of the k best gallery items of every query: (n_q, D) embeddings, or a store / view (its .glob rows)."""
+        dev = _device()
+        if _is_packed_store(queries):
+            queries = queries.glob
+        with torch.no_grad():
+            return ops.search_index_topk(self.index, torch.as_tensor(queries).to(dev, torch.float32), k, dim=self.dim,
+                                         return_scores=True)
+
+
+def _gallery_index(images, captions, direction, who):
+    """The GalleryIndex among a search's two sides, checked against the direction: (index or None, queries)."""
+    if isinstance(images, GalleryIndex) and isinstance(captions, GalleryIndex):
+        raise ValueError('%s: one side is the gallery index, the other the queries' % who)
+    for side, gallery, queries in (('captions', captions, images), ('images', images, captions)):
+        if isinstance(gallery, GalleryIndex):
+            if gallery.side != side or gallery.direction != direction:
+                want = 'captions' if direction == 'i2t' else 'images'
+                raise ValueError("%s: direction %r searches a gallery of %s, passed in the %s position; got an index of %s in the %s position"
+                                 % (who, direction, want, want, gallery.side, side))
+            return gallery, queries
+    return None, None
+
+
 def search_topk(images, captions, k=50, direction='i2t'):
     """The k best gallery items of every query from matching-head embeddings, best first: (indices, scores) as an (n_q, k) int32
     and an (n_q, k) float32 device tensor.  direction='i2t': the (n_img, D) images query the (n_cap, D) captions; 't2i': the
     captions query the images.  The same entries as the first k of a stable descending sort of compute_sim_matrix(images,
     captions) along the gallery axis (ties -> lower index; -1 / -inf past the gallery size), without the score matrix:
-    ops.search_topk, up to 589824 gallery items."""
+    ops.search_topk, up to 589824 gallery items.  The gallery side (captions for 'i2t', images for 't2i') may be a GalleryIndex:
+    the same result without packing the gallery again."""
     if direction not in ('i2t', 't2i'):
         raise ValueError("direction must be 'i2t' or 't2i'")
+    index, queries = _gallery_index(images, captions, direction, 'search_topk')
+    if index is not None:
+        return index.search(queries, k)
     dev = _device()
     if _is_packed_store(images) != _is_packed_store(captions):
         raise ValueError('search_topk: pass two stores or two tensors')
@@ -207,9 +259,20 @@ def search_rerank(images, captions, k=50, direction='i2t', shortlist=None):
     float32 device tensor, best first by the ALIGNMENT head.  The shortlist of every query is search_topk(images, captions, k,
     direction) on the stores' matching-head embeddings (shortlist=None) or the caller's (n_q, k) int32 table of gallery
     positions (-1 = none); its pairs are scored straight from the stores (store.alignment_scores_for_pairs) and ordered by
-    score, ties -> the earlier shortlist slot, -1 / -inf last.  Nothing of the size of the (n_q, gallery) grid is computed."""
+    score, ties -> the earlier shortlist slot, -1 / -inf last.  Nothing of the size of the (n_q, gallery) grid is computed.
+    The gallery side may be a GalleryIndex built from a store / view: the shortlist comes from the index, the re-scoring from its
+    store -- the same result."""
     if direction not in ('i2t', 't2i'):
         raise ValueError("direction must be 'i2t' or 't2i'")
+    index, queries = _gallery_index(images, captions, direction, 'search_rerank')
+    if index is not None:
+        if index.store is None:
+            raise ValueError('search_rerank: the gallery index must be built from a store / view (its sets are re-scored), not from a tensor')
+        if not _is_packed_store(queries):
+            raise ValueError('search_rerank: pass two stores / views (encode_data_packed), not tensors')
+        if shortlist is None:
+            shortlist, _ = index.search(queries, k)
+        images, captions = (queries, index.store) if direction == 'i2t' else (index.store, queries)
     if not (_is_packed_store(images) and _is_packed_store(captions)):
         raise ValueError('search_rerank: pass two stores / views (encode_data_packed), not tensors')
     from .store import alignment_scores_for_pairs
@@ -229,6 +292,10 @@ def search_explain(images, captions, k=50, direction='i2t', shortlist=None, top=
     if top < 1:
         raise ValueError('search_explain: top must be >= 1 (got %d)' % top)
     idx, val = search_rerank(images, captions, k, direction, shortlist)
+    if isinstance(images, GalleryIndex):                 # search_rerank has checked it: built from a store, on the direction's side
+        images = images.store
+    if isinstance(captions, GalleryIndex):
+        captions = captions.store
     from .store import alignment_map_for_pairs
     with torch.no_grad():
         return idx, val, alignment_map_for_pairs(images, captions, idx[:, :min(top, idx.shape[1])].contiguous(), direction)

@@ -132,6 +132,73 @@ def search_topk(img, cap, k, dim=1, return_scores=False):
     return (idx, val) if return_scores else idx
 
 
+SEARCH_INDEX_STREAM_MAX_Q = 32       # queries of D <= 768 that take the one-pass route of an index search (STREAM_MAX_Q, csrc/search.hip)
+SEARCH_INDEX_STREAM_MAX_D = 768
+
+
+class SearchIndex:
+    """A gallery packed once for search_index_topk: the device buffer of aladin_search_index_build, the gallery's n and D.
+    Immutable; it cannot be appended to (a new absmax would rescale the rows already packed) -- build a new one."""
+
+    __slots__ = ('buf', 'n', 'D')
+
+    def __init__(self, buf, n, D):
+        self.buf, self.n, self.D = buf, n, D
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def device(self):
+        return self.buf.device
+
+
+def build_search_index(gallery):
+    """SearchIndex of an (n, D) float32 device tensor of matching-head embeddings, images or captions alike: the rows packed
+    [hi | lo] with one power-of-two scale (the operand format of sim_matrix), up to 589824 of them.  The gallery tensor is not
+    needed afterwards."""
+    if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2:
+        raise ValueError('aladin_amd: build_search_index expects an (n,D) embedding tensor')
+    n, D = gallery.shape
+    if n > SEARCH_MAX_GALLERY:
+        raise ValueError('aladin_amd: build_search_index indexes at most %d gallery items (got %d)' % (SEARCH_MAX_GALLERY, n))
+    if n < 1 or D < 1:
+        raise ValueError('aladin_amd: build_search_index needs non-empty embeddings')
+    _require_gpu(gallery)
+    lib = _lib.load()
+    gallery = gallery if gallery.stride(1) == 1 else gallery.contiguous()
+    buf = torch.empty(int(lib.aladin_search_index_bytes(n, D)), dtype=torch.uint8, device=gallery.device)
+    _lib.check(lib.aladin_search_index_build(_ptr(gallery), _ld(gallery), n, D, _ptr(buf), _stream()), 'search_index_build')
+    return SearchIndex(buf, n, D)
+
+
+def search_index_topk(index, queries, k, dim=1, return_scores=False):
+    """search_topk with the gallery taken from a SearchIndex: (n_q, k) int32 indices of each query's k best gallery items, the same
+    ints (and, with return_scores=True, the same score bits) as search_topk on the fp32 gallery.  dim=1: the (n_q, D) queries are
+    images and the index holds captions; dim=0: the queries are captions and the index holds images.  Only the queries are
+    packed per call; up to 32 queries of D <= 768 read the gallery once."""
+    if not isinstance(index, SearchIndex) or queries.dim() != 2 or queries.shape[1] != index.D or dim not in (0, 1):
+        raise ValueError('aladin_amd: search_index_topk expects a SearchIndex, (n_q,D) embeddings of its D and dim 0 or 1')
+    k = int(k)
+    if not 1 <= k <= SEARCH_MAX_K:
+        raise ValueError('aladin_amd: search_index_topk needs 1 <= k <= %d (got %d)' % (SEARCH_MAX_K, k))
+    n_q, D = queries.shape
+    if n_q < 1:
+        raise ValueError('aladin_amd: search_index_topk needs non-empty embeddings')
+    _require_gpu(queries)
+    if queries.device != index.device:
+        raise RuntimeError('aladin_amd: the queries are on %s, the index on %s' % (queries.device, index.device))
+    lib = _lib.load()
+    queries = queries if queries.stride(1) == 1 else queries.contiguous()
+    dev = queries.device
+    idx = torch.empty((n_q, k), dtype=torch.int32, device=dev)
+    val = torch.empty((n_q, k), dtype=torch.float32, device=dev) if return_scores else None
+    ws = _workspace(lib.aladin_search_index_workspace_bytes(n_q, index.n, D, k, dim), dev)
+    _lib.check(lib.aladin_search_index_topk(_ptr(index.buf), index.n, D, _ptr(queries), _ld(queries), n_q, k, dim, _ptr(idx), _ptr(val),
+                                            _ptr(ws), _stream()), 'search_index_topk')
+    return (idx, val) if return_scores else idx
+
+
 RESCORE_MAX_K = 256
 RESCORE_MAX_COUNT = 96               # scored positions per set: the tile classes' limit
 

@@ -529,6 +529,32 @@ ALADIN_API size_t aladin_search_workspace_bytes(int n_img, int n_cap, int D, int
 ALADIN_API int aladin_search_topk(const float* img, int64_t img_row_stride, const float* cap, int64_t cap_row_stride, int n_img,
                        int n_cap, int D, int k, int dim, int32_t* out_idx, float* out_val, void* workspace, void* stream);
 
+/* Gallery index: a matching-head gallery prepared ONCE and searched many times (csrc/search.hip).
+ * aladin_search_index_build packs the n x D fp32 gallery into `index`, a caller-owned device buffer of
+ * aladin_search_index_bytes(n, D) bytes: a header (the power-of-two scale of the gallery's absmax, build scratch) and the rows
+ * in the [hi | lo] operand format of aladin_sim_matrix, zero-padded so that the gallery can stand on either side.  The layout does
+ * not depend on whether the rows are images or captions; the fp32 gallery is not needed after the build.  The index is
+ * IMMUTABLE: a search never writes into it, so searches on several streams may share one.  It cannot be appended to -- a
+ * new absmax would change the scale of the rows already packed; build a new one.
+ * aladin_search_index_topk: aladin_search_topk's contract, word for word, with the gallery taken from the index --
+ *   dim = 1: the n_q rows of q are images and query an index of captions;  dim = 0: they are captions and query an index of images;
+ *   out_idx (n_q x k int32) best first, ties -> lower index, -1 past the gallery size; out_val (may be NULL) the bits
+ *   aladin_sim_matrix would store for the pair, -inf past the gallery size; NaN scores sort last; positions past n count as -inf.
+ * Only the queries are packed per call, their scale from the absmax of the whole n_q x D matrix of the call.  Up to 32 queries
+ * of D <= 768 take ONE pass over the gallery (every row fetched once, scores of all n_q x n pairs left in the workspace, the k
+ * best groups gathered from there); anything else runs the passes of aladin_search_topk on the packed gallery.  The results do
+ * not depend on the route.
+ * Limits: 1 <= k <= 256; at most 36864 groups = 589824 gallery items (ALADIN_ERR_UNSUPPORTED above; _bytes and
+ * _workspace_bytes return 0 for arguments the calls refuse).  Arguments are checked before any launch.  No allocation, no
+ * synchronisation, no atomics: graph-capturable.
+ * workspace: aladin_search_index_workspace_bytes(n_q, n, D, k, dim): the packed queries, 6 bytes per (query, group), 8 per
+ * (query, selected group) and 64 bytes per (query, group) of scores on the one-pass route / 64 per (query, selected group) otherwise. */
+ALADIN_API size_t aladin_search_index_bytes(int n, int D);
+ALADIN_API int aladin_search_index_build(const float* x, int64_t row_stride, int n, int D, void* index, void* stream);
+ALADIN_API size_t aladin_search_index_workspace_bytes(int n_q, int n, int D, int k, int dim);
+ALADIN_API int aladin_search_index_topk(const void* index, int n, int D, const float* q, int64_t q_row_stride, int n_q, int k, int dim,
+                       int32_t* out_idx, float* out_val, void* workspace, void* stream);
+
 /* Two-stage retrieval: alignment-head (MrSw) scores of LISTED pairs straight from two embedding stores, and the order of
  * every query's re-scored shortlist (csrc/rescore.hip).  Work and memory are proportional to n_q * k; no operand is repacked.
  *   x_* / y_*: the image / caption store as aladin_align_pack_store_x / _y take it (rows, offsets, counts, ids: view position
