@@ -113,6 +113,9 @@ def _signatures():
         'aladin_nn_entropy_bwd': (C.c_int, [p, i64, p, i64, i32, i32, p, p, p, p, p, p]),
         'aladin_xent_workspace_bytes': (sz, [i32]),
         'aladin_xent_fwd_bwd': (C.c_int, [p, i64, i32, p, p, p, p, p, p]),
+        'aladin_attdistill_workspace_bytes': (sz, [i32, i32, i32, i32, i32]),
+        'aladin_attdistill_fwd': (C.c_int, [SV, SV, i32, i32, i32, i32, i32, p, i64, i64, i64, i32, i32, p, p, p]),
+        'aladin_attdistill_bwd': (C.c_int, [SV, SV, i32, i32, i32, i32, i32, p, i64, i64, i64, i32, i32, p, GV, GV, p, p]),
     }
 
 

@@ -15,7 +15,8 @@ import torch
 from torch import nn
 
 from . import ops
-from .loss import AlignmentContrastiveLoss, ContrastiveLoss, CrossEntropyCriterion, DistillationLoss, dot_sim
+from .loss import (AlignmentContrastiveLoss, AttentionDistillationLoss, ContrastiveLoss, CrossEntropyCriterion, DistillationLoss,
+                   dot_sim)
 
 
 def pairwise_NNs_inner(x):
@@ -61,9 +62,8 @@ class ALADModel(nn.Module):
             self.auto_weight = True
         if 'distillation' in self.losses_types:                       # :275-276
             self.distillation_loss = DistillationLoss(mode=training['distillation-mode'])
-        if 'attdistillation' in self.losses_types:
-            raise NotImplementedError("aladin_amd: 'attdistillation' is constructed but never used by the "
-                                      "reference's forward_loss (alad_model.py:278-279); not provided")
+        if 'attdistillation' in self.losses_types:                    # :278-279
+            self.att_distillation_loss = AttentionDistillationLoss()
         if 'alignment' in self.losses_types or 'distillation' in self.losses_types:    # :285-288
             self.alignment_criterion = AlignmentContrastiveLoss(
                 margin=training['margin'], measure=training['measure'],
@@ -108,12 +108,16 @@ class ALADModel(nn.Module):
             example_txts = [c.cuda() if isinstance(c, torch.Tensor) else c for c in example_txts]
         return self.img_txt_enc(example_imgs, example_txts)
 
-    def forward_loss(self, img_emb, cap_emb, img_emb_set, cap_emb_seq, img_lengths, cap_lengths, reg_loss, log=True):
+    def forward_loss(self, img_emb, cap_emb, img_emb_set, cap_emb_seq, img_lengths, cap_lengths, reg_loss, log=True,
+                     teacher_attentions=None):
         """reference alad_model.py:371-428.  Same terms, same insertion order, same logger keys; the
         per-term `.item()` host syncs of the reference are batched into one device->host copy.
         log=False (used under HIP-graph capture, where a host sync is illegal: aladin_amd.graphs) skips the
         logger update and leaves the (key, tensor, n) triples in `self.pending_log` for `flush_log()`.
-        The length arguments may be Python lists (as the reference passes them) or int32 device tensors."""
+        The length arguments may be Python lists (as the reference passes them) or int32 device tensors.
+        teacher_attentions ((B, B, Wt, Rt), alad/train.py:340-384): with 'attdistillation' among the loss types the attention
+        distillation term is added; without the tensor the term is skipped (the reference constructs the criterion, :278-279,
+        and never calls it)."""
         losses = {}
         logged = []                                                   # (key, tensor, n)
         img_emb_set = img_emb_set.permute(1, 0, 2)                    # :377-378  (S,B,D) -> (B,S,D) views
@@ -163,6 +167,11 @@ class ALADModel(nn.Module):
                 distillation_loss = self.distillation_loss(teacher_scores, matching_mat)
             losses['distillation'] = distillation_loss
             logged.append(('distillation_loss', distillation_loss, img_emb.size(0)))
+
+        if 'attdistillation' in self.losses_types and teacher_attentions is not None:
+            att_loss = self.att_distillation_loss(img_emb_set, cap_emb_seq, img_lengths, cap_lengths, teacher_attentions)
+            losses['attdistillation'] = att_loss
+            logged.append(('attdistillation_loss', att_loss, img_emb.size(0)))
 
         if 'entropy' in self.losses_types:                            # :410-421
             loss_uniform = ops.nn_entropy_loss(img_emb, cap_emb)
@@ -225,7 +234,7 @@ class ALADModel(nn.Module):
                 and not torch.cuda.is_current_stream_capturing())
 
     def forward_loss_total(self, img_emb, cap_emb, img_emb_set, cap_emb_seq, img_lengths, cap_lengths, reg_loss, epoch=0,
-                           distill_epoch=2, log=True):
+                           distill_epoch=2, log=True, teacher_attentions=None):
         """forward_loss + the weighted sum of forward (alad_model.py:371-428 + :442-453) -> (loss, loss_dict).
         For the shipped configurations the whole thing is ONE autograd node (no element-wise glue; three head launches at
         bs <= 64): the terms of `loss_dict` are then detached values for logging, `loss` carries the graph.
@@ -241,7 +250,8 @@ class ALADModel(nn.Module):
         # long sets at bs <= SMALL_BATCH_MAX: the composed path (the fused small-batch heads stop at the tile classes)
         long_small = img_emb.shape[0] <= ops.SMALL_BATCH_MAX and ops.is_long(img_emb_set.shape[0], cap_emb_seq.shape[0])
         if not self._fused_heads_ok(img_emb) or long_small:
-            d = self.forward_loss(img_emb, cap_emb, img_emb_set, cap_emb_seq, img_lengths, cap_lengths, reg_loss, log=log)
+            d = self.forward_loss(img_emb, cap_emb, img_emb_set, cap_emb_seq, img_lengths, cap_lengths, reg_loss, log=log,
+                                  teacher_attentions=teacher_attentions)
             return self.weighted_total(d, epoch, distill_epoch), d
         wants_matching = 'matching' in self.config['training']['loss-type']
         heads = [k for k in ('matching', 'alignment', 'distillation')
@@ -287,12 +297,12 @@ class ALADModel(nn.Module):
             self.flush_log()
         return total, {k: terms[k] for k in heads}
 
-    def forward(self, example_imgs, example_txts, epoch=0, distill_epoch=2):
-        """reference alad_model.py:430-454."""
+    def forward(self, example_imgs, example_txts, epoch=0, distill_epoch=2, teacher_attentions=None):
+        """reference alad_model.py:430-454.  teacher_attentions: see forward_loss."""
         self.Eiters += 1
         if self._logger is not None:
             self._logger.update('Eit', self.Eiters)
         img_emb_aggr, cap_emb_aggr, img_feats, cap_feats, img_lengths, cap_lengths, regul_loss = \
             self.forward_emb(example_imgs, example_txts)
         return self.forward_loss_total(img_emb_aggr, cap_emb_aggr, img_feats, cap_feats, img_lengths, cap_lengths, regul_loss,
-                                       epoch, distill_epoch)
+                                       epoch, distill_epoch, teacher_attentions=teacher_attentions)

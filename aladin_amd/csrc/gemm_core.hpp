@@ -94,6 +94,21 @@ __device__ __forceinline__ void gemm_stage_k(const half_t* __restrict__ a_rows, 
     __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src), LDS_PTR(stage + chunk * 1024), 16, 0, 0);
   }
 }
+// One 64-deep K step of ONE SAMPLE's panel (its rows are contiguous: an evaluation store, the attention-distillation operands)
+// -> LDS rows [lds_row0, lds_row0 + 8 * ceil(cnt / 8)), pieces p0, p0 + pstep, ...
+// lds_row0 is a multiple of 16, so piece p's swizzle parity is p & 1 (stage_lane_offset above).
+__device__ __forceinline__ void sample_panel_stage(const half_t* __restrict__ panel, int cnt, int64_t ldk, int64_t k_off, char* stage, int lds_row0,
+                                              int p0, int pstep, int lane) {
+  const int r = lane >> 3;
+  const int npieces = (cnt + 7) >> 3;
+  for (int p = p0; p < npieces; p += pstep) {                                  // wave-uniform
+    const int row = min(8 * p + r, cnt - 1);                                   // never past the sample's last row
+    const int logical = (lane & 7) ^ (((r >> 1) ^ ((p & 1) << 2)) & 7);
+    const half_t* src = panel + (int64_t)row * ldk + k_off + logical * 8;
+    __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src), LDS_PTR(stage + (lds_row0 + 8 * p) * 128), 16, 0, 0);
+  }
+}
+
 // K-step -> K offsets of the two panels.  KMapLinear: both panels walk K together (every caller but the split similarity GEMM).
 struct KMapLinear {
   __device__ __forceinline__ int64_t a(int kt) const { return (int64_t)kt * 64; }

@@ -51,20 +51,6 @@ __device__ __forceinline__ RescoreSide rescore_pick(bool first, const RescoreSid
                      first ? a.n : b.n, first ? a.cmax : b.cmax, first ? a.prows : b.prows};
 }
 
-// One 64-deep K step of a sample's panel -> LDS rows [lds_row0, lds_row0 + 8 * ceil(cnt / 8)), pieces p0, p0 + pstep, ...
-// lds_row0 is a multiple of 16, so piece p's swizzle parity is p & 1 (stage_lane_offset, gemm_core.hpp).
-__device__ __forceinline__ void rescore_stage(const half_t* __restrict__ panel, int cnt, int64_t ldk, int64_t k_off, char* stage, int lds_row0,
-                                              int p0, int pstep, int lane) {
-  const int r = lane >> 3;
-  const int npieces = (cnt + 7) >> 3;
-  for (int p = p0; p < npieces; p += pstep) {                                  // wave-uniform
-    const int row = min(8 * p + r, cnt - 1);                                   // never past the sample's last row
-    const int logical = (lane & 7) ^ (((r >> 1) ^ ((p & 1) << 2)) & 7);
-    const half_t* src = panel + (int64_t)row * ldk + k_off + logical * 8;
-    __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src), LDS_PTR(stage + (lds_row0 + 8 * p) * 128), 16, 0, 0);
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // aladin_align_pair_map: the alignment behind a pair's score.  The same accumulation (the body of rescore_kernel below), then
 // per word the best region and per region the best word, (value, index) carried through the reductions rescore_kernel runs on the value
@@ -222,16 +208,16 @@ __global__ __launch_bounds__(512) void rescore_kernel(RescoreSide x, RescoreSide
   // K offsets of the image (a) and caption (b) rows; the shared / gathered panels take the one of their side
   auto k_sh = [&](int kt) { return split ? (dim == 1 ? km.a(kt) : km.b(kt)) : (int64_t)kt * 64; };
   auto k_ga = [&](int kt) { return split ? (dim == 1 ? km.b(kt) : km.a(kt)) : (int64_t)kt * 64; };
-  rescore_stage(pan_s, cnt_s, ldk, k_sh(0), smem, 0, wave, nw, lane);
-  rescore_stage(pan_g, cnt_g, ldk, k_ga(0), smem, g_row0, 0, 1, lane);
+  sample_panel_stage(pan_s, cnt_s, ldk, k_sh(0), smem, 0, wave, nw, lane);
+  sample_panel_stage(pan_g, cnt_g, ldk, k_ga(0), smem, g_row0, 0, 1, lane);
   for (int kt = 0; kt < ktiles; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                          // step kt is in LDS for every wave; every wave is done with step kt - 1
     const char* cur = smem + (kt & 1) * stage_bytes;
     if (kt + 1 < ktiles) {
       char* nxt = smem + ((kt + 1) & 1) * stage_bytes;
-      rescore_stage(pan_s, cnt_s, ldk, k_sh(kt + 1), nxt, 0, wave, nw, lane);
-      rescore_stage(pan_g, cnt_g, ldk, k_ga(kt + 1), nxt, g_row0, 0, 1, lane);
+      sample_panel_stage(pan_s, cnt_s, ldk, k_sh(kt + 1), nxt, 0, wave, nw, lane);
+      sample_panel_stage(pan_g, cnt_g, ldk, k_ga(kt + 1), nxt, g_row0, 0, 1, lane);
     }
 #pragma unroll
     for (int k32 = 0; k32 < 2; ++k32) {

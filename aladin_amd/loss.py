@@ -6,6 +6,7 @@
     DistillationLoss          <- alad/loss.py:359-447
     Contrastive               <- alad/loss.py:29-67 (shared hinge)
     CrossEntropyCriterion     <- alad/loss.py:190-201
+    AttentionDistillationLoss <- alad/loss.py:273-334
     AlignmentCrossEntropyLoss    (not in the reference: the same criterion on the alignment head's scores)
 
 None of them holds parameters or buffers, except DistillationLoss(mode='mse') whose learnable pair
@@ -160,6 +161,21 @@ class CrossEntropyCriterion(nn.Module):
 
     def forward(self, im, s):
         return ops.match_cross_entropy(im, s, self.temperature)
+
+
+class AttentionDistillationLoss(nn.Module):
+    """reference alad/loss.py:273-334: the KL divergence between a cross-encoder teacher's word-by-region attentions
+    (teacher_attentions, (Bi, Bc, Wt, Rt) -- the reference's 69 x 70, sliced in place) and the softmax over regions of the scaled
+    dot products of the fine-grained head's sets, 'batchmean' over every pair's words.  One fused kernel pass per direction: the
+    (Bi, Bc, R - 1, T - 1) tensor of the reference is never formed.  Masked regions drop out of the loss, where the reference
+    evaluates 0 * -inf (NaN on a batch with a short image); the gradients are the reference's whenever the teacher puts no mass on
+    masked regions."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, im_set, s_seq, im_len, s_len, teacher_attentions):
+        return ops.attention_distillation_loss(im_set, s_seq, im_len, s_len, teacher_attentions)
 
 
 class AlignmentCrossEntropyLoss(nn.Module):

@@ -1,6 +1,6 @@
 """Score-matrix losses and the exact-fp32 products over the C ABI: the VSE++ hinge, ListNet and the other distillation modes,
-the symmetric cross-entropy criterion, order / dot similarities, l2norm (reference alad/loss.py:8-67, 190-201, 359-447,
-alad/utils.py:134-139).  Autograd plumbing only."""
+the symmetric cross-entropy criterion, the attention distillation, order / dot similarities, l2norm (reference alad/loss.py:8-67,
+190-201, 273-334, 359-447, alad/utils.py:134-139).  Autograd plumbing only."""
 import ctypes as C
 
 import torch
@@ -357,6 +357,86 @@ def cross_entropy_scores(scores, log_temperature):
     _require_gpu(scores)
     _xent_limit(scores.shape[0])
     return _CrossEntropy.apply(scores, _xent_temperature(log_temperature, scores.device))
+
+
+# ------------------------------------------------------------------------------------------------
+# attention distillation (softmax over regions against a teacher's attention, every pair)
+# ------------------------------------------------------------------------------------------------
+def _attdistill_args(im, s, im_len_t, s_len_t, teacher):
+    """the argument run aladin_attdistill_fwd / _bwd share (the views must stay alive until the call returned)"""
+    from .ops import _set_view
+    sv_im, sv_s = _set_view(im, im_len_t), _set_view(s, s_len_t)
+    Bi, R, D = im.shape
+    Bc, T, _ = s.shape
+    return (sv_im, sv_s), [C.byref(sv_im), C.byref(sv_s), Bi, Bc, R, T, D, _ptr(teacher), teacher.stride(0), teacher.stride(1),
+                           teacher.stride(2), teacher.shape[2], teacher.shape[3]]
+
+
+class _AttDistill(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, im, s, im_len_t, s_len_t, teacher):
+        lib = _lib.load()
+        Bi, R, D = im.shape
+        Bc, T, _ = s.shape
+        loss = torch.empty((), dtype=torch.float32, device=im.device)
+        ws = _workspace(lib.aladin_attdistill_workspace_bytes(Bi, Bc, R, T, D), im.device)
+        keep, args = _attdistill_args(im, s, im_len_t, s_len_t, teacher)
+        _lib.check(lib.aladin_attdistill_fwd(*args, _ptr(loss), _ptr(ws), _stream()), 'attdistill_fwd')
+        ctx.save_for_backward(im, s, im_len_t, s_len_t, teacher, ws)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        from .ops import _grad_view
+        im, s, im_len_t, s_len_t, teacher, ws = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        # fresh row-major outputs; the kernels write every row (slot 0 and masked positions as zeros)
+        d_im = torch.empty(im.shape, dtype=torch.float32, device=im.device) if ctx.needs_input_grad[0] else None
+        d_s = torch.empty(s.shape, dtype=torch.float32, device=s.device) if ctx.needs_input_grad[1] else None
+        if d_im is None and d_s is None:
+            return None, None, None, None, None
+        gv_im = _grad_view(d_im) if d_im is not None else None
+        gv_s = _grad_view(d_s) if d_s is not None else None
+        keep, args = _attdistill_args(im, s, im_len_t, s_len_t, teacher)
+        _lib.check(_lib.load().aladin_attdistill_bwd(*args, _ptr(g), C.byref(gv_im) if gv_im is not None else None,
+                                                     C.byref(gv_s) if gv_s is not None else None, _ptr(ws), _stream()), 'attdistill_bwd')
+        return d_im, d_s, None, None, None
+
+
+def attention_distillation_loss(im_set, s_seq, im_len, s_len, teacher):
+    """KL(teacher attention || softmax over regions of <word, region> / sqrt(D)) over every (image, caption) pair and every word,
+    'batchmean' over the Bi * sum_j (s_len[j] - 1) word rows; replaces AttentionDistillationLoss.forward, reference
+    alad/loss.py:277-334.  teacher: (Bi, Bc, Wt, Rt) float32 with Wt >= T - 1, Rt >= R - 1 and a unit innermost stride, read in
+    place through its strides (the reference's 69 x 70 tensor as it is); it gets no gradient.  One autograd node: three launches
+    forward, one per wanted gradient backward; the (Bi, Bc, R - 1, T - 1) logits tensor is never formed.  Masked regions drop
+    out of the loss (behavioural notes)."""
+    _require_gpu(im_set, s_seq)
+    if im_set.dim() != 3 or s_seq.dim() != 3:
+        raise ValueError('aladin_amd: im_set (B,R,D) and s_seq (B,T,D) expected')
+    if len(im_len) != im_set.shape[0] or len(s_len) != s_seq.shape[0]:
+        raise ValueError('aladin_amd: one length per sample expected')
+    if im_set.shape[2] != s_seq.shape[2]:
+        raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (im_set.shape[2], s_seq.shape[2]))
+    Bi, R, _ = im_set.shape
+    Bc, T, _ = s_seq.shape
+    if Bi < 1 or Bc < 1 or R < 2 or T < 2 or im_set.shape[2] < 1:
+        raise ValueError('aladin_amd: attention distillation needs non-empty sets with at least one scored position, got %s and %s'
+                         % (tuple(im_set.shape), tuple(s_seq.shape)))
+    if R - 1 > _lib.TILE_MAX_SCORED or T - 1 > _lib.TILE_MAX_SCORED:
+        raise ValueError('aladin_amd: attention distillation covers at most %d scored positions per set (got %d regions, %d words)'
+                         % (_lib.TILE_MAX_SCORED, R - 1, T - 1))
+    if not isinstance(teacher, torch.Tensor) or not teacher.is_cuda or teacher.dtype != torch.float32 or teacher.device != im_set.device:
+        raise ValueError('aladin_amd: the teacher attentions must be a float32 tensor on the device of the sets')
+    if teacher.dim() != 4 or teacher.shape[0] != Bi or teacher.shape[1] != Bc or teacher.shape[2] < T - 1 or teacher.shape[3] < R - 1:
+        raise ValueError('aladin_amd: teacher attentions of shape (%d, %d, >= %d, >= %d) expected (images, captions, words, regions), '
+                         'got %s' % (Bi, Bc, T - 1, R - 1, tuple(teacher.shape)))
+    if (teacher.shape[3] > 1 and teacher.stride(3) != 1) or teacher.stride(2) < teacher.shape[3] or min(teacher.stride()) < 0:
+        raise ValueError('aladin_amd: the teacher attentions are read in place and need a unit innermost stride and word rows that '
+                         'do not overlap (got strides %s for shape %s)' % (tuple(teacher.stride()), tuple(teacher.shape)))
+    from .ops import _pad_features
+    im_len_t, s_len_t = lengths_tensor(im_len, im_set.device), lengths_tensor(s_len, im_set.device)
+    im_set, s_seq = _pad_features(im_set, s_seq)
+    return _AttDistill.apply(_rows_inner_contig(im_set), _rows_inner_contig(s_seq), im_len_t, s_len_t, teacher.detach())
 
 
 class _L2Norm(torch.autograd.Function):

@@ -454,6 +454,34 @@ ALADIN_API int aladin_xent_fwd_bwd(const float* S, int64_t ldS, int B, const flo
                         float* d_log_temperature, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Attention distillation -- AttentionDistillationLoss, reference alad/loss.py:273-334 (csrc/attdistill.hip): the fine-grained head's
+ * word-by-region attention against a teacher's, for every (image, caption) pair, without the (Bi, Bc, R - 1, T - 1) logits tensor.
+ * With Rq = R - 1, Tq = T - 1, n_i = clamp(im.len[i] - 1, 0, Rq), m_j = clamp(s.len[j] - 1, 0, Tq) (no tail is dropped here) and
+ *   L[i,j,w,r] = <s[j, w + 1], im[i, r + 1]> / sqrt(D)   (raw dot products),   logp = L - logsumexp_{r < n_i} L,
+ *   P[i,j,w,r] = A[i,j,w,r] / max(sum_{r' < Rq} |A[i,j,w,r']|, 1e-12)          (A = teacher; the norm runs over ALL Rq regions),
+ *   loss = (1 / N) sum_i sum_j sum_{w < m_j} sum_{r < n_i} [ xlogy(P, P) - P logp ],   N = Bi * sum_j m_j  (N = 0: loss 0),
+ *   g    = (softmax_r L * sigma - P) / N,  sigma = sum_{r < n_i} P,
+ *   d im[i, r + 1] = sum_j sum_w g s[j, w + 1] / sqrt(D),   d s[j, w + 1] = sum_i sum_r g im[i, r + 1] / sqrt(D);
+ * slot 0 and positions past a length get exactly 0, the teacher gets no gradient.  Masked regions drop out of the loss (the
+ * reference evaluates 0 * -inf there); an image without a valid region contributes nothing.
+ * teacher: (Bi, Bc, Wt, Rt) fp32, element [i][j][w][r] at teacher[i * t_si + j * t_sj + w * t_sw + r] (strides in floats), read in
+ * place; Wt >= Tq, Rt >= Rq, t_sw >= Rt.  The logits run on unit rows in split precision ([hi | lo] fp16, ~2^-22) times fp32 norms,
+ * fp32 accumulation; the backward's second products run in fp32 on the raw rows.
+ * fwd: three launches (pack, pairs, finish) -> *loss; leaves the operands, (LSE, 1 / L1, sigma) per (i, j, w) and N in `workspace`.
+ * bwd: after fwd on the SAME arguments and workspace; one launch per output (d_im, d_s: either may be NULL), every row written
+ *      exactly once; gscale: a DEVICE scalar, the upstream gradient.
+ * Limits: Bi, Bc >= 1, R, T >= 2, Rq and Tq <= ALADIN_TILE_MAX_SCORED (beyond it ALADIN_ERR_UNSUPPORTED), D >= 1; checked before
+ * any launch.  workspace: aladin_attdistill_workspace_bytes(...) bytes (0 outside the limits), 16-byte aligned, the caller's.  All
+ * on `stream`; no allocation, no synchronisation, no atomics, every sum in a fixed order: deterministic and graph-capturable.
+ * ------------------------------------------------------------------------------------------- */
+ALADIN_API size_t aladin_attdistill_workspace_bytes(int Bi, int Bc, int R, int T, int D);
+ALADIN_API int aladin_attdistill_fwd(const aladin_set* im, const aladin_set* s, int Bi, int Bc, int R, int T, int D, const float* teacher,
+                          int64_t t_si, int64_t t_sj, int64_t t_sw, int Wt, int Rt, float* loss, void* workspace, void* stream);
+ALADIN_API int aladin_attdistill_bwd(const aladin_set* im, const aladin_set* s, int Bi, int Bc, int R, int T, int D, const float* teacher,
+                          int64_t t_si, int64_t t_sj, int64_t t_sw, int Wt, int Rt, const float* gscale, const aladin_set_grad* d_im,
+                          const aladin_set_grad* d_s, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Retrieval similarity matrix  sim = img @ cap.T  at evaluation scale (5000 x 25000 x 768) on the
  * 16-bit MFMA path with a hi/lo fp16 split (3 MFMAs per product, ~fp32 accuracy so that ranks
  * agree with the reference; operand rows are kept [hi | lo] and one accumulator chain runs hi.hi, lo.hi, hi.lo).  Replaces ims.mm(caps.t()), reference alad/recall_auxiliary.py:30,51
