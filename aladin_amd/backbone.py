@@ -106,12 +106,36 @@ class CaptionBertSelfAttention(nn.Module):
     def transpose_for_scores(self, x):
         return x.view(x.size(0), x.size(1), self.num_attention_heads, self.attention_head_size).permute(0, 2, 1, 3)
 
-    def forward(self, hidden_states, attention_mask, head_mask=None, history_state=None):
+    def forward(self, hidden_states, attention_mask, head_mask=None, history_state=None, window=None):
+        """window: None, or (rows, cols, mask2d, fused, out) -- additionally return, as the LAST output, the mean over heads of this
+        layer's attention probabilities for rows = (row0, W) and cols = (col0, Rw) (what alad/train.py:373-376 reads of the last
+        layer).  Fused path (ops.attention_window_mean, csrc/attn_window.hip): the context still comes from SDPA, the window from
+        this layer's query(x) / key(x) outputs in one launch -- taken when the probabilities would not be touched by dropout or a
+        head mask, the mask is the 2-D one (mask2d), nothing needs a gradient and q, k are float32 GPU tensors within the kernel's
+        limits (or the 16-bit states of a float32 model under autocast, cast back first).
+        Otherwise the plain path: THIS layer runs matmul / add / softmax / dropout and the window is cut from its probabilities.
+        fused: None automatic, False the plain path, True raises where the fused path cannot run."""
         kv_in = hidden_states if history_state is None else torch.cat([history_state, hidden_states], dim=1)     # :32-36
-        q = self.transpose_for_scores(self.query(hidden_states))
-        k = self.transpose_for_scores(self.key(kv_in))
+        q_lin, k_lin = self.query(hidden_states), self.key(kv_in)
+        q = self.transpose_for_scores(q_lin)
+        k = self.transpose_for_scores(k_lin)
         v = self.transpose_for_scores(self.value(kv_in))
-        if not self.output_attentions and head_mask is None:
+        win, fused = None, False
+        if window is not None:
+            rows, cols, mask2d, want, win_out = window
+            if want is not False:
+                needs_grad = torch.is_grad_enabled() and (q_lin.requires_grad or k_lin.requires_grad)
+                # the kernel is for float32 models; only the 16-bit states autocast makes of a float32 model are cast back for it
+                # (a half, bfloat16 or double model takes the plain path and keeps its own precision)
+                autocast = (q_lin.is_cuda and torch.is_autocast_enabled() and self.query.weight.dtype == torch.float32
+                            and q_lin.dtype in (torch.float16, torch.bfloat16))
+                if q_lin.is_cuda and not needs_grad and (autocast or q_lin.dtype == torch.float32):
+                    q_lin, k_lin = q_lin.detach().float(), k_lin.detach().float()
+                why = self._window_unfused(q_lin, k_lin, mask2d, head_mask, history_state, needs_grad)
+                if why is not None and want:
+                    raise RuntimeError('aladin_amd.backbone: the fused attention window cannot run: ' + why)
+                fused = why is None
+        if not self.output_attentions and head_mask is None and (window is None or fused):
             p = self.dropout.p if self.training else 0.0
             ctx = F.scaled_dot_product_attention(q, k, v, attn_mask=attention_mask.to(q.dtype), dropout_p=p)
             probs = None
@@ -121,8 +145,35 @@ class CaptionBertSelfAttention(nn.Module):
             if head_mask is not None:
                 probs = probs * head_mask
             ctx = torch.matmul(probs, v)
+        if window is not None:
+            if fused:
+                from . import ops
+                if win_out is None or win_out.dtype == torch.float32:
+                    win = ops.attention_window_mean(q_lin, k_lin, mask2d, self.num_attention_heads, rows, cols, out=win_out)
+                else:                                                   # the caller's tensor is not float32: through a temporary
+                    win = win_out.copy_(ops.attention_window_mean(q_lin, k_lin, mask2d, self.num_attention_heads, rows, cols))
+            else:
+                win = probs.mean(dim=1)[:, rows[0]:rows[0] + rows[1], cols[0]:cols[0] + cols[1]]                     # train.py:373-376
+                if win_out is not None:
+                    win = win_out.copy_(win)
         ctx = ctx.permute(0, 2, 1, 3).contiguous().view(hidden_states.size(0), hidden_states.size(1), self.all_head_size)
-        return (ctx, probs) if self.output_attentions else (ctx,)
+        out = (ctx, probs) if self.output_attentions else (ctx,)
+        return out if window is None else out + (win,)
+
+    def _window_unfused(self, q_lin, k_lin, mask2d, head_mask, history_state, needs_grad):
+        """None where the fused window path applies, else the reason as text."""
+        from . import ops
+        if self.training and self.dropout.p > 0:
+            return 'attention dropout is active (training mode, p = %g)' % self.dropout.p
+        if head_mask is not None:
+            return 'a head mask is given'
+        if history_state is not None:
+            return 'history states lengthen the keys'
+        if mask2d is None:
+            return 'the attention mask is not 2-D'
+        if needs_grad:
+            return 'a gradient is wanted (the kernel has no backward; run under torch.no_grad())'
+        return ops.attention_window_unsupported(q_lin, k_lin, mask2d, self.num_attention_heads)
 
 
 class BertSelfOutput(nn.Module):
@@ -144,8 +195,8 @@ class CaptionBertAttention(nn.Module):
         self.self = CaptionBertSelfAttention(config)
         self.output = BertSelfOutput(config)
 
-    def forward(self, input_tensor, attention_mask, head_mask=None, history_state=None):
-        self_outputs = self.self(input_tensor, attention_mask, head_mask, history_state)
+    def forward(self, input_tensor, attention_mask, head_mask=None, history_state=None, window=None):
+        self_outputs = self.self(input_tensor, attention_mask, head_mask, history_state, window)
         return (self.output(self_outputs[0], input_tensor),) + self_outputs[1:]
 
 
@@ -181,8 +232,8 @@ class CaptionBertLayer(nn.Module):
         self.intermediate = BertIntermediate(config)
         self.output = BertOutput(config)
 
-    def forward(self, hidden_states, attention_mask, head_mask=None, history_state=None):
-        att = self.attention(hidden_states, attention_mask, head_mask, history_state)
+    def forward(self, hidden_states, attention_mask, head_mask=None, history_state=None, window=None):
+        att = self.attention(hidden_states, attention_mask, head_mask, history_state, window)
         return (self.output(self.intermediate(att[0]), att[0]),) + att[1:]
 
 
@@ -195,14 +246,19 @@ class CaptionBertEncoder(nn.Module):
         self.output_hidden_states = config.output_hidden_states
         self.layer = nn.ModuleList([CaptionBertLayer(config) for _ in range(config.num_hidden_layers)])
 
-    def forward(self, hidden_states, attention_mask, head_mask=None, encoder_history_states=None):
+    def forward(self, hidden_states, attention_mask, head_mask=None, encoder_history_states=None, window=None):
+        """window (see CaptionBertSelfAttention.forward) goes to the LAST layer only; its tensor ends the outputs tuple."""
         all_hidden, all_att = (), ()
+        win, last = None, len(self.layer) - 1
         for i, layer in enumerate(self.layer):
             if self.output_hidden_states:
                 all_hidden = all_hidden + (hidden_states,)
             hist = None if encoder_history_states is None else encoder_history_states[i]
-            out = layer(hidden_states, attention_mask, None if head_mask is None else head_mask[i], hist)
+            out = layer(hidden_states, attention_mask, None if head_mask is None else head_mask[i], hist,
+                        window if i == last else None)
             hidden_states = out[0]
+            if window is not None and i == last:
+                win = out[-1]
             if self.output_attentions:
                 all_att = all_att + (out[1],)
         if self.output_hidden_states:
@@ -212,7 +268,7 @@ class CaptionBertEncoder(nn.Module):
             outputs = outputs + (all_hidden,)
         if self.output_attentions:
             outputs = outputs + (all_att,)
-        return outputs
+        return outputs if window is None else outputs + (win,)
 
 
 class BertPooler(nn.Module):
@@ -261,7 +317,22 @@ class BertImgModel(nn.Module):
         self.apply(lambda m: _init_bert_weights(m, config.initializer_range))
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, position_ids=None, head_mask=None,
-                img_feats=None, encoder_history_states=None):
+                img_feats=None, encoder_history_states=None, attention_window=None, attention_window_fused=None, attention_window_out=None):
+        """attention_window = (row0, W, col0, Rw): append, as the LAST element of the outputs, the (B, W, Rw) mean over heads of the
+        LAST layer's attention probabilities for those rows and columns (CaptionBertSelfAttention.forward says how); None (the
+        default) changes nothing.  attention_window_fused: None automatic, False the plain path, True raises where the kernel
+        cannot run.  attention_window_out: None, or the (B, W, Rw) tensor or view the window is written to (and which is returned)."""
+        window = None
+        if attention_window is not None:
+            row0, W, col0, Rw = (int(x) for x in attention_window)
+            L = input_ids.size(1) + (0 if img_feats is None else img_feats.size(1))
+            if row0 < 0 or W < 1 or row0 + W > L or col0 < 0 or Rw < 1 or col0 + Rw > L:
+                raise ValueError('aladin_amd.backbone: attention_window rows [%d, %d) x columns [%d, %d) must be non-empty and lie inside '
+                                 'the %d positions of a sequence' % (row0, row0 + W, col0, col0 + Rw, L))
+            mask2d = attention_mask if attention_mask is not None and attention_mask.dim() == 2 else None
+            if attention_mask is None and img_feats is None:
+                mask2d = torch.ones_like(input_ids)
+            window = ((row0, W), (col0, Rw), mask2d, attention_window_fused, attention_window_out)
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         if token_type_ids is None:
@@ -288,7 +359,10 @@ class BertImgModel(nn.Module):
             if self.use_img_layernorm:
                 e = self.LayerNorm(e)
             x = torch.cat((x, self.dropout(e)), 1)                     # :265-266
-        enc = self.encoder(x, ext, head_mask=head_mask, encoder_history_states=encoder_history_states)
+        if window is None:
+            enc = self.encoder(x, ext, head_mask=head_mask, encoder_history_states=encoder_history_states)
+        else:
+            enc = self.encoder(x, ext, head_mask=head_mask, encoder_history_states=encoder_history_states, window=window)
         return (enc[0], self.pooler(enc[0])) + enc[1:]                 # :274-279
 
 
@@ -367,8 +441,11 @@ class ImageBertForSequenceClassification(nn.Module):
         return model
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, labels=None, position_ids=None, head_mask=None,
-                img_feats=None):
+                img_feats=None, attention_window=None, attention_window_fused=None, attention_window_out=None):
+        """-> (logits,) + the backbone's outputs past the pooled one.  `labels` is accepted and ignored (the reference's teacher
+        call site passes them, alad/train.py:355-362; the reference then puts a loss FIRST, which this model never computes)."""
         outputs = self.bert(input_ids, position_ids=position_ids, token_type_ids=token_type_ids, attention_mask=attention_mask,
-                            head_mask=head_mask, img_feats=img_feats)
+                            head_mask=head_mask, img_feats=img_feats, attention_window=attention_window,
+                            attention_window_fused=attention_window_fused, attention_window_out=attention_window_out)
         logits = self.classifier(self.dropout(outputs[1]))
         return (logits,) + outputs[2:]

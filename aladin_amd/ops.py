@@ -705,6 +705,85 @@ def alignment_sum_scores(im_set, s_seq, im_len, s_len, mean=False):
 
 
 # ------------------------------------------------------------------------------------------------
+# head-mean attention window (the cross-encoder teacher's read of its last layer)
+# ------------------------------------------------------------------------------------------------
+def _window_args(L, rows, cols):
+    (row0, W), (col0, Rw) = (int(rows[0]), int(rows[1])), (int(cols[0]), int(cols[1]))
+    if row0 < 0 or W < 1 or row0 + W > L or col0 < 0 or Rw < 1 or col0 + Rw > L:
+        raise ValueError('aladin_amd: the attention window rows [%d, %d) x columns [%d, %d) must be non-empty and lie inside the '
+                         '%d positions of a sequence' % (row0, row0 + W, col0, col0 + Rw, L))
+    return row0, W, col0, Rw
+
+
+def attention_window_unsupported(q, k, mask, heads):
+    """None if aladin_attn_window_mean covers these tensors, else the reason as text (the limits of include/aladin_hip.h:
+    float32 GPU tensors (N, L, heads * dh) with a unit innermost stride, L <= 256, dh a multiple of 4 up to 128, heads <= 32,
+    a 2-D mask).  backbone.CaptionBertSelfAttention chooses between the kernel and its plain path with it."""
+    if not (isinstance(q, torch.Tensor) and isinstance(k, torch.Tensor) and isinstance(mask, torch.Tensor)):
+        return 'tensors expected'
+    if not (q.is_cuda and k.is_cuda and mask.is_cuda):
+        return 'the kernel runs on the GPU, got tensors on %s / %s / %s' % (q.device, k.device, mask.device)
+    if q.dtype != torch.float32 or k.dtype != torch.float32:
+        return 'float32 q and k expected, got %s / %s' % (q.dtype, k.dtype)
+    if mask.dim() != 2:
+        return 'a 2-D (N, L) mask expected, got %d-D' % mask.dim()
+    if q.dim() != 3 or q.shape != k.shape:
+        return 'q and k of one shape (N, L, heads * dh) expected, got %s / %s' % (tuple(q.shape), tuple(k.shape))
+    N, L, HD = q.shape
+    if N < 1 or L < 1 or heads < 1 or HD % heads:
+        return 'non-empty (N, L, heads * dh) tensors expected, got %s for %d heads' % (tuple(q.shape), heads)
+    dh = HD // heads
+    if L > _lib.ATTN_WINDOW_MAX_L or heads > _lib.ATTN_WINDOW_MAX_HEADS or dh > _lib.ATTN_WINDOW_MAX_DH or dh % 4:
+        return ('L <= %d, heads <= %d and a head size that is a multiple of 4 up to %d expected, got L=%d heads=%d dh=%d'
+                % (_lib.ATTN_WINDOW_MAX_L, _lib.ATTN_WINDOW_MAX_HEADS, _lib.ATTN_WINDOW_MAX_DH, L, heads, dh))
+    return None
+
+
+def attention_window_mean(q, k, mask, heads, rows, cols, out=None):
+    """out[n, i - row0, j - col0] = mean over heads of softmax_j(<q_i, k_j> / sqrt(dh) + (1 - mask_j) * -10000)[i, j] for
+    rows = (row0, W), cols = (col0, Rw): the slice the cross-encoder teacher takes of `attention[-1].mean(dim=1)`, reference
+    alad/train.py:373-376 over oscar/modeling/modeling_bert.py:47-53, from the layer's query(x) / key(x) outputs
+    (N, L, heads * dh) -- one launch, no (N, heads, L, L) tensor.  q and k are read in place through their strides (unit innermost
+    stride required, nothing is copied or transposed); mask: (N, L) of 0 / 1, int64 or float.  out: None or a float32
+    (N, W, Rw) tensor or view with a unit innermost stride (a slice of a larger preallocated tensor); it is returned.
+    No autograd: the teacher is a target."""
+    why = attention_window_unsupported(q, k, mask, heads)
+    if why is not None:
+        raise ValueError('aladin_amd: attention_window_mean: ' + why)
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad):
+        raise RuntimeError('aladin_amd: attention_window_mean has no backward (the teacher is built under torch.no_grad()); '
+                           'detach q and k or disable grad')
+    _require_gpu(q, k)
+    N, L, HD = q.shape
+    row0, W, col0, Rw = _window_args(L, rows, cols)
+    if mask.shape[0] != N or mask.shape[1] != L or mask.device != q.device or k.device != q.device:
+        raise ValueError('aladin_amd: attention_window_mean: a mask of shape (%d, %d) on %s expected, got %s on %s'
+                         % (N, L, q.device, tuple(mask.shape), mask.device))
+    for name, t in (('q', q), ('k', k)):
+        if t.stride(2) != 1 or t.stride(1) < HD or t.stride(0) < 0 or t.data_ptr() % 4:
+            raise ValueError('aladin_amd: attention_window_mean: %s is read in place and needs a unit innermost stride and rows that '
+                             'do not overlap (strides %s for shape %s)' % (name, tuple(t.stride()), tuple(t.shape)))
+    if mask.dtype not in (torch.int64, torch.float32):
+        mask = mask.to(torch.float32)
+    if mask.stride(1) != 1 and L > 1:
+        mask = mask.contiguous()
+    if out is None:
+        out = torch.empty((N, W, Rw), dtype=torch.float32, device=q.device)
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != q.device or tuple(out.shape) != (N, W, Rw):
+            raise ValueError('aladin_amd: attention_window_mean: out must be a float32 (%d, %d, %d) tensor on %s' % (N, W, Rw, q.device))
+        if (Rw > 1 and out.stride(2) != 1) or (W > 1 and out.stride(1) < Rw) or (N > 1 and out.stride(0) < W * out.stride(1)):
+            raise ValueError('aladin_amd: attention_window_mean: out needs a unit innermost stride and rows that do not overlap '
+                             '(strides %s)' % (tuple(out.stride()),))
+    o_sr = out.stride(1) if W > 1 else max(out.stride(1), Rw)
+    o_sn = out.stride(0) if N > 1 else max(out.stride(0), W * o_sr)
+    _lib.check(_lib.load().aladin_attn_window_mean(
+        _ptr(q), q.stride(0), q.stride(1), _ptr(k), k.stride(0), k.stride(1), _ptr(mask), 2, int(mask.dtype == torch.int64),
+        mask.stride(0), N, L, heads, HD // heads, row0, W, col0, Rw, _ptr(out), o_sn, o_sr, _stream()), 'attn_window_mean')
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # One namespace for callers (`from aladin_amd import ops; ops.hinge_loss(...)`): the losses, the loss heads and the retrieval
 # functions live in ops_losses / ops_heads / ops_retrieval (round 5 split of a 1400-line module) and are looked up lazily, so that
 # ops_heads may import THIS module (it builds on the alignment nodes) without a cycle.

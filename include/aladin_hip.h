@@ -482,6 +482,33 @@ ALADIN_API int aladin_attdistill_bwd(const aladin_set* im, const aladin_set* s, 
                           const aladin_set_grad* d_s, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Head-mean attention window -- what the cross-encoder teacher reads of its last layer, reference alad/train.py:373-376 over
+ * oscar/modeling/modeling_bert.py:47-53 (csrc/attn_window.hip), without any (N, H, L, L) probability tensor.  For every
+ * sequence n and head h, with q, k that layer's query(x) / key(x) outputs (N, L, H * dh):
+ *   S[n,h,i,j] = <q[n,i,h*dh:(h+1)*dh], k[n,j,h*dh:(h+1)*dh]> / sqrt(dh) + (1 - mask[n,j]) * (-10000)      j over ALL L columns
+ *   P[n,h,i,:] = softmax_j S[n,h,i,:]
+ *   out[n, i - row0, j - col0] = (1 / H) * sum_h P[n,h,i,j]       row0 <= i < row0 + W,  col0 <= j < col0 + Rw
+ * The mask is ADDED, not selected: a masked column's exponential underflows to exactly 0 wherever the row attends one column,
+ * and a sequence whose mask is all zero keeps a finite softmax over its raw scores, as the reference does.
+ * q, k: fp32, element [n][i][c] at q[n * q_sn + i * q_sr + c] (strides in floats, unit inner stride, 4-byte aligned; 16-byte
+ * loads are taken where pointer and strides allow), read in place.  mask: (N, L) of 0 / 1, row n at element n * mask_sn, unit
+ * inner stride, int64 (mask_is_int64 != 0) or fp32; mask_ndim is the caller's mask rank and must be 2 (the (N, L, L) form of
+ * the reference's model is not covered).  out: fp32, element [n][i][j] at out[n * o_sn + i * o_sr + j]; o_sr >= Rw and
+ * o_sn >= W * o_sr, so a chunk of sequences can land in its slice of a larger tensor; every element written exactly once.
+ * The logits run on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation), the softmax in fp32, the heads are summed
+ * in the order 0 .. H - 1.
+ * Limits: N >= 1, 1 <= L <= ALADIN_ATTN_WINDOW_MAX_L, 1 <= H <= ALADIN_ATTN_WINDOW_MAX_HEADS, dh a multiple of 4 up to
+ * ALADIN_ATTN_WINDOW_MAX_DH, 0 <= row0, W >= 1, row0 + W <= L and the same for the columns; outside them ALADIN_ERR_ARG, checked
+ * before any launch.  One launch on `stream`; no workspace, no allocation, no atomics: deterministic and graph-capturable.
+ * ------------------------------------------------------------------------------------------- */
+#define ALADIN_ATTN_WINDOW_MAX_L 256
+#define ALADIN_ATTN_WINDOW_MAX_DH 128
+#define ALADIN_ATTN_WINDOW_MAX_HEADS 32
+ALADIN_API int aladin_attn_window_mean(const float* q, int64_t q_sn, int64_t q_sr, const float* k, int64_t k_sn, int64_t k_sr,
+                            const void* mask, int mask_ndim, int mask_is_int64, int64_t mask_sn, int N, int L, int H, int dh,
+                            int row0, int W, int col0, int Rw, float* out, int64_t o_sn, int64_t o_sr, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Retrieval similarity matrix  sim = img @ cap.T  at evaluation scale (5000 x 25000 x 768) on the
  * 16-bit MFMA path with a hi/lo fp16 split (3 MFMAs per product, ~fp32 accuracy so that ranks
  * agree with the reference; operand rows are kept [hi | lo] and one accumulator chain runs hi.hi, lo.hi, hi.lo).  Replaces ims.mm(caps.t()), reference alad/recall_auxiliary.py:30,51
