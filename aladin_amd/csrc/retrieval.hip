@@ -818,8 +818,10 @@ static int retrieval_ranks_impl(const float* img, int64_t img_rs, const float* c
   hipStream_t st = (hipStream_t)stream;
   RetrWs rw;
   retr_layout(n_img, n_cap, D, (char*)workspace, &rw);
-  // the pack grid zeroes the statistics and the two rank (= counter) arrays; the arg-max arrays need no zeroing: every entry is
-  // first written (plain store) with its ground-truth pair by the kernel that computes the ground truths
+  // the pack grid zeroes the statistics and the two rank (= counter) arrays.  The arg-max arrays: when the ground truths come out of
+  // the packing pass (sim_pack_gt_kernel) every entry is first written, a plain store, with its ground-truth pair and nothing is
+  // zeroed; when they need their own kernel (below), best_i2t is zeroed first (sim_gt_kernel's tiles meet there in an atomicMax)
+  // and best_t2i is a plain store, one ground truth per column
   SimFusedPrep fused{caps_per_img, rw.gt, rw.best_i2t, rw.best_t2i, {rw.stats, rank_i2t, rank_t2i}, {rw.stats_zero_words, n_img, n_cap}, false};
   SimPacked p;
   int rc = sim_prepare(SimIn{img, img_rs, cap, cap_rs, n_img, n_cap, D}, workspace, st, &p, &fused);

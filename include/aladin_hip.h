@@ -13,6 +13,13 @@
  *   - `stream` is a hipStream_t (PyTorch: torch.cuda.current_stream().cuda_stream); all work is
  *     enqueued asynchronously on it, nothing synchronises, nothing is allocated: outputs and
  *     workspaces are caller-owned, and no pointer is retained after return;
+ *   - output buffers and workspaces may hold ANYTHING on entry (fresh, recycled from another call,
+ *     never zeroed): a call writes exactly the documented extent of each output -- every element of
+ *     it, masked and padded positions included -- zeroes whatever it accumulates into, reads no
+ *     workspace word it has not written in the same call, and stays inside *_workspace_bytes /
+ *     *_index_bytes.  What a workspace holds afterwards is unspecified except where an entry point
+ *     documents it (the arg-max table and dS^T for the backward, the statistics behind
+ *     aladin_retrieval_stats_offset);
  *   - return value: 0 = ok, 1 = bad argument, 2 = unsupported shape, 3 = HIP launch error;
  *     aladin_last_error() gives the message (thread-local).  Never aborts.
  *   - float = IEEE binary32.  16-bit packed operands are IEEE binary16 (fp16): the MFMA path
