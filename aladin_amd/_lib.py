@@ -16,6 +16,8 @@ LAYOUT_AUTO, LAYOUT_TILES, LAYOUT_TILES_WHOLE, LAYOUT_LONG = -1, 0, 1, 2      # 
 TILE_MAX_SCORED = 96                        # ALADIN_TILE_MAX_SCORED
 NN_ENTROPY_MAX_N = 32768                    # ALADIN_NN_ENTROPY_MAX_N
 XENT_MAX_B = 32768                          # ALADIN_XENT_MAX_B
+SEM_MAX_B = 8192                            # ALADIN_SEM_MAX_B
+SEM_MAX_VIOLATION, SEM_COLUMNS_ALIGNED, SEM_MASK_POSITIVES = 1, 2, 4      # ALADIN_SEM_*
 ATTN_WINDOW_MAX_L, ATTN_WINDOW_MAX_DH, ATTN_WINDOW_MAX_HEADS = 256, 128, 32      # ALADIN_ATTN_WINDOW_MAX_*
 BWD_PARTNERS_FP16, BWD_DENSE, BWD_DENSE_GATHER, TRIPLET_BWD_BASE_WORKSPACE, BWD_OWN_ROW_FP16 = 1, 2, 4, 8, 16      # ALADIN_BWD_*, ALADIN_TRIPLET_BWD_BASE_WORKSPACE
 
@@ -114,6 +116,8 @@ def _signatures():
         'aladin_nn_entropy_bwd': (C.c_int, [p, i64, p, i64, i32, i32, p, p, p, p, p, p]),
         'aladin_xent_workspace_bytes': (sz, [i32]),
         'aladin_xent_fwd_bwd': (C.c_int, [p, i64, i32, p, p, p, p, p, p]),
+        'aladin_semantic_hinge_workspace_bytes': (sz, [i32]),
+        'aladin_semantic_hinge_fwd_bwd': (C.c_int, [p, i64, p, i64, i64, i32, f32, f32, i32, p, p, p, p, p, p]),
         'aladin_attdistill_workspace_bytes': (sz, [i32, i32, i32, i32, i32]),
         'aladin_attdistill_fwd': (C.c_int, [SV, SV, i32, i32, i32, i32, i32, p, i64, i64, i64, i32, i32, p, p, p]),
         'aladin_attdistill_bwd': (C.c_int, [SV, SV, i32, i32, i32, i32, i32, p, i64, i64, i64, i32, i32, p, GV, GV, p, p]),

@@ -6,8 +6,10 @@
     DistillationLoss          <- alad/loss.py:359-447
     Contrastive               <- alad/loss.py:29-67 (shared hinge)
     CrossEntropyCriterion     <- alad/loss.py:190-201
+    SemanticContrastiveLoss   <- alad/loss.py:203-270
     AttentionDistillationLoss <- alad/loss.py:273-334
     AlignmentCrossEntropyLoss    (not in the reference: the same criterion on the alignment head's scores)
+    AlignmentSemanticContrastiveLoss (not in the reference: SemanticContrastiveLoss's criterion on the alignment head's scores)
 
 None of them holds parameters or buffers, except DistillationLoss(mode='mse') whose learnable pair
 `wb` the reference has too (:366) and the cross-entropy criteria's `temperature` (:193) -- state dicts
@@ -163,6 +165,43 @@ class CrossEntropyCriterion(nn.Module):
         return ops.match_cross_entropy(im, s, self.temperature)
 
 
+class SemanticContrastiveLoss(nn.Module):
+    """reference alad/loss.py:203-270: the hinge anchored, per row and per column, at ONE positive drawn among the pairs whose
+    relevance exceeds `threshold` (ops.semantic_hinge_loss).  relevances: (B, B) float32 on the GPU, images x captions --
+    rouge.relevance_matrix(captions, caps_per_img=1).t() is the natural source.  Where it differs from the reference
+    (INTEGRATION.md section 2): the draws come from the DEVICE generator (or the caller's `draws`, int32 (2B,)), not from the
+    host stream; a line without a candidate falls back to its diagonal cell instead of raising; column_positives='aligned' and
+    mask_positives=True are options the reference does not have."""
+
+    def __init__(self, margin=0, threshold=0.4, measure=False, max_violation=False, *, column_positives='reference',
+                 mask_positives=False):
+        super().__init__()
+        if measure == 'order':
+            self.sim = order_sim
+        elif measure == 'cosine':
+            self.sim = cosine_sim
+        elif measure == 'dot':
+            self.sim = dot_sim
+        if column_positives not in ops.SEMANTIC_COLUMN_ORDERS:
+            raise ValueError("aladin_amd: column_positives is 'reference' or 'aligned', got %r" % (column_positives,))
+        self.margin = margin
+        self.max_violation = max_violation
+        self.threshold = threshold
+        self.column_positives = column_positives
+        self.mask_positives = mask_positives
+
+    def compute_semantic_contrastive_loss(self, scores, relevances, *, draws=None):
+        return ops.semantic_hinge_loss(scores, relevances, self.margin, self.threshold, self.max_violation, draws=draws,
+                                       column_positives=self.column_positives, mask_positives=self.mask_positives)
+
+    def forward(self, im, s, relevances, return_similarity_mat=False, *, draws=None):
+        scores = self.sim(im, s)
+        loss = self.compute_semantic_contrastive_loss(scores, relevances, draws=draws)
+        if return_similarity_mat:
+            return loss, scores
+        return loss
+
+
 class AttentionDistillationLoss(nn.Module):
     """reference alad/loss.py:273-334: the KL divergence between a cross-encoder teacher's word-by-region attentions
     (teacher_attentions, (Bi, Bc, Wt, Rt) -- the reference's 69 x 70, sliced in place) and the softmax over regions of the scaled
@@ -198,4 +237,34 @@ class AlignmentCrossEntropyLoss(nn.Module):
                              'got %d image sets and %d captions' % (im_set.shape[0], s_seq.shape[0]))
         aggr_similarity = alignment_similarity(self.aggregation, im_set, s_seq, im_len, s_len)
         loss = ops.cross_entropy_scores(aggr_similarity, self.temperature)
+        return (loss, aggr_similarity) if return_similarity_mat else loss
+
+
+class AlignmentSemanticContrastiveLoss(nn.Module):
+    """NOT in the reference: SemanticContrastiveLoss's criterion on the alignment head's score matrix -- the (B, B) matrix
+    AlignmentContrastiveLoss(aggregation=...) scores, through ops.semantic_hinge_loss.  The score functions are
+    AlignmentContrastiveLoss's; their backward here is the dense-dS one, as under AlignmentCrossEntropyLoss (in max_violation mode
+    dS has at most 4 B non-zeros, but they are not the triplet step's diagonal pairs)."""
+
+    def __init__(self, margin=0, threshold=0.4, max_violation=False, aggregation='MrSw', *, column_positives='reference',
+                 mask_positives=False):
+        super().__init__()
+        _check_aggregation(aggregation)
+        if column_positives not in ops.SEMANTIC_COLUMN_ORDERS:
+            raise ValueError("aladin_amd: column_positives is 'reference' or 'aligned', got %r" % (column_positives,))
+        self.margin = margin
+        self.threshold = threshold
+        self.max_violation = max_violation
+        self.aggregation = aggregation
+        self.column_positives = column_positives
+        self.mask_positives = mask_positives
+
+    def forward(self, im_set, s_seq, im_len, s_len, relevances, return_similarity_mat=False, *, draws=None):
+        _check_aggregation(self.aggregation)
+        if im_set.shape[0] != s_seq.shape[0]:
+            raise ValueError('aladin_amd: the semantic contrastive loss needs a square score matrix: one caption per image set, '
+                             'got %d image sets and %d captions' % (im_set.shape[0], s_seq.shape[0]))
+        aggr_similarity = alignment_similarity(self.aggregation, im_set, s_seq, im_len, s_len)
+        loss = ops.semantic_hinge_loss(aggr_similarity, relevances, self.margin, self.threshold, self.max_violation, draws=draws,
+                                       column_positives=self.column_positives, mask_positives=self.mask_positives)
         return (loss, aggr_similarity) if return_similarity_mat else loss

@@ -360,6 +360,82 @@ def cross_entropy_scores(scores, log_temperature):
 
 
 # ------------------------------------------------------------------------------------------------
+# semantic contrastive loss (the hinge anchored at relevance-chosen positives)
+# ------------------------------------------------------------------------------------------------
+SEMANTIC_COLUMN_ORDERS = ('reference', 'aligned')
+
+
+class _SemanticHinge(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, rel, draws, margin, threshold, flags, want_positives):
+        lib = _lib.load()
+        B = scores.shape[0]
+        dev = scores.device
+        sc = scores if (scores.stride(1) == 1 and (B == 1 or scores.stride(0) >= B)) else scores.contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        dS = torch.empty((B, B), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        pos = torch.empty(2 * B, dtype=torch.int32, device=dev) if want_positives else None
+        ws = _workspace(lib.aladin_semantic_hinge_workspace_bytes(B), dev)
+        _lib.check(lib.aladin_semantic_hinge_fwd_bwd(_ptr(sc), _ld(sc), _ptr(rel), rel.stride(0), rel.stride(1), B, float(margin),
+                                                     float(threshold), int(flags), _ptr(draws), _ptr(loss), _ptr(dS), _ptr(pos),
+                                                     _ptr(ws), _stream()), 'semantic_hinge_fwd_bwd')
+        ctx.dS = dS
+        if pos is None:
+            return loss
+        ctx.mark_non_differentiable(pos)
+        return loss, pos
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        return (ctx.dS * g if ctx.dS is not None else None), None, None, None, None, None, None
+
+
+def semantic_hinge_loss(scores, relevances, margin, threshold=0.4, max_violation=False, *, draws=None, generator=None,
+                        column_positives='reference', mask_positives=False, return_positives=False):
+    """The hinge of a square score matrix (images x captions) anchored at relevance-chosen positives; replaces
+    compute_semantic_contrastive_loss, reference alad/loss.py:216-261.  Per row and per column ONE positive is drawn among the
+    pairs with relevances > threshold (the ``draws[v] mod n``-th of a line's n candidates, ascending; a line WITHOUT candidates
+    falls back to its diagonal cell, where the reference raises); the costs are cleared on the diagonal, as the reference's.
+    relevances: (B, B) float32 aligned with scores, read in place through its strides (a transposed or sliced view costs no copy);
+    it gets no gradient.  draws: int32 (2B,) on the device, values in [0, 2^31 - 1): rows, then columns; None draws them there
+    with torch.randint(0, 2**31 - 1, ...) from ``generator`` -- the reference's distribution up to a modulo bias below B / 2^31,
+    not its host stream.  column_positives: 'reference' hands the column anchors out in the row-major order the reference reads
+    them back in, 'aligned' gives column j its own.  mask_positives (not in the reference): the costs are also cleared wherever
+    relevances > threshold.  return_positives: also the int32 (2B,) choice, every row's column then every column's row.
+    One autograd node: four launches ('aligned': three), no host synchronisation."""
+    for t in (scores, relevances):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('aladin_amd: expected a torch.Tensor, got %r' % type(t))
+    if scores.dim() != 2 or scores.shape[0] != scores.shape[1] or scores.shape[0] < 1:
+        raise ValueError('aladin_amd: the semantic contrastive loss needs a square score matrix, got %s' % (tuple(scores.shape),))
+    if tuple(relevances.shape) != tuple(scores.shape):
+        raise ValueError('aladin_amd: relevances of shape %s expected (aligned with the scores), got %s'
+                         % (tuple(scores.shape), tuple(relevances.shape)))
+    B = scores.shape[0]
+    if B > _lib.SEM_MAX_B:
+        raise ValueError('aladin_amd: the semantic contrastive loss covers B <= %d, got %d' % (_lib.SEM_MAX_B, B))
+    if column_positives not in SEMANTIC_COLUMN_ORDERS:
+        raise ValueError("aladin_amd: column_positives is 'reference' or 'aligned', got %r" % (column_positives,))
+    if draws is not None:
+        if not isinstance(draws, torch.Tensor):
+            raise TypeError('aladin_amd: draws is an int32 tensor, got %r' % type(draws))
+        if draws.dtype != torch.int32 or tuple(draws.shape) != (2 * B,):
+            raise ValueError('aladin_amd: draws is an int32 tensor of shape (%d,) (rows, then columns), got %s of shape %s'
+                             % (2 * B, draws.dtype, tuple(draws.shape)))
+    _require_gpu(scores, relevances)
+    if relevances.device != scores.device:
+        raise RuntimeError('aladin_amd: relevances on %s, scores on %s' % (relevances.device, scores.device))
+    if draws is None:
+        draws = torch.randint(0, 2 ** 31 - 1, (2 * B,), dtype=torch.int32, device=scores.device, generator=generator)
+    elif draws.device != scores.device:
+        raise RuntimeError('aladin_amd: draws must live on the device of the scores (%s), got %s; they are read by the kernel'
+                           % (scores.device, draws.device))
+    flags = (_lib.SEM_MAX_VIOLATION if max_violation else 0) | (_lib.SEM_COLUMNS_ALIGNED if column_positives == 'aligned' else 0) \
+        | (_lib.SEM_MASK_POSITIVES if mask_positives else 0)
+    return _SemanticHinge.apply(scores, relevances.detach(), draws.contiguous(), margin, threshold, flags, bool(return_positives))
+
+
+# ------------------------------------------------------------------------------------------------
 # attention distillation (softmax over regions against a teacher's attention, every pair)
 # ------------------------------------------------------------------------------------------------
 def _attdistill_args(im, s, im_len_t, s_len_t, teacher):

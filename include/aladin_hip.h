@@ -461,6 +461,43 @@ ALADIN_API int aladin_xent_fwd_bwd(const float* S, int64_t ldS, int B, const flo
                         float* d_log_temperature, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Semantic contrastive loss on a B x B score matrix with relevance-chosen positives -- SemanticContrastiveLoss, reference
+ * alad/loss.py:203-270 (csrc/semantic.hip).  S: images x captions, row stride ldS, unit column stride.  rel: B x B relevances
+ * aligned with S, element [i][j] at rel[i * rel_row_stride + j * rel_col_stride] (strides in floats, >= 0: a transposed or sliced
+ * view is read in place).  draws: 2B int32 values in [0, 2^31 - 1) on the DEVICE.  Line v < B is row v, line B + j is column j:
+ *   candidates of row i: the columns j with rel[i][j] > threshold, ascending; of column j: the rows, likewise.  NaN compares false.
+ *   pos[v] = the (draws[v] mod n)-th of line v's n candidates.  n = 0: the line's DIAGONAL cell (the reference raises inside
+ *            torch.randint(0, ..); a kernel cannot raise without a synchronisation).
+ *   a1[i]  = S[i][pos[i]].
+ *   a2[m]  = ALADIN_SEM_COLUMNS_ALIGNED: S[pos[B+m]][m].  Otherwise the reference's order (scores[cols_mask].view(B, 1).t() reads
+ *            the chosen cells back row-major): the score at the m-th of the B cells (pos[B+j], j) sorted by (row, column); rank[j]
+ *            is the place of column j's cell.  With diagonal-only positives both orders are the VSE++ hinge.
+ *   cs[i][j] = max(margin + S[i][j] - a1[i], 0),  ci[i][j] = max(margin + S[i][j] - a2[j], 0); both 0 on the DIAGONAL (not at the
+ *            chosen positive, as alad/loss.py:249-254) and, with ALADIN_SEM_MASK_POSITIVES (not in the reference: its TODO at :239),
+ *            wherever rel[i][j] > threshold.
+ *   loss   = sum cs + sum ci;  ALADIN_SEM_MAX_VIOLATION: sum_i max_j cs + sum_j max_i ci, TIES GO TO THE LOWEST INDEX.
+ *   dS[i][j] = [cs active] + [ci active] - [pos[i] == j] nrow[i] - [pos[B+j] == i] ncol[rank[j]]   (B x B contiguous, WRITTEN; may
+ *            be NULL), the gradient of an upstream gradient of 1: nrow / ncol count a line's active terms; under MAX_VIOLATION a
+ *            line counts 1 if its maximum is > 0 and its active element is the arg-max.  Integer valued; no atomics.
+ *   positives (2B int32; may be NULL) receives pos: every row's column, then every column's row.
+ * A NaN cost makes the loss NaN (dS is then unspecified on its row and column).
+ * Limits: 1 <= B <= ALADIN_SEM_MAX_B (beyond it ALADIN_ERR_UNSUPPORTED: the ranking of the column positives compares every pair
+ * of columns), ldS >= B; checked before any launch.
+ * workspace: aladin_semantic_hinge_workspace_bytes(B) bytes (0 outside the limits), 16-byte aligned, the caller's.  Four launches
+ * on `stream` (select, rank, line statistics, finish), three with ALADIN_SEM_COLUMNS_ALIGNED (no ranking); draws and the threshold
+ * comparison are read by the kernels: no host synchronisation, and a replayed graph follows the current draws.  No allocation, no
+ * atomics, every sum in a fixed order: deterministic and graph-capturable.
+ * ------------------------------------------------------------------------------------------- */
+#define ALADIN_SEM_MAX_B 8192
+#define ALADIN_SEM_MAX_VIOLATION 1
+#define ALADIN_SEM_COLUMNS_ALIGNED 2
+#define ALADIN_SEM_MASK_POSITIVES 4
+ALADIN_API size_t aladin_semantic_hinge_workspace_bytes(int B);
+ALADIN_API int aladin_semantic_hinge_fwd_bwd(const float* S, int64_t ldS, const float* rel, int64_t rel_row_stride,
+                                  int64_t rel_col_stride, int B, float margin, float threshold, int flags, const int32_t* draws,
+                                  float* loss, float* dS, int32_t* positives, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Attention distillation -- AttentionDistillationLoss, reference alad/loss.py:273-334 (csrc/attdistill.hip): the fine-grained head's
  * word-by-region attention against a teacher's, for every (image, caption) pair, without the (Bi, Bc, R - 1, T - 1) logits tensor.
  * With Rq = R - 1, Tq = T - 1, n_i = clamp(im.len[i] - 1, 0, Rq), m_j = clamp(s.len[j] - 1, 0, Tq) (no tail is dropped here) and
