@@ -68,6 +68,16 @@ def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
 
 
+def _unit_cols(x):
+    """A 2-D tensor as the kernels read it through _ld: unit column stride and, with more than one row, rows that do not overlap
+    (an expanded row has row stride 0); anything else is copied."""
+    return x if x.stride(1) == 1 and (x.shape[0] == 1 or x.stride(0) >= x.shape[1]) else x.contiguous()
+
+
+def _require_square(scores, what, hint=''):
+    if scores.dim() != 2 or scores.shape[0] != scores.shape[1] or scores.shape[0] < 1:
+        raise ValueError('aladin_amd: %s needs a square score matrix, got %s%s' % (what, tuple(scores.shape), hint))
+
 
 def _workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)

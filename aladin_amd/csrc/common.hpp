@@ -100,15 +100,21 @@ __device__ __forceinline__ int lane_xor16(int v) { return __float_as_int(lane_xo
 // The arg-max combine on the variables `v` / `idx` of the enclosing scope: greater value, or equal value and lower index.
 // Commutative and associative, so a reduction's result does not depend on its order.
 #define ALADIN_ARGMAX_STEP(OV, OI) do { const float ov_ = (OV); const int oi_ = (OI); if (ov_ > v || (ov_ == v && oi_ < idx)) { v = ov_; idx = oi_; } } while (0)
-// (max value, smallest index attaining it) over the 64 lanes of a wave, in every lane.  The combine is symmetric, so after
-// each step partners agree and the DPP rotations act as the xor butterfly (see row16_sum).
-__device__ __forceinline__ void wave_argmax(float& v, int& idx) {
-  ALADIN_ARGMAX_STEP(lane_xor32(v), lane_xor32(idx));
-  ALADIN_ARGMAX_STEP(lane_xor16(v), lane_xor16(idx));
+// (max value, smallest index attaining it) in every lane over a row of 16 lanes, each half-wave, the wave: like row16_sum / half_wave_sum
+// / wave_sum.  The combine is symmetric, so after each step partners agree and the DPP rotations act as the xor butterfly (row16_sum).
+__device__ __forceinline__ void row16_argmax(float& v, int& idx) {
   ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 8), __builtin_amdgcn_update_dpp(0, idx, 0x128, 0xF, 0xF, false));
   ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 4), __builtin_amdgcn_update_dpp(0, idx, 0x124, 0xF, 0xF, false));
   ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 2), __builtin_amdgcn_update_dpp(0, idx, 0x122, 0xF, 0xF, false));
   ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 1), __builtin_amdgcn_update_dpp(0, idx, 0x121, 0xF, 0xF, false));
+}
+__device__ __forceinline__ void half_wave_argmax(float& v, int& idx) {
+  ALADIN_ARGMAX_STEP(lane_xor16(v), lane_xor16(idx));
+  row16_argmax(v, idx);
+}
+__device__ __forceinline__ void wave_argmax(float& v, int& idx) {
+  ALADIN_ARGMAX_STEP(lane_xor32(v), lane_xor32(idx));
+  half_wave_argmax(v, idx);
 }
 
 __device__ __forceinline__ double wave_sum_f64(double v) {

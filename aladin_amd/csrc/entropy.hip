@@ -62,12 +62,7 @@ __global__ __launch_bounds__(1024) void nn_gram_kernel(NNSources s, int D, NNPar
       int idx = cbase + col;
       if (rbase + row == idx) v = -1.0f;                               // the reference's diagonal fill: -1, not -inf
       if (col >= Nc) { v = -INFINITY; idx = 0x7fffffff; }
-      // over the 32 lanes of this half-wave (one row of the accumulator), the butterfly of wave_argmax without its first step
-      ALADIN_ARGMAX_STEP(lane_xor16(v), lane_xor16(idx));
-      ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 8), __builtin_amdgcn_update_dpp(0, idx, 0x128, 0xF, 0xF, false));
-      ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 4), __builtin_amdgcn_update_dpp(0, idx, 0x124, 0xF, 0xF, false));
-      ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 2), __builtin_amdgcn_update_dpp(0, idx, 0x122, 0xF, 0xF, false));
-      ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 1), __builtin_amdgcn_update_dpp(0, idx, 0x121, 0xF, 0xF, false));
+      half_wave_argmax(v, idx);                                        // this half-wave holds one row of the accumulator
       if ((lane & 31) == r) { mv = v; mi = idx; }                      // lane r of each half keeps register r's row
     }
   }

@@ -1,6 +1,6 @@
 // Loss reductions on the B x B score matrices (tiny next to the score kernel; one pass of row/column
 // statistics + one element-wise pass, no atomics, bitwise reproducible):
-//   hinge    VSE++ triplet loss, reference alad/loss.py:42-67
+//   hinge    VSE++ triplet loss, reference alad/loss.py:42-67 (a thread's statistics: HingeAcc, matrix_losses.hpp)
 //   listnet  score distillation, reference alad/loss.py:369-370,427-445
 //   sgemm    C = A * B with arbitrary strides on the exact-fp32 MFMA (dot_sim alad/loss.py:8-11 and
 //            its two backward products)
@@ -10,7 +10,8 @@
 #include "sgemm_tile.hpp"
 
 // ------------------------------------------------------------------------------------------------
-// hinge: the statistics of line b (HingeStats, matrix_losses.hpp), rows (b < B) then columns, as val[2B] | arg[2B]
+// hinge: the statistics of line b (HingeStats, matrix_losses.hpp), rows (b < B) then columns, as val[2B] | arg[2B].  One workgroup
+// per line, a HingeAcc per thread, met by block_argmax / block_sum (the strip walk of line_walk.hpp is xent.hip's and semantic.hip's)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void hinge_stats_kernel(const float* __restrict__ S, int64_t ld, int B, float margin,
                                                           int max_violation, float* __restrict__ val,
@@ -22,27 +23,18 @@ __global__ __launch_bounds__(256) void hinge_stats_kernel(const float* __restric
   const bool is_row = b < B;
   const int q = is_row ? b : b - B;
   const float diag = S[(int64_t)q * ld + q];
-  float best = 0.f, sum = 0.f;
-  int besti = 0x7fffffff, cnt = 0;
-  for (int t = threadIdx.x; t < B; t += blockDim.x) {
-    const float s = is_row ? S[(int64_t)q * ld + t] : S[(int64_t)t * ld + q];
-    const float x = hinge_x(margin, s, diag);
-    // a NaN cost rides the reductions that run anyway: as itself in the sum, as (+inf, index -1) in the arg-max, which beats a
-    // true +inf
-    const bool nan = hinge_cost_is_nan(x, t == q);
-    const float c = nan ? INFINITY : hinge_cost(x, t == q);
-    const int ti = nan ? -1 : t;
-    if (c > best || (c == best && ti < besti)) { best = c; besti = ti; }
-    sum += nan ? x : c;
-    cnt += (c > 0.f);
-  }
+  HingeAcc acc;
+  acc.clear();
+  for (int t = threadIdx.x; t < B; t += blockDim.x)
+    acc.add(margin, is_row ? S[(int64_t)q * ld + t] : S[(int64_t)t * ld + q], diag, t == q, t);
+  // only the mode's own reduction runs; a NaN cost rides it (HingeAcc)
   if (max_violation) {
-    block_argmax(best, besti, redv, redi);
-    if (threadIdx.x == 0) { val[b] = besti < 0 ? NAN : best; arg[b] = besti < 0 ? 0 : besti; }
+    block_argmax(acc.best, acc.besti, redv, redi);
+    if (threadIdx.x == 0) acc.store(1, val + b, arg + b);
   } else {
-    sum = block_sum(sum, redv);
-    const float fc = block_sum((float)cnt, redv);
-    if (threadIdx.x == 0) { val[b] = sum; arg[b] = (int)fc; }
+    acc.sum = block_sum(acc.sum, redv);
+    acc.cnt = (int)block_sum((float)acc.cnt, redv);
+    if (threadIdx.x == 0) acc.store(0, val + b, arg + b);
   }
 }
 
@@ -134,11 +126,8 @@ __global__ __launch_bounds__(256) void listnet_finish_kernel(const float* __rest
                                                              float* __restrict__ loss, float* __restrict__ dM) {
   __shared__ float red[4];
   if (blockIdx.x == 0) {
-    float rs = 0.f, cs = 0.f;
-    for (int t = threadIdx.x; t < B; t += blockDim.x) { rs += stats[(size_t)t * 6 + 5]; cs += stats[(size_t)(B + t) * 6 + 5]; }
-    rs = block_sum(rs, red);
-    cs = block_sum(cs, red);
-    if (threadIdx.x == 0) *loss = listnet_loss(rs, cs, B);
+    const float2 t = line_sums(B, red, [&](int v) { return stats[(size_t)v * 6 + 5]; });     // the lines' loss terms
+    if (threadIdx.x == 0) *loss = listnet_loss(t.x, t.y, B);
   }
   if (dM == nullptr) return;
   const int64_t n = (int64_t)B * B;

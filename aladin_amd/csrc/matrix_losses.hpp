@@ -2,9 +2,15 @@
 // distillation (alad/loss.py:369-370,427-445) and the weighted total (alad_model.py:450-453).  Two paths run them, chosen by
 // batch size: losses.hip (any B; a workgroup per line) and small_batch.hip (B <= 64; a wave per line, three launches for the
 // whole chain); the merged finish + pair-argmax kernel of align_bwd.hip runs either finish pass.  Each path keeps its own
-// reductions and its own way of dealing elements to threads; what an element IS lives here.
+// reductions and its own way of dealing elements to threads; what an element IS lives here, and so does what a thread keeps of
+// the elements it has seen.  Who runs what:
+//   hinge_x / hinge_cost / hinge_cost_is_nan   HingeAcc, hinge_vector_stats (small_batch.hip, a lane per element), sem_finish_kernel
+//   HingeAcc                                   hinge_stats_kernel (losses.hip, a workgroup per line), sem_stats_kernel (semantic.hip,
+//                                              line_walk against relevance-chosen anchors)
+//   everything else                            both paths' statistics and finish passes
 #pragma once
 #include "common.hpp"
+#include "line_walk.hpp"
 
 // ---- the small-batch statistics: SB_ST floats per line v in [0, 2B), rows then columns ---------------------------------------
 #define SB_MAX 64
@@ -42,6 +48,41 @@ __device__ __forceinline__ float hinge_x(float margin, float s, float diag) { re
 __device__ __forceinline__ float hinge_cost(float x, bool on_diag) { return on_diag ? 0.f : fmaxf(x, 0.f); }
 // fmaxf drops a NaN; the reference's clamp / max / sum keep it, so a NaN cost makes the line's statistic NaN
 __device__ __forceinline__ bool hinge_cost_is_nan(float x, bool on_diag) { return (x != x) && !on_diag; }
+
+// The running statistics of a line in a thread that sees many of its elements: the best cost with the lowest index on ties, the
+// sum, the number of positive costs.  A NaN cost goes as itself into the sum and as (+inf, index -1) into the arg-max, which
+// beats a true +inf.  As an accumulator of line_walk (line_walk.hpp) it brings its reductions along.
+struct HingeAcc {
+  float best, sum; int besti, cnt;
+  __device__ __forceinline__ void clear() { best = 0.f; sum = 0.f; besti = 0x7fffffff; cnt = 0; }
+  // element t of the line: score s against the line's anchor; `zero`: its cost is cleared (the diagonal, a masked positive)
+  __device__ __forceinline__ void add(float margin, float s, float anchor, bool zero, int t) {
+    const float x = hinge_x(margin, s, anchor);
+    const bool nan = hinge_cost_is_nan(x, zero);
+    const float c = nan ? INFINITY : hinge_cost(x, zero);
+    const int ti = nan ? -1 : t;
+    if (c > best || (c == best && ti < besti)) { best = c; besti = ti; }
+    sum += nan ? x : c;
+    cnt += (c > 0.f);
+  }
+  __device__ __forceinline__ void store(int max_violation, float* val, int* arg) const {       // reduced: the line's HingeStats
+    if (max_violation) { *val = besti < 0 ? NAN : best; *arg = besti < 0 ? 0 : besti; }
+    else { *val = sum; *arg = cnt; }
+  }
+  static constexpr int FIELDS = 4;
+  __device__ __forceinline__ void put(float* p) const { p[0] = best; p[64] = __int_as_float(besti); p[128] = sum; p[192] = __int_as_float(cnt); }
+  __device__ __forceinline__ void get(const float* p) { best = p[0]; besti = __float_as_int(p[64]); sum = p[128]; cnt = __float_as_int(p[192]); }
+  __device__ __forceinline__ void merge(const HingeAcc& o) {
+    float& v = best; int& idx = besti;
+    ALADIN_ARGMAX_STEP(o.best, o.besti);
+    sum += o.sum; cnt += o.cnt;
+  }
+  __device__ __forceinline__ void wave_reduce() {
+    wave_argmax(best, besti);
+    sum = wave_sum(sum);
+    cnt = (int)wave_sum((float)cnt);                       // exact: cnt < 2^24
+  }
+};
 
 // element (i, j) of dloss/dS
 __device__ __forceinline__ float hinge_grad_at(const HingeStats& st, const float* S, int64_t ld, int B, int i, int j, float margin,
@@ -114,11 +155,8 @@ __device__ __forceinline__ void hinge_finish_body(int vblock, int nblocks, const
                                                   int* __restrict__ pair_count, float* __restrict__ dST = nullptr) {
   __shared__ float red[4];
   if (vblock == 0) {
-    float rs = 0.f, cs = 0.f;                             // rows first, then columns, fixed order
-    for (int t = threadIdx.x; t < B; t += blockDim.x) { rs += st.value(t); cs += st.value(B + t); }
-    rs = block_sum(rs, red);
-    cs = block_sum(cs, red);
-    if (threadIdx.x == 0) *loss = rs + cs;
+    const float2 t = line_sums(B, red, [&](int v) { return st.value(v); });
+    if (threadIdx.x == 0) *loss = t.x + t.y;
   }
   if (dS == nullptr && pairs == nullptr) return;
   // rows are dealt to blocks, columns to threads: no integer division per element

@@ -144,10 +144,7 @@ __device__ __forceinline__ void rescore_map_epilogue(const f32x4 (&acc)[RESCORE_
           const bool in = w < cnt_y;
           ALADIN_ARGMAX_STEP(in ? acc[rt][ct][reg] : -INFINITY, in ? w : RESCORE_FILL);
         }
-        ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 8), __builtin_amdgcn_update_dpp(0, idx, 0x128, 0xF, 0xF, false));
-        ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 4), __builtin_amdgcn_update_dpp(0, idx, 0x124, 0xF, 0xF, false));
-        ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 2), __builtin_amdgcn_update_dpp(0, idx, 0x122, 0xF, 0xF, false));
-        ALADIN_ARGMAX_STEP(ALADIN_ROW_ROR(v, 1), __builtin_amdgcn_update_dpp(0, idx, 0x121, 0xF, 0xF, false));
+        row16_argmax(v, idx);
         if (col0 == reg) { bv = v; bi = idx; }                                 // every lane of the row holds the result: lane `reg` keeps it
       }
       const int r = rt * 16 + row0 + col0;                                     // lanes 0..3 of each row: 16 consecutive regions a tile

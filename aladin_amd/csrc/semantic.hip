@@ -19,9 +19,8 @@
 //                      for a row-major Rel and for a transposed view of one.  Writes pos, a1 and, in 'aligned' order, a2 / rank.
 //   sem_rank_kernel    ('reference' order) one wave per column j counts the chosen cells before (pos[B+j], j); rank[j] = k,
 //                      a2[k] = S[pos[B+j], j].
-//   sem_stats_kernel   HingeStats (matrix_losses.hpp) of every line.  Rows: one wave per row.  Columns: strips of 64 adjacent
-//                      columns, lanes across columns, 16 waves walking the rows (coalesced 256-byte reads), merged through LDS in
-//                      ascending wave order.
+//   sem_stats_kernel   HingeStats of every line: line_walk (line_walk.hpp) with HingeAcc (matrix_losses.hpp), the VSE++ hinge's own
+//                      running statistics, against the line's anchor; the masks are this file's.
 //   sem_finish_kernel  block (0, 0) sums the lines' values, rows then columns; every block writes dS for its 256 columns over the
 //                      rows dealt to it (owner-computes: a cell receives at most one row anchor and one column anchor).
 // Nothing is accumulated with atomics and every sum runs in a fixed order: the same input gives the same bits.  draws and the
@@ -156,83 +155,20 @@ __global__ __launch_bounds__(256) void sem_rank_kernel(const float* __restrict__
   if (lane == 0) { rank[j] = k; a2[k] = S[(int64_t)r * ld + j]; }
 }
 
-// the running statistics of a line: what hinge_stats_kernel (losses.hip) keeps per thread
-struct SemAcc {
-  float best, sum; int besti, cnt;
-  __device__ __forceinline__ void clear() { best = 0.f; sum = 0.f; besti = 0x7fffffff; cnt = 0; }
-  // element t of the line: score s against the line's anchor; `zero`: on the diagonal or a masked positive
-  __device__ __forceinline__ void add(float margin, float s, float anchor, bool zero, int t) {
-    const float x = hinge_x(margin, s, anchor);
-    // a NaN cost: as itself in the sum, as (+inf, index -1) in the arg-max, which beats a true +inf
-    const bool nan = hinge_cost_is_nan(x, zero);
-    const float c = nan ? INFINITY : hinge_cost(x, zero);
-    const int ti = nan ? -1 : t;
-    if (c > best || (c == best && ti < besti)) { best = c; besti = ti; }
-    sum += nan ? x : c;
-    cnt += (c > 0.f);
-  }
-};
-__device__ __forceinline__ void sem_line_store(int max_violation, float best, int besti, float sum, int cnt, float* val, int* arg) {
-  if (max_violation) { *val = besti < 0 ? NAN : best; *arg = besti < 0 ? 0 : besti; }
-  else { *val = sum; *arg = cnt; }
+// HingeStats of every line: line_walk with HingeAcc, each line against its own anchor
+__global__ __launch_bounds__(LINE_WALK_THREADS) void sem_stats_kernel(const float* __restrict__ S, int64_t ld, SemRel rel, int B,
+                                                                      float margin, int max_violation, int mask_positives, int row_blocks,
+                                                                      const float* __restrict__ a1, const float* __restrict__ a2,
+                                                                      float* __restrict__ val, int* __restrict__ arg) {
+  const int line = line_walk_line(B, row_blocks);
+  const float anchor = line < 0 ? 0.f : line < B ? a1[line] : a2[line - B];
+  line_walk<HingeAcc>(
+      S, ld, B, row_blocks,
+      [&](HingeAcc& acc, float s, int i, int j, int t) { acc.add(margin, s, anchor, i == j || (mask_positives && rel.above(i, j)), t); },
+      [&](const HingeAcc& acc, int v) { acc.store(max_violation, val + v, arg + v); });
 }
 
-// blocks [0, row_blocks): rows, one wave each;  blocks [row_blocks, row_blocks + cdiv(B, 64)): column strips
-__global__ __launch_bounds__(SEM_THREADS) void sem_stats_kernel(const float* __restrict__ S, int64_t ld, SemRel rel, int B, float margin,
-                                                                int max_violation, int mask_positives, int row_blocks,
-                                                                const float* __restrict__ a1, const float* __restrict__ a2,
-                                                                float* __restrict__ val, int* __restrict__ arg) {
-  __shared__ float pbest[SEM_WAVES][64], psum[SEM_WAVES][64];
-  __shared__ int pidx[SEM_WAVES][64], pcnt[SEM_WAVES][64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  SemAcc acc;
-  acc.clear();
-  if ((int)blockIdx.x < row_blocks) {
-    const int i = blockIdx.x * SEM_WAVES + wave;
-    if (i >= B) return;                                      // wave-uniform; no barrier on this side
-    const float* __restrict__ row = S + (int64_t)i * ld;
-    const float anchor = a1[i];
-    for (int j = lane; j < B; j += 64) acc.add(margin, row[j], anchor, j == i || (mask_positives && rel.above(i, j)), j);
-    float v = acc.best;
-    int idx = acc.besti;
-    wave_argmax(v, idx);
-    const float sum = wave_sum(acc.sum);
-    const int cnt = (int)wave_sum((float)acc.cnt);
-    if (lane == 0) sem_line_store(max_violation, v, idx, sum, cnt, val + i, arg + i);
-    return;
-  }
-  const int j = ((int)blockIdx.x - row_blocks) * 64 + lane;
-  const bool live = j < B;
-  const float* __restrict__ col = S + (live ? j : 0);
-  const float anchor = live ? a2[j] : 0.f;
-  // four rows in flight per wave: the loads do not depend on the running state
-  int i = wave;
-  for (; i + 3 * SEM_WAVES < B; i += 4 * SEM_WAVES) {
-    float x[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) x[q] = live ? col[(int64_t)(i + q * SEM_WAVES) * ld] : 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int iq = i + q * SEM_WAVES;
-      if (live) acc.add(margin, x[q], anchor, iq == j || (mask_positives && rel.above(iq, j)), iq);
-    }
-  }
-  for (; i < B; i += SEM_WAVES)
-    if (live) acc.add(margin, col[(int64_t)i * ld], anchor, i == j || (mask_positives && rel.above(i, j)), i);
-  pbest[wave][lane] = acc.best; pidx[wave][lane] = acc.besti; psum[wave][lane] = acc.sum; pcnt[wave][lane] = acc.cnt;
-  __syncthreads();
-  if (wave != 0 || !live) return;
-  float v = acc.best, sum = acc.sum;
-  int idx = acc.besti, cnt = acc.cnt;
-  for (int w = 1; w < SEM_WAVES; ++w) {                      // ascending waves: a fixed order
-    ALADIN_ARGMAX_STEP(pbest[w][lane], pidx[w][lane]);
-    sum += psum[w][lane];
-    cnt += pcnt[w][lane];
-  }
-  sem_line_store(max_violation, v, idx, sum, cnt, val + B + j, arg + B + j);
-}
-
-// grid (cdiv(B, 256) column chunks, row groups); dS == NULL: one block, the sum only
+// grid line_finish_grid; dS == NULL: one block, the sum only
 __global__ __launch_bounds__(256) void sem_finish_kernel(const float* __restrict__ S, int64_t ld, SemRel rel, int B, float margin,
                                                          int max_violation, int mask_positives, const float* __restrict__ val,
                                                          const int* __restrict__ arg, const int* __restrict__ pos,
@@ -241,11 +177,8 @@ __global__ __launch_bounds__(256) void sem_finish_kernel(const float* __restrict
                                                          float* __restrict__ dS) {
   __shared__ float red[4];
   if (blockIdx.x == 0 && blockIdx.y == 0) {
-    float rs = 0.f, cs = 0.f;                                // rows first, then columns, fixed order
-    for (int t = threadIdx.x; t < B; t += blockDim.x) { rs += val[t]; cs += val[B + t]; }
-    rs = block_sum(rs, red);
-    cs = block_sum(cs, red);
-    if (threadIdx.x == 0) *loss = rs + cs;
+    const float2 t = line_sums(B, red, [&](int v) { return val[v]; });
+    if (threadIdx.x == 0) *loss = t.x + t.y;
   }
   if (dS == nullptr) return;
   const int j = blockIdx.x * 256 + threadIdx.x;
@@ -313,16 +246,11 @@ extern "C" int aladin_semantic_hinge_fwd_bwd(const float* S, int64_t ldS, const 
     hipLaunchKernelGGL(sem_rank_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, S, ldS, B, (const int*)w.pos, w.a2, w.rank);
     if (int rc = aladin_check_launch("sem_rank_kernel")) return rc;
   }
-  const int row_blocks = cdiv(B, SEM_WAVES);
-  hipLaunchKernelGGL(sem_stats_kernel, dim3(row_blocks + cdiv(B, 64)), dim3(SEM_THREADS), 0, st, S, ldS, r, B, margin, max_violation,
-                     mask_positives, row_blocks, (const float*)w.a1, (const float*)w.a2, w.val, w.arg);
+  hipLaunchKernelGGL(sem_stats_kernel, dim3(line_walk_blocks(B)), dim3(LINE_WALK_THREADS), 0, st, S, ldS, r, B, margin, max_violation,
+                     mask_positives, line_row_blocks(B), (const float*)w.a1, (const float*)w.a2, w.val, w.arg);
   if (int rc = aladin_check_launch("sem_stats_kernel")) return rc;
-  const int gx = dS ? cdiv(B, 256) : 1;
-  int gy = dS ? 2048 / gx : 1;                               // about 2048 workgroups at the most; the rows are dealt to them
-  if (gy > B) gy = B;
-  if (gy < 1) gy = 1;
-  hipLaunchKernelGGL(sem_finish_kernel, dim3(gx, gy), dim3(256), 0, st, S, ldS, r, B, margin, max_violation, mask_positives,
-                     (const float*)w.val, (const int*)w.arg, (const int*)w.pos, (const float*)w.a1, (const float*)w.a2,
+  hipLaunchKernelGGL(sem_finish_kernel, line_finish_grid(B, dS != nullptr), dim3(256), 0, st, S, ldS, r, B, margin, max_violation,
+                     mask_positives, (const float*)w.val, (const int*)w.arg, (const int*)w.pos, (const float*)w.a1, (const float*)w.a2,
                      (const int*)w.rank, loss, dS);
   return aladin_check_launch("sem_finish_kernel");
 }

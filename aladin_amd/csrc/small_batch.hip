@@ -21,7 +21,8 @@
 
 namespace {
 
-// VSE++ hinge statistics of one row / column vector held a lane per element (alad/loss.py:49-67): out[0] = value, out[1] = arg
+// VSE++ hinge statistics of one row / column vector held a lane per element (alad/loss.py:49-67): out[0] = value, out[1] = arg.
+// HingeAcc (matrix_losses.hpp) states the same rule for a thread that sees many elements; with one per lane a ballot finds the NaN.
 __device__ __forceinline__ void hinge_vector_stats(float m, float diag, int q, int B, float margin, int max_violation, int lane,
                                                    float* out) {
   const bool live = lane < B;

@@ -12,8 +12,8 @@
 //                       that the line's diagonal part of the gradient, P_dd - 1, is known as -(off-diagonal mass) / s: formed as
 //                       e^(x - m) / s - 1 it is 0 as soon as the mass is below 2^-25, while the off-diagonal entries it balances
 //                       are still exact -- the whole gradient of a well-trained batch.
-//                       Rows: one wave per row, lanes across columns.  Columns: a workgroup takes a strip of 64 adjacent columns,
-//                       lanes across columns, its 16 waves walk the rows (coalesced 256-byte reads) and merge through LDS.
+//                       The lines are walked by line_walk (line_walk.hpp) with Lse as its accumulator: a wave per row, strips of
+//                       64 columns under 16 waves; this file supplies the element (the logit, off the diagonal) and the store.
 //                       line[b] = {m, s, P_dd - 1, 0} and piece[b] = {LSE - L_dd, the line's share of dt}, rows then columns.
 //   xent_finish_kernel  block (0, 0) sums the lines' shares of loss and dt in a fixed order; every block writes dS for its
 //                       256 columns (column statistics in registers) over the rows dealt to it.
@@ -22,13 +22,12 @@
 #include <float.h>
 #include "../../include/aladin_hip.h"
 #include "common.hpp"
+#include "line_walk.hpp"
 
 // No contraction: lse_merge must give both partners of a butterfly step the same bits (a * b + c * d contracted is not symmetric).
 #pragma clang fp contract(off)
 
 #define XENT_MAX_B ALADIN_XENT_MAX_B
-#define XENT_STATS_THREADS 1024          // 16 waves: 16 rows of the row part, or one 64-column strip walked by 16 waves
-#define XENT_STATS_WAVES (XENT_STATS_THREADS / 64)
 
 // (m, s, u) of an empty set: m is the most negative FINITE float, so that m - M, 0 * (m - M) and e^(m - M) stay finite / zero
 // without a guard (an infinite m would give inf - inf and 0 * inf)
@@ -42,6 +41,11 @@ struct Lse {
     if (x > m) { u = t * (u - s * dx); s = s * t + 1.f; m = x; }      // a new maximum: the old terms shift by m - x = -dx
     else { u = u + t * dx; s = s + t; }
   }
+  static constexpr int FIELDS = 3;                           // from here: what line_walk asks of an accumulator
+  __device__ __forceinline__ void put(float* p) const { p[0] = m; p[64] = s; p[128] = u; }
+  __device__ __forceinline__ void get(const float* p) { m = p[0]; s = p[64]; u = p[128]; }
+  __device__ __forceinline__ void merge(const Lse& o);       // lse_merge
+  __device__ __forceinline__ void wave_reduce();             // wave_lse
 };
 
 // the union of two sets; symmetric in its arguments bit for bit
@@ -68,6 +72,8 @@ __device__ __forceinline__ Lse wave_lse(Lse v) {
   XENT_LANE_STEP(ALADIN_ROW_ROR(v.m, 1), ALADIN_ROW_ROR(v.s, 1), ALADIN_ROW_ROR(v.u, 1));
   return v;
 }
+__device__ __forceinline__ void Lse::merge(const Lse& o) { *this = lse_merge(*this, o); }
+__device__ __forceinline__ void Lse::wave_reduce() { *this = wave_lse(*this); }
 
 // v: the line's off-diagonal elements; xd: its diagonal logit.  -> line = {m, s, P_dd - 1, 0}, piece = {LSE - L_dd, sum P (L - L_dd)}
 __device__ __forceinline__ void xent_line_store(Lse v, float xd, float4* __restrict__ line, float2* __restrict__ piece) {
@@ -79,56 +85,19 @@ __device__ __forceinline__ void xent_line_store(Lse v, float xd, float4* __restr
   *piece = make_float2(off + logf(v.s), v.u / v.s + off);
 }
 
-static inline int xent_row_blocks(int B) { return cdiv(B, XENT_STATS_WAVES); }
 // workspace: line[2B] (float4) | piece[2B] (float2)
 static inline size_t xent_line_bytes(int B) { return (size_t)B * 2 * sizeof(float4); }
 
-// blocks [0, row_blocks): rows, one wave each;  blocks [row_blocks, row_blocks + cdiv(B, 64)): column strips
-__global__ __launch_bounds__(XENT_STATS_THREADS) void xent_stats_kernel(const float* __restrict__ S, int64_t ld, int B,
-                                                                        const float* __restrict__ log_t, int row_blocks,
-                                                                        float4* __restrict__ line, float2* __restrict__ piece) {
-  __shared__ float part[XENT_STATS_WAVES][3][64];
+__global__ __launch_bounds__(LINE_WALK_THREADS) void xent_stats_kernel(const float* __restrict__ S, int64_t ld, int B,
+                                                                       const float* __restrict__ log_t, int row_blocks,
+                                                                       float4* __restrict__ line, float2* __restrict__ piece) {
   const float et = expf(*log_t);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  Lse v;
-  v.clear();
-  if ((int)blockIdx.x < row_blocks) {
-    const int i = blockIdx.x * XENT_STATS_WAVES + wave;
-    if (i >= B) return;                                      // wave-uniform; no barrier on this side
-    const float* row = S + (int64_t)i * ld;
-    for (int j = lane; j < B; j += 64)
-      if (j != i) v.add(row[j] * et);
-    v = wave_lse(v);
-    if (lane == 0) xent_line_store(v, row[i] * et, line + i, piece + i);
-    return;
-  }
-  const int j = ((int)blockIdx.x - row_blocks) * 64 + lane;
-  const bool live = j < B;
-  const float* col = S + (live ? j : 0);
-  // four rows in flight per wave: the loads do not depend on the running state
-  int i = wave;
-  for (; i + 3 * XENT_STATS_WAVES < B; i += 4 * XENT_STATS_WAVES) {
-    float x[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) x[q] = live ? col[(int64_t)(i + q * XENT_STATS_WAVES) * ld] : 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (live && i + q * XENT_STATS_WAVES != j) v.add(x[q] * et);
-  }
-  for (; i < B; i += XENT_STATS_WAVES)
-    if (live && i != j) v.add(col[(int64_t)i * ld] * et);
-  part[wave][0][lane] = v.m; part[wave][1][lane] = v.s; part[wave][2][lane] = v.u;
-  __syncthreads();
-  if (wave != 0 || !live) return;
-  for (int w = 1; w < XENT_STATS_WAVES; ++w) {               // ascending waves: a fixed order
-    Lse o;
-    o.m = part[w][0][lane]; o.s = part[w][1][lane]; o.u = part[w][2][lane];
-    v = lse_merge(v, o);
-  }
-  xent_line_store(v, S[(int64_t)j * ld + j] * et, line + B + j, piece + B + j);
+  line_walk<Lse>(
+      S, ld, B, row_blocks, [&](Lse& v, float s, int i, int j, int) { if (j != i) v.add(s * et); },
+      [&](const Lse& v, int b) { const int d = b < B ? b : b - B; xent_line_store(v, S[(int64_t)d * ld + d] * et, line + b, piece + b); });
 }
 
-// grid (cdiv(B, 256) column chunks, row groups); dS == NULL: one block, the sums only
+// grid line_finish_grid; dS == NULL: one block, the sums only
 __global__ __launch_bounds__(256) void xent_finish_kernel(const float* __restrict__ S, int64_t ld, int B, const float* __restrict__ log_t,
                                                           const float4* __restrict__ line, const float2* __restrict__ piece,
                                                           float* __restrict__ loss, float* __restrict__ dS, float* __restrict__ d_log_t) {
@@ -136,15 +105,12 @@ __global__ __launch_bounds__(256) void xent_finish_kernel(const float* __restric
   const float et = expf(*log_t);
   const float inv = 1.f / (2.f * (float)B);
   if (blockIdx.x == 0 && blockIdx.y == 0) {
-    float rl = 0.f, cl = 0.f, rt = 0.f, ct = 0.f;            // rows, then columns
+    float rl = 0.f, cl = 0.f, rt = 0.f, ct = 0.f;            // line_sums of both shares in one pass over piece: rows, then columns
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
       const float2 r = piece[b], c = piece[B + b];
       rl += r.x; cl += c.x; rt += r.y; ct += c.y;
     }
-    rl = block_sum(rl, red);
-    cl = block_sum(cl, red);
-    rt = block_sum(rt, red);
-    ct = block_sum(ct, red);
+    rl = block_sum(rl, red); cl = block_sum(cl, red); rt = block_sum(rt, red); ct = block_sum(ct, red);
     if (threadIdx.x == 0) {
       *loss = (rl + cl) * inv;
       if (d_log_t) *d_log_t = (rt + ct) * inv;
@@ -185,16 +151,11 @@ extern "C" int aladin_xent_fwd_bwd(const float* S, int64_t ldS, int B, const flo
   float4* line = (float4*)workspace;
   float2* piece = (float2*)((char*)workspace + xent_line_bytes(B));
   hipStream_t st = (hipStream_t)stream;
-  const int row_blocks = xent_row_blocks(B);
-  hipLaunchKernelGGL(xent_stats_kernel, dim3(row_blocks + cdiv(B, 64)), dim3(XENT_STATS_THREADS), 0, st, S, ldS, B, log_temperature,
-                     row_blocks, line, piece);
+  hipLaunchKernelGGL(xent_stats_kernel, dim3(line_walk_blocks(B)), dim3(LINE_WALK_THREADS), 0, st, S, ldS, B, log_temperature,
+                     line_row_blocks(B), line, piece);
   if (int rc = aladin_check_launch("xent_stats_kernel")) return rc;
-  const int gx = dS ? cdiv(B, 256) : 1;
-  int gy = dS ? 2048 / gx : 1;                               // about 2048 workgroups at the most; the rows are dealt to them
-  if (gy > B) gy = B;
-  if (gy < 1) gy = 1;
-  hipLaunchKernelGGL(xent_finish_kernel, dim3(gx, gy), dim3(256), 0, st, S, ldS, B, log_temperature, line, piece, loss, dS,
-                     d_log_temperature);
+  hipLaunchKernelGGL(xent_finish_kernel, line_finish_grid(B, dS != nullptr), dim3(256), 0, st, S, ldS, B, log_temperature, line, piece,
+                     loss, dS, d_log_temperature);
   return aladin_check_launch("xent_finish_kernel");
 }
 

@@ -6,7 +6,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._ops_common import _RAW_STREAM, _stream, _ptr, _require_gpu, _rows_inner_contig, _LEN_CACHE, lengths_tensor, _ld, _workspace
+from ._ops_common import (_RAW_STREAM, _stream, _ptr, _require_gpu, _rows_inner_contig, _LEN_CACHE, lengths_tensor, _ld, _workspace,
+                          _unit_cols, _require_square)
 
 
 def _hinge_raw(scores, margin, max_violation, want_grad, want_pairs=False, loss_out=None):
@@ -14,7 +15,7 @@ def _hinge_raw(scores, margin, max_violation, want_grad, want_pairs=False, loss_
     loss_out: a one-element float32 view the kernel writes the loss into (instead of a fresh scalar)."""
     lib = _lib.load()
     B = scores.shape[0]
-    sc = scores if scores.stride(1) == 1 else scores.contiguous()
+    sc = _unit_cols(scores)
     dev = scores.device
     loss = loss_out if loss_out is not None else torch.empty((), dtype=torch.float32, device=dev)
     dS = torch.empty((B, B), dtype=torch.float32, device=dev) if want_grad else None
@@ -45,9 +46,7 @@ class _Hinge(torch.autograd.Function):
 def hinge_loss(scores, margin, max_violation):
     """VSE++ hinge on a square score matrix; replaces reference alad/loss.py:42-67."""
     _require_gpu(scores)
-    if scores.dim() != 2 or scores.shape[0] != scores.shape[1]:
-        raise ValueError('aladin_amd: the contrastive loss needs a square score matrix, got %s '
-                         '(the reference fails in diag/expand_as, alad/loss.py:43-45)' % (tuple(scores.shape),))
+    _require_square(scores, 'the contrastive loss', ' (the reference fails in diag/expand_as, alad/loss.py:43-45)')
     return _Hinge.apply(scores, margin, max_violation)
 
 
@@ -56,8 +55,7 @@ class _ListNet(torch.autograd.Function):
     def forward(ctx, teacher, student, temperature, eps):
         lib = _lib.load()
         B = student.shape[0]
-        t = teacher if teacher.stride(1) == 1 else teacher.contiguous()
-        m = student if student.stride(1) == 1 else student.contiguous()
+        t, m = _unit_cols(teacher), _unit_cols(student)
         loss = torch.empty((), dtype=torch.float32, device=student.device)
         dM = torch.empty((B, B), dtype=torch.float32, device=student.device) if ctx.needs_input_grad[1] else None
         ws = _workspace(lib.aladin_listnet_workspace_bytes(B), student.device)
@@ -74,9 +72,9 @@ class _ListNet(torch.autograd.Function):
 def listnet_loss(teacher_scores, student_scores, temperature=6.0, eps=1e-10):
     """ListNet distillation; replaces reference alad/loss.py:427-445 (teacher detached, :370)."""
     _require_gpu(teacher_scores, student_scores)
-    if teacher_scores.shape != student_scores.shape or student_scores.dim() != 2 \
-            or student_scores.shape[0] != student_scores.shape[1]:
+    if teacher_scores.shape != student_scores.shape:
         raise ValueError('aladin_amd: listnet needs two square score matrices of equal shape')
+    _require_square(student_scores, 'listnet')
     return _ListNet.apply(teacher_scores.detach(), student_scores, temperature, eps)
 
 
@@ -87,8 +85,7 @@ class _DistillMode(torch.autograd.Function):
     def forward(ctx, teacher, student, wb, mode, margin, threshold, stride):
         lib = _lib.load()
         B = student.shape[0]
-        t = teacher if teacher.stride(1) == 1 else teacher.contiguous()
-        m = student if student.stride(1) == 1 else student.contiguous()
+        t, m = _unit_cols(teacher), _unit_cols(student)
         dev = student.device
         loss = torch.empty((), dtype=torch.float32, device=dev)
         dM = torch.empty((B, B), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
@@ -121,9 +118,9 @@ def distillation_loss(teacher_scores, student_scores, mode, margin=0.2, threshol
     _require_gpu(teacher_scores, student_scores)
     if mode not in ('mse', 'contrastive', 'ordinal'):
         raise ValueError('aladin_amd: unknown distillation mode %r' % (mode,))
-    if teacher_scores.shape != student_scores.shape or student_scores.dim() != 2 \
-            or student_scores.shape[0] != student_scores.shape[1]:
+    if teacher_scores.shape != student_scores.shape:
         raise ValueError('aladin_amd: distillation needs two square score matrices of equal shape')
+    _require_square(student_scores, 'distillation')
     if mode == 'mse':
         if wb is None or wb.numel() != 2:
             raise ValueError("aladin_amd: mode 'mse' needs the (2,) parameter wb")
@@ -140,8 +137,7 @@ class _OrderScores(torch.autograd.Function):
     @staticmethod
     def forward(ctx, im, s):
         lib = _lib.load()
-        a = im if im.stride(1) == 1 else im.contiguous()
-        b = s if s.stride(1) == 1 else s.contiguous()
+        a, b = _unit_cols(im), _unit_cols(s)
         out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
         _lib.check(lib.aladin_order_sim_fwd(_ptr(a), _ld(a), _ptr(b), _ld(b), a.shape[0], b.shape[0], a.shape[1],
                                             _ptr(out), out.stride(0), _stream()), 'order_sim_fwd')
@@ -238,8 +234,7 @@ def _nn_entropy_limit(N):
 class _NNEntropy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, cap):
-        a = img if img.stride(1) == 1 else img.contiguous()
-        b = cap if cap.stride(1) == 1 else cap.contiguous()
+        a, b = _unit_cols(img), _unit_cols(cap)
         loss, nn, dist = _nn_entropy_raw(a, b, True)
         ctx.save_for_backward(a, b, nn, dist)
         ctx.mark_non_differentiable(nn, dist)
@@ -275,7 +270,7 @@ def pairwise_nns_inner(x):
         raise ValueError('aladin_amd: a non-empty (N, D) matrix expected')
     _nn_entropy_limit(x.shape[0])
     x = x.detach()
-    return _nn_entropy_raw(x if x.stride(1) == 1 else x.contiguous(), None, False)[1].to(torch.int64)
+    return _nn_entropy_raw(_unit_cols(x), None, False)[1].to(torch.int64)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -323,7 +318,7 @@ class _CrossEntropy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scores, log_t):
         B = scores.shape[0]
-        sc = scores if (scores.stride(1) == 1 and (B == 1 or scores.stride(0) >= B)) else scores.contiguous()
+        sc = _unit_cols(scores)
         ctx.want_dt = ctx.needs_input_grad[1]
         loss, grads = _xent_raw(sc, log_t, ctx.needs_input_grad[0] or ctx.want_dt, ctx.want_dt)
         ctx.save_for_backward(grads)
@@ -340,20 +335,14 @@ class _CrossEntropy(torch.autograd.Function):
         return (out[:n].view(ctx.B, ctx.B) if ctx.needs_input_grad[0] else None), (out[n:].view(ctx.t_shape) if ctx.want_dt else None)
 
 
-def _check_square(scores):
-    if not isinstance(scores, torch.Tensor):
-        raise TypeError('aladin_amd: expected a torch.Tensor, got %r' % type(scores))
-    if scores.dim() != 2 or scores.shape[0] != scores.shape[1] or scores.shape[0] < 1:
-        raise ValueError('aladin_amd: the cross-entropy criterion needs a square score matrix, got %s '
-                         '(the reference fails in F.cross_entropy, alad/loss.py:198-199)' % (tuple(scores.shape),))
-
-
 def cross_entropy_scores(scores, log_temperature):
     """Symmetric cross-entropy (InfoNCE) of a square score matrix: with L = scores * exp(log_temperature), the mean of
     cross_entropy(L, arange) and cross_entropy(L.T, arange) -- what CrossEntropyCriterion (reference alad/loss.py:190-201) computes
     from its logits.  log_temperature: a one-element float32 GPU tensor (it gets a gradient) or a Python float (a constant).
     One autograd node, two launches forward; the backward scales the saved gradients by the upstream one in one launch."""
-    _check_square(scores)
+    if not isinstance(scores, torch.Tensor):
+        raise TypeError('aladin_amd: expected a torch.Tensor, got %r' % type(scores))
+    _require_square(scores, 'the cross-entropy criterion', ' (the reference fails in F.cross_entropy, alad/loss.py:198-199)')
     _require_gpu(scores)
     _xent_limit(scores.shape[0])
     return _CrossEntropy.apply(scores, _xent_temperature(log_temperature, scores.device))
@@ -371,7 +360,7 @@ class _SemanticHinge(torch.autograd.Function):
         lib = _lib.load()
         B = scores.shape[0]
         dev = scores.device
-        sc = scores if (scores.stride(1) == 1 and (B == 1 or scores.stride(0) >= B)) else scores.contiguous()
+        sc = _unit_cols(scores)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         dS = torch.empty((B, B), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         pos = torch.empty(2 * B, dtype=torch.int32, device=dev) if want_positives else None
@@ -406,8 +395,7 @@ def semantic_hinge_loss(scores, relevances, margin, threshold=0.4, max_violation
     for t in (scores, relevances):
         if not isinstance(t, torch.Tensor):
             raise TypeError('aladin_amd: expected a torch.Tensor, got %r' % type(t))
-    if scores.dim() != 2 or scores.shape[0] != scores.shape[1] or scores.shape[0] < 1:
-        raise ValueError('aladin_amd: the semantic contrastive loss needs a square score matrix, got %s' % (tuple(scores.shape),))
+    _require_square(scores, 'the semantic contrastive loss')
     if tuple(relevances.shape) != tuple(scores.shape):
         raise ValueError('aladin_amd: relevances of shape %s expected (aligned with the scores), got %s'
                          % (tuple(scores.shape), tuple(relevances.shape)))
@@ -518,7 +506,7 @@ def attention_distillation_loss(im_set, s_seq, im_len, s_len, teacher):
 class _L2Norm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        x = x if x.stride(1) == 1 else x.contiguous()
+        x = _unit_cols(x)
         out = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
         _lib.check(_lib.load().aladin_l2norm_fwd(_ptr(x), _ld(x), x.shape[0], x.shape[1], _ptr(out), _stream()), 'l2norm_fwd')
         ctx.save_for_backward(x)
@@ -527,7 +515,7 @@ class _L2Norm(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (x,) = ctx.saved_tensors
-        g = g if g.stride(1) == 1 else g.contiguous()
+        g = _unit_cols(g)
         dx = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
         _lib.check(_lib.load().aladin_l2norm_bwd(_ptr(x), _ld(x), _ptr(g), _ld(g), x.shape[0], x.shape[1], _ptr(dx), _stream()),
                    'l2norm_bwd')

@@ -261,6 +261,28 @@ def test_listnet_propagates_nan():
     assert np.isnan(float(ops.listnet_loss(T(teacher), T(student))))
 
 
+@pytest.mark.parametrize('op', ['hinge', 'listnet', 'distill_contrastive'])
+def test_an_expanded_row_is_copied_not_refused(op):
+    """A (B, B) expand of one row has unit column stride and row stride 0: the matrix ops copy it (the C ABI refuses ld < B) and give
+    the bits of the .contiguous() input, loss and gradient."""
+    from aladin_amd import ops
+    B = 5
+    rng = np.random.default_rng(7)
+    row, trow = T(rng.standard_normal(B).astype(np.float32)), T(rng.standard_normal(B).astype(np.float32))
+    run = {'hinge': lambda t, s: ops.hinge_loss(s, 0.2, False),
+           'listnet': lambda t, s: ops.listnet_loss(t, s),
+           'distill_contrastive': lambda t, s: ops.distillation_loss(t, s, 'contrastive')}[op]
+    teacher = trow.expand(B, B)
+    view = row.expand(B, B).detach().requires_grad_(True)
+    contig = row.expand(B, B).contiguous().requires_grad_(True)
+    assert view.stride() == (0, 1) and teacher.stride() == (0, 1)
+    loss_v, loss_c = run(teacher, view), run(teacher.contiguous(), contig)
+    (loss_v * 1.5).backward()
+    (loss_c * 1.5).backward()
+    assert torch.equal(loss_v.detach(), loss_c.detach()) and torch.isfinite(loss_c)
+    assert tuple(view.grad.shape) == (B, B) and torch.equal(view.grad, contig.grad) and contig.grad.any()
+
+
 # ------------------------------------------------------------------------------------------------
 # dot_scores / sgemm
 # ------------------------------------------------------------------------------------------------

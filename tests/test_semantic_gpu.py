@@ -158,6 +158,16 @@ def test_matrix_op_matches_the_restatement_past_one_strip_and_one_chunk(family, 
     assert_matches(run_op(T(S), T(rel), D32(draws), max_violation=mv), ref, 'B 1025 %s %s' % (family, 'max' if mv else 'sum'))
 
 
+@pytest.mark.parametrize('B', [16, 17, 48, 49, 113])
+def test_matrix_op_matches_the_restatement_at_the_line_walk_edges(B):
+    """The edges of the walk sem_stats_kernel shares (line_walk.hpp) that the sizes above miss: 16 / 17, the last block of 16 wave-rows
+    full and one over; 48 / 49, the last size at which a strip's waves run the tail loop only and the first at which wave 0 has four
+    rows in flight; 113, both loops in waves 1 to 15."""
+    for mv in X.MODES:
+        S, rel, draws, margin, ref = restated(B, 'dense', 0, mv)
+        assert_matches(run_op(T(S), T(rel), D32(draws), max_violation=mv), ref, 'B %d dense %s' % (B, 'max' if mv else 'sum'))
+
+
 @pytest.mark.parametrize('B', [5, 65, 257])
 def test_quantised_family_equals_the_restatement_ties_included(B):
     for mv in X.MODES:

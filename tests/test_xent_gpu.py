@@ -130,6 +130,14 @@ def test_matrix_op_matches_float64(B, family):
         assert np.abs(dS.sum()) <= 1e-4 * np.abs(dS).sum()                           # sum_ij dL_ij = 0: the diagonal balances its lines
 
 
+@pytest.mark.parametrize('B', [16, 17, 48, 49, 113])
+def test_matrix_op_matches_float64_at_the_line_walk_edges(B):
+    """The edges of the walk xent_stats_kernel shares (line_walk.hpp) that X.SIZES misses: 16 / 17, the last block of 16 wave-rows full
+    and one over; 48 / 49, the last size at which a strip's waves run the tail loop only and the first at which wave 0 has four rows
+    in flight; 113, both loops in waves 1 to 15.  The same gates, on the family with the cancellation trap."""
+    test_matrix_op_matches_float64(B, 'sharp')
+
+
 def test_upstream_gradient_loss_only_and_constant_temperature():
     from aladin_amd import ops
     B = 257
