@@ -583,6 +583,10 @@ def alignment_triplet_loss(im_set, s_seq, im_len, s_len, margin, max_violation):
                          '(the reference fails in diag/expand_as, alad/loss.py:43-45)' % (im_set.shape[0], s_seq.shape[0]))
     if torch.is_grad_enabled() and (im_set.requires_grad or s_seq.requires_grad):
         im_set, s_seq = _pad_features(im_set, s_seq)
+    elif not torch.is_grad_enabled():
+        # a Function's ctx.needs_input_grad follows requires_grad even under torch.no_grad(): without this the node would prepare
+        # (and, for a feature size that is no multiple of 4, refuse) a backward nobody can ask for
+        im_set, s_seq = im_set.detach(), s_seq.detach()
     fill = None if max_violation else _caption_fill(s_len, s_seq.shape[1])
     return _AlignTriplet.apply(im_set, s_seq, im_len_t, s_len_t, margin, max_violation, fill)
 

@@ -6,7 +6,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._ops_common import _stream, _ptr, _require_gpu, _rows_inner_contig, _ld, _workspace
+from ._ops_common import _stream, _ptr, _require_gpu, _rows_inner_contig, _ld, _workspace, _unit_cols
 from .ops import (AlignSaved, _align_forward, _align_head_forward, _caption_fill, _check_backward_supported, _check_sets,
                   _pad_features, _pair_kernel_covers, _set_view, is_long)
 from .ops_losses import _hinge_raw, _sgemm, _xent_limit, _xent_raw, _xent_scale, _xent_temperature, dot_scores
@@ -17,6 +17,16 @@ from .ops_losses import _hinge_raw, _sgemm, _xent_limit, _xent_raw, _xent_scale,
 # ------------------------------------------------------------------------------------------------
 SMALL_BATCH_MAX = 64
 HEAD_MATCH_HINGE, HEAD_ALIGN_HINGE, HEAD_LISTNET = 1, 2, 4      # ALADIN_HEAD_* of include/aladin_hip.h
+
+
+def _small_rows(x):
+    """Embedding rows as the small-batch kernels read them through _ld: _unit_cols, and -- where D is a multiple of 4 -- rows on
+    16-byte boundaries: heads_small_stats_kernel sums a misaligned row lane by lane and an aligned one four features per lane, in
+    another order, and the result must not depend on the memory layout."""
+    x = _unit_cols(x)
+    if x.shape[1] % 4 == 0 and (x.data_ptr() % 16 or (x.shape[0] > 1 and x.stride(0) % 4)):
+        return x.contiguous()
+    return x
 
 
 def _heads_small_fwd(im, s, S, margin, max_violation, flags, temperature, eps, weights, want_grads, want_pairs, align=None):
@@ -74,11 +84,8 @@ class _SmallMatchDistill(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, im, s, teacher, margin, max_violation, want_hinge, temperature, eps):
-        im = im if im.stride(1) == 1 else im.contiguous()
-        s = s if s.stride(1) == 1 else s.contiguous()
-        t = None
-        if teacher is not None:
-            t = teacher if teacher.stride(1) == 1 else teacher.contiguous()
+        im, s = _small_rows(im), _small_rows(s)
+        t = _unit_cols(teacher) if teacher is not None else None
         flags = (HEAD_MATCH_HINGE if want_hinge else 0) | (HEAD_LISTNET if t is not None else 0)
         need = any(ctx.needs_input_grad[:2])
         o = _heads_small_fwd(im, s, t, margin, max_violation, flags, temperature, eps, (1.0, 1.0, 1.0), need, False)
@@ -96,7 +103,7 @@ class _SmallMatchDistill(torch.autograd.Function):
         d_s = torch.empty((B, D), dtype=torch.float32, device=im.device) if ctx.needs_input_grad[1] else None
         gh = g_h.to(torch.float32).contiguous() if (g_h is not None and dMh is not None) else None
         gl = g_l.to(torch.float32).contiguous() if (g_l is not None and dMl is not None) else None
-        gM = (g_M if g_M.stride(1) == 1 else g_M.contiguous()) if g_M is not None else None
+        gM = _unit_cols(g_M) if g_M is not None else None          # autograd hands over (0, 1)- and (0, 0)-strided gradients
         _lib.check(_lib.load().aladin_heads_small_bwd(_ptr(im), _ld(im), _ptr(s), _ld(s), B, D,
                                                       _ptr(dMh if gh is not None else None), _ptr(gh), 1.0,
                                                       _ptr(dMl if gl is not None else None), _ptr(gl), 1.0, _ptr(gM),
@@ -122,8 +129,7 @@ class _SmallHeads(torch.autograd.Function):
             S, packed = _align_forward(im, s, im_len_t, s_len_t)
         a = b = None
         if flags & (HEAD_MATCH_HINGE | HEAD_LISTNET):
-            a = img_emb if img_emb.stride(1) == 1 else img_emb.contiguous()
-            b = cap_emb if cap_emb.stride(1) == 1 else cap_emb.contiguous()
+            a, b = _small_rows(img_emb), _small_rows(cap_emb)
         align = (im, s, im_len_t, s_len_t, packed) if (packed is not None and need_sets and flags & HEAD_ALIGN_HINGE) else None
         o = _heads_small_fwd(a, b, S, margin, max_violation, flags, temperature, eps, weights, need_sets or need_embs, True, align)
         if o['sets'] is not None:
@@ -181,8 +187,7 @@ class _BigHeads(torch.autograd.Function):
                                               hinge=bool(flags & HEAD_ALIGN_HINGE), loss_out=terms[1:2])
         a = b = M = dMh = dMl = None
         if flags & (HEAD_MATCH_HINGE | HEAD_LISTNET):
-            a = img_emb if img_emb.stride(1) == 1 else img_emb.contiguous()
-            b = cap_emb if cap_emb.stride(1) == 1 else cap_emb.contiguous()
+            a, b = _unit_cols(img_emb), _unit_cols(cap_emb)
             M = torch.empty((B, B), dtype=torch.float32, device=dev)
             _sgemm(B, B, a.shape[1], a, a.stride(0), a.stride(1), b, b.stride(1), b.stride(0), M)
             if flags & HEAD_MATCH_HINGE:
@@ -241,7 +246,9 @@ def small_batch_loss_heads(img_emb, cap_emb, im_set, s_seq, im_len, s_len, margi
     """The loss heads of one training step in a single autograd node (three head launches at B <= SMALL_BATCH_MAX,
     the general kernels above it -- either way no element-wise glue).
     heads: subset of {'matching', 'alignment', 'distillation'}; weights: dict head -> fixed loss weight.
-    -> (total = sum_k w_k L_k  [differentiable], terms (3,) = matching / alignment / distillation values, S, M)."""
+    -> (total = sum_k w_k L_k  [differentiable], terms (3,) = matching / alignment / distillation values, S, M).
+    The slots of `terms` that belong to heads not selected are unspecified (uninitialised above SMALL_BATCH_MAX): read only the
+    selected heads' slots."""
     flags = (HEAD_MATCH_HINGE if 'matching' in heads else 0) | (HEAD_ALIGN_HINGE if 'alignment' in heads else 0) | \
         (HEAD_LISTNET if 'distillation' in heads else 0)
     if not flags:
@@ -254,6 +261,8 @@ def small_batch_loss_heads(img_emb, cap_emb, im_set, s_seq, im_len, s_len, margi
             raise ValueError('aladin_amd: the loss heads need one image set, one caption and one embedding pair per sample')
         if torch.is_grad_enabled() and (im_set.requires_grad or s_seq.requires_grad):
             im_set, s_seq = _pad_features(im_set, s_seq)          # D % 4 != 0: zero features, dropped again by autograd
+        elif not torch.is_grad_enabled():                         # (needs_input_grad follows requires_grad even under no_grad)
+            im_set, s_seq = im_set.detach(), s_seq.detach()
     w = (float(weights.get('matching', 0.0)), float(weights.get('alignment', 0.0)), float(weights.get('distillation', 0.0)))
     # long sets never reach the small-batch kernels (their tile classes stop at 96 scored positions): the general node
     long_sets = im_set is not None and s_seq is not None and flags & (HEAD_ALIGN_HINGE | HEAD_LISTNET) and \
@@ -275,8 +284,7 @@ class _MatchHinge(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, im, s, margin, max_violation):
-        a = im if im.stride(1) == 1 else im.contiguous()
-        b = s if s.stride(1) == 1 else s.contiguous()
+        a, b = _unit_cols(im), _unit_cols(s)
         B = a.shape[0]
         M = torch.empty((B, B), dtype=torch.float32, device=a.device)
         _sgemm(B, B, a.shape[1], a, a.stride(0), a.stride(1), b, b.stride(1), b.stride(0), M)
@@ -334,8 +342,7 @@ class _MatchCrossEntropy(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, im, s, log_t):
-        a = im if im.stride(1) == 1 else im.contiguous()
-        b = s if s.stride(1) == 1 else s.contiguous()
+        a, b = _unit_cols(im), _unit_cols(s)
         B = a.shape[0]
         M = torch.empty((B, B), dtype=torch.float32, device=a.device)
         _sgemm(B, B, a.shape[1], a, a.stride(0), a.stride(1), b, b.stride(1), b.stride(0), M)
