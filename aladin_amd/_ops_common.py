@@ -1,4 +1,5 @@
-"""Helpers shared by the ops modules: device checks, raw pointers, the current stream, length tensors, workspaces.
+"""Helpers shared by the ops modules: device checks, raw pointers, the current stream, length tensors, workspaces, the set
+structs and entry checks of the functions that take image / caption sets.
 Every tensor function of this package requires float32 tensors on an AMD GPU ("cuda" device of PyTorch-ROCm) and raises
 otherwise; there is no CPU or eager-PyTorch fallback."""
 import ctypes as C
@@ -20,6 +21,12 @@ def _stream():
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _require_tensors(*tensors):
+    for t in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('aladin_amd: expected a torch.Tensor, got %r' % type(t))
 
 
 def _require_gpu(*tensors):
@@ -81,3 +88,56 @@ def _require_square(scores, what, hint=''):
 
 def _workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
+def _upstream(g):
+    """The upstream gradient of a scalar loss as the kernels read it through a pointer: one float32 on the device."""
+    return g.to(torch.float32).contiguous()
+
+
+def _set_view(t, len_t):
+    """struct aladin_set of a (B, N, D) tensor with a unit inner stride."""
+    return _lib.SetView(t.data_ptr(), t.stride(0), t.stride(1), len_t.data_ptr())
+
+
+def _grad_view(t):
+    return _lib.GradView(t.data_ptr(), t.stride(0), t.stride(1))
+
+
+def _check_set_shapes(im_set, s_seq, im_len, s_len):
+    _require_gpu(im_set, s_seq)
+    if im_set.dim() != 3 or s_seq.dim() != 3:
+        raise ValueError('aladin_amd: im_set (B,R,D) and s_seq (B,T,D) expected')
+    if len(im_len) != im_set.shape[0] or len(s_len) != s_seq.shape[0]:
+        raise ValueError('aladin_amd: one length per sample expected')
+    if im_set.shape[2] != s_seq.shape[2]:
+        raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (im_set.shape[2], s_seq.shape[2]))
+
+
+def _check_sets(im_set, s_seq, im_len, s_len):
+    """_check_set_shapes -> the lengths as device tensors (im_len_t, s_len_t)"""
+    _check_set_shapes(im_set, s_seq, im_len, s_len)
+    return lengths_tensor(im_len, im_set.device), lengths_tensor(s_len, im_set.device)
+
+
+def _pad_features(im_set, s_seq):
+    """The backward kernels move rows as 16-byte float4 columns (D % 4 == 0).  The reference has no such limit: a set whose
+    feature size is not a multiple of 4 is padded with zero features here, OUTSIDE the autograd nodes -- zeros change neither
+    a norm nor a dot product, and autograd's own backward of the padding drops the extra gradient columns.  One copy of each set,
+    paid by odd feature sizes only (every shipped configuration has D = 768)."""
+    D = im_set.shape[-1]
+    if D % 4 == 0 or im_set.dim() != 3 or s_seq.dim() != 3 or s_seq.shape[-1] != D:
+        return im_set, s_seq
+    pad = 4 - D % 4
+    return torch.nn.functional.pad(im_set, (0, pad)), torch.nn.functional.pad(s_seq, (0, pad))
+
+
+def _sets_for_node(im_set, s_seq):
+    """The sets as a fused loss node takes them: padded (_pad_features) when a gradient can be asked for, detached under
+    torch.no_grad() -- a Function's ctx.needs_input_grad follows requires_grad even there: without this the node would prepare
+    (and, for a feature size that is no multiple of 4, refuse) a backward nobody can ask for."""
+    if not torch.is_grad_enabled():
+        return im_set.detach(), s_seq.detach()
+    if im_set.requires_grad or s_seq.requires_grad:
+        return _pad_features(im_set, s_seq)
+    return im_set, s_seq

@@ -11,7 +11,8 @@ import torch
 
 from . import _lib
 
-from ._ops_common import _RAW_STREAM, _stream, _ptr, _require_gpu, _rows_inner_contig, _LEN_CACHE, lengths_tensor, _ld, _workspace
+from ._ops_common import (_RAW_STREAM, _stream, _ptr, _require_gpu, _rows_inner_contig, _LEN_CACHE, lengths_tensor, _ld, _workspace,
+                          _set_view, _grad_view, _pad_features, _check_set_shapes, _check_sets, _sets_for_node, _upstream)
 from .ops_losses import _DotScores, _hinge_raw        # (the other names of ops_losses / ops_heads / ops_retrieval: __getattr__ below)
 
 
@@ -170,15 +171,6 @@ def is_long(R, T, x_tail=0, y_tail=2):
     return LONG_PATH_FORCE or R - 1 - x_tail > _lib.TILE_MAX_SCORED or T - 1 - y_tail > _lib.TILE_MAX_SCORED
 
 
-def _set_view(t, len_t):
-    """struct aladin_set of a (B, N, D) tensor with a unit inner stride."""
-    return _lib.SetView(t.data_ptr(), t.stride(0), t.stride(1), len_t.data_ptr())
-
-
-def _grad_view(t):
-    return _lib.GradView(t.data_ptr(), t.stride(0), t.stride(1))
-
-
 def pack_images(im, im_len_t, geom, rnorm=None, out=None):
     """(xm, xe): L2-normalised, sliced, length-masked fp16 MFMA operands of the image sets.  rnorm (optional float32 tensor of
     geom.rnorm_bytes / 4 elements): receives the image rows' inverse norms in its [xm | xe] part.  out = (xm, xe): write into
@@ -212,18 +204,6 @@ def scores_from_packed(xm, xe, y, geom, out=None, e_scratch=None, reuse_side=Fal
     _lib.check(lib.aladin_align_scores(C.byref(pk), C.byref(geom), _ptr(e), _ptr(S), S.stride(0), 1 if reuse_side else 0, _stream()),
                'align_scores')
     return S
-
-
-def _pad_features(im_set, s_seq):
-    """The backward kernels move rows as 16-byte float4 columns (D % 4 == 0).  The reference has no such limit: a set whose
-    feature size is not a multiple of 4 is padded with zero features here, OUTSIDE the autograd nodes -- zeros change neither
-    a norm nor a dot product, and autograd's own backward of the padding drops the extra gradient columns.  One copy of each set,
-    paid by odd feature sizes only (every shipped configuration has D = 768)."""
-    D = im_set.shape[-1]
-    if D % 4 == 0 or im_set.dim() != 3 or s_seq.dim() != 3 or s_seq.shape[-1] != D:
-        return im_set, s_seq
-    pad = 4 - D % 4
-    return torch.nn.functional.pad(im_set, (0, pad)), torch.nn.functional.pad(s_seq, (0, pad))
 
 
 def _check_backward_supported(im, s, x_tail, y_tail):
@@ -556,20 +536,9 @@ class _AlignTriplet(torch.autograd.Function):
         if g_loss is None and g_scores is None:
             return None, None, None, None, None, None, None
         im_len_t, s_len_t, *saved = ctx.saved_tensors
-        g = g_loss.to(torch.float32).contiguous() if g_loss is not None else None
+        g = _upstream(g_loss) if g_loss is not None else None
         d_im, d_s = ctx.align.backward(saved, im_len_t, s_len_t, g, g_scores)
         return d_im, d_s, None, None, None, None, None
-
-
-def _check_sets(im_set, s_seq, im_len, s_len):
-    _require_gpu(im_set, s_seq)
-    if im_set.dim() != 3 or s_seq.dim() != 3:
-        raise ValueError('aladin_amd: im_set (B,R,D) and s_seq (B,T,D) expected')
-    if len(im_len) != im_set.shape[0] or len(s_len) != s_seq.shape[0]:
-        raise ValueError('aladin_amd: one length per sample expected')
-    if im_set.shape[2] != s_seq.shape[2]:
-        raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (im_set.shape[2], s_seq.shape[2]))
-    return lengths_tensor(im_len, im_set.device), lengths_tensor(s_len, im_set.device)
 
 
 def alignment_triplet_loss(im_set, s_seq, im_len, s_len, margin, max_violation):
@@ -581,12 +550,7 @@ def alignment_triplet_loss(im_set, s_seq, im_len, s_len, margin, max_violation):
     if im_set.shape[0] != s_seq.shape[0]:
         raise ValueError('aladin_amd: the contrastive loss needs a square score matrix, got (%d, %d) '
                          '(the reference fails in diag/expand_as, alad/loss.py:43-45)' % (im_set.shape[0], s_seq.shape[0]))
-    if torch.is_grad_enabled() and (im_set.requires_grad or s_seq.requires_grad):
-        im_set, s_seq = _pad_features(im_set, s_seq)
-    elif not torch.is_grad_enabled():
-        # a Function's ctx.needs_input_grad follows requires_grad even under torch.no_grad(): without this the node would prepare
-        # (and, for a feature size that is no multiple of 4, refuse) a backward nobody can ask for
-        im_set, s_seq = im_set.detach(), s_seq.detach()
+    im_set, s_seq = _sets_for_node(im_set, s_seq)
     fill = None if max_violation else _caption_fill(s_len, s_seq.shape[1])
     return _AlignTriplet.apply(im_set, s_seq, im_len_t, s_len_t, margin, max_violation, fill)
 
@@ -602,13 +566,7 @@ def alignment_scores(im_set, s_seq, im_len, s_len, aggregation='MrSw', precision
     if aggregation not in ('MrSw', 'MwSr', 'symm'):
         raise NotImplementedError('aladin_amd: aggregation %r' % (aggregation,))
     if not (torch.is_grad_enabled() and (im_set.requires_grad or s_seq.requires_grad)):
-        _require_gpu(im_set, s_seq)
-        if im_set.dim() != 3 or s_seq.dim() != 3:
-            raise ValueError('aladin_amd: im_set (B,R,D) and s_seq (B,T,D) expected')
-        if len(im_len) != im_set.shape[0] or len(s_len) != s_seq.shape[0]:
-            raise ValueError('aladin_amd: one length per sample expected')
-        if im_set.shape[2] != s_seq.shape[2]:
-            raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (im_set.shape[2], s_seq.shape[2]))
+        _check_set_shapes(im_set, s_seq, im_len, s_len)
         prec = precision if precision is not None else _EVAL_PRECISION[0]
         from .eval_grid import TensorSide, _host_lengths, score_grid        # (eval_grid imports this module)
         with torch.no_grad():

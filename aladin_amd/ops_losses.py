@@ -6,20 +6,24 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._ops_common import (_RAW_STREAM, _stream, _ptr, _require_gpu, _rows_inner_contig, _LEN_CACHE, lengths_tensor, _ld, _workspace,
-                          _unit_cols, _require_square)
+from ._ops_common import (_stream, _ptr, _require_gpu, _require_tensors, _require_square, _rows_inner_contig, _ld, _workspace, _unit_cols,
+                          _set_view, _grad_view, _pad_features, _check_sets, _upstream)
+
+
+def _loss_buffers(scores, want_grad, workspace_bytes, loss_out=None):
+    """What a *_fwd_bwd call on a (B, B) score matrix writes: -> (B, loss scalar, its gradient matrix or None, workspace).
+    loss_out: a one-element float32 view the kernel writes the loss into (instead of a fresh scalar)."""
+    B, dev = scores.shape[0], scores.device
+    loss = loss_out if loss_out is not None else torch.empty((), dtype=torch.float32, device=dev)
+    grad = torch.empty((B, B), dtype=torch.float32, device=dev) if want_grad else None
+    return B, loss, grad, _workspace(workspace_bytes(B), dev)
 
 
 def _hinge_raw(scores, margin, max_violation, want_grad, want_pairs=False, loss_out=None):
-    """-> (loss, dS or None, pairs or None); pairs = (int32 list of non-zero i*B+j, int32 count).
-    loss_out: a one-element float32 view the kernel writes the loss into (instead of a fresh scalar)."""
+    """-> (loss, dS or None, pairs or None); pairs = (int32 list of non-zero i*B+j, int32 count); loss_out: see _loss_buffers."""
     lib = _lib.load()
-    B = scores.shape[0]
-    sc = _unit_cols(scores)
-    dev = scores.device
-    loss = loss_out if loss_out is not None else torch.empty((), dtype=torch.float32, device=dev)
-    dS = torch.empty((B, B), dtype=torch.float32, device=dev) if want_grad else None
-    ws = _workspace(lib.aladin_hinge_workspace_bytes(B), dev)
+    sc, dev = _unit_cols(scores), scores.device
+    B, loss, dS, ws = _loss_buffers(scores, want_grad, lib.aladin_hinge_workspace_bytes, loss_out)
     pairs = None
     if want_grad and want_pairs:
         pairs = (torch.empty(B * B, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev))
@@ -29,18 +33,42 @@ def _hinge_raw(scores, margin, max_violation, want_grad, want_pairs=False, loss_
     return loss, dS, pairs
 
 
+def _listnet_raw(teacher, student, temperature, eps, want_grad, loss_out=None):
+    """-> (loss, dM or None), dM the gradient on the student; loss_out: see _loss_buffers."""
+    lib = _lib.load()
+    t, m = _unit_cols(teacher), _unit_cols(student)
+    B, loss, dM, ws = _loss_buffers(student, want_grad, lib.aladin_listnet_workspace_bytes, loss_out)
+    _lib.check(lib.aladin_listnet_fwd_bwd(_ptr(t), _ld(t), _ptr(m), _ld(m), B, float(temperature), float(eps), _ptr(loss), _ptr(dM),
+                                          _ptr(ws), _stream()), 'listnet_fwd_bwd')
+    return loss, dM
+
+
+def _grad_combine(g, w_a, A, w_b=0.0, B=None, out=None, w_scale=0.0, scale=None):
+    """aladin_grad_combine, one launch: out = g * (w_a * A + w_b * B) over out's elements (A, B at least as long; None: not there)
+    and scale = g * w_scale, g the _upstream scalar.  -> out"""
+    _lib.check(_lib.load().aladin_grad_combine(out.numel() if out is not None else 0, _ptr(g), w_a, _ptr(A), w_b, _ptr(B), _ptr(out),
+                                               w_scale, _ptr(scale), _stream()), 'grad_combine')
+    return out
+
+
+def _scaled(saved, g):
+    return saved * g if saved is not None else None
+
+
 # ------------------------------------------------------------------------------------------------
-# hinge / listnet
+# hinge / listnet / distillation modes: ONE *_fwd_bwd call leaves the loss and its gradient for an upstream 1, which goes through
+# save_for_backward (released by backward(); a second backward() without retain_graph raises); backward scales it
 # ------------------------------------------------------------------------------------------------
 class _Hinge(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scores, margin, max_violation):
-        loss, ctx.dS, _ = _hinge_raw(scores, margin, max_violation, ctx.needs_input_grad[0])
+        loss, dS, _ = _hinge_raw(scores, margin, max_violation, ctx.needs_input_grad[0])
+        ctx.save_for_backward(dS)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        return (ctx.dS * g if ctx.dS is not None else None), None, None
+        return _scaled(ctx.saved_tensors[0], g), None, None
 
 
 def hinge_loss(scores, margin, max_violation):
@@ -53,20 +81,13 @@ def hinge_loss(scores, margin, max_violation):
 class _ListNet(torch.autograd.Function):
     @staticmethod
     def forward(ctx, teacher, student, temperature, eps):
-        lib = _lib.load()
-        B = student.shape[0]
-        t, m = _unit_cols(teacher), _unit_cols(student)
-        loss = torch.empty((), dtype=torch.float32, device=student.device)
-        dM = torch.empty((B, B), dtype=torch.float32, device=student.device) if ctx.needs_input_grad[1] else None
-        ws = _workspace(lib.aladin_listnet_workspace_bytes(B), student.device)
-        _lib.check(lib.aladin_listnet_fwd_bwd(_ptr(t), _ld(t), _ptr(m), _ld(m), B, float(temperature),
-                                              float(eps), _ptr(loss), _ptr(dM), _ptr(ws), _stream()), 'listnet_fwd_bwd')
-        ctx.dM = dM
+        loss, dM = _listnet_raw(teacher, student, temperature, eps, ctx.needs_input_grad[1])
+        ctx.save_for_backward(dM)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        return None, (ctx.dM * g if ctx.dM is not None else None), None, None
+        return None, _scaled(ctx.saved_tensors[0], g), None, None
 
 
 def listnet_loss(teacher_scores, student_scores, temperature=6.0, eps=1e-10):
@@ -84,32 +105,28 @@ class _DistillMode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, teacher, student, wb, mode, margin, threshold, stride):
         lib = _lib.load()
-        B = student.shape[0]
         t, m = _unit_cols(teacher), _unit_cols(student)
-        dev = student.device
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        dM = torch.empty((B, B), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
-        ws = _workspace(lib.aladin_distill_workspace_bytes(B), dev)
-        ctx.dwb = None
+        B, loss, dM, ws = _loss_buffers(student, ctx.needs_input_grad[1], lib.aladin_distill_workspace_bytes)
+        mats = (_ptr(t), _ld(t), _ptr(m), _ld(m), B)
+        dwb = None
         if mode == 'mse':
             w = wb.detach().to(torch.float32).contiguous()
-            ctx.dwb = torch.empty(2, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
-            _lib.check(lib.aladin_distill_mse_fwd_bwd(_ptr(t), _ld(t), _ptr(m), _ld(m), B, _ptr(w), _ptr(loss), _ptr(dM),
-                                                      _ptr(ctx.dwb), _ptr(ws), _stream()), 'distill_mse_fwd_bwd')
+            dwb = torch.empty(2, dtype=torch.float32, device=student.device) if ctx.needs_input_grad[2] else None
+            _lib.check(lib.aladin_distill_mse_fwd_bwd(*mats, _ptr(w), _ptr(loss), _ptr(dM), _ptr(dwb), _ptr(ws), _stream()),
+                       'distill_mse_fwd_bwd')
         elif mode == 'contrastive':
-            _lib.check(lib.aladin_distill_contrastive_fwd_bwd(_ptr(t), _ld(t), _ptr(m), _ld(m), B, float(margin), _ptr(loss),
-                                                              _ptr(dM), _ptr(ws), _stream()), 'distill_contrastive_fwd_bwd')
+            _lib.check(lib.aladin_distill_contrastive_fwd_bwd(*mats, float(margin), _ptr(loss), _ptr(dM), _ptr(ws), _stream()),
+                       'distill_contrastive_fwd_bwd')
         else:
-            _lib.check(lib.aladin_distill_ordinal_fwd_bwd(_ptr(t), _ld(t), _ptr(m), _ld(m), B, float(margin),
-                                                          float(threshold), int(stride), _ptr(loss), _ptr(dM), _ptr(ws),
-                                                          _stream()), 'distill_ordinal_fwd_bwd')
-        ctx.dM = dM
+            _lib.check(lib.aladin_distill_ordinal_fwd_bwd(*mats, float(margin), float(threshold), int(stride), _ptr(loss), _ptr(dM),
+                                                          _ptr(ws), _stream()), 'distill_ordinal_fwd_bwd')
+        ctx.save_for_backward(dM, dwb)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        return (None, ctx.dM * g if ctx.dM is not None else None, ctx.dwb * g if ctx.dwb is not None else None,
-                None, None, None, None)
+        dM, dwb = ctx.saved_tensors
+        return None, _scaled(dM, g), _scaled(dwb, g), None, None, None, None
 
 
 def distillation_loss(teacher_scores, student_scores, mode, margin=0.2, threshold=0.1, stride=3, wb=None):
@@ -180,24 +197,35 @@ def _sgemm(M, N, K, A, a_rs, a_cs, B, b_rs, b_cs, out):
     return out
 
 
+def _product(a, b, M=None):
+    """M = a @ b.T, a (Bi, D) and b (Bc, D) read through their strides: M[m][n] = sum_k a[m,k] * b[n,k], into a fresh or the given M."""
+    if M is None:
+        M = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
+    return _sgemm(a.shape[0], b.shape[0], a.shape[1], a, a.stride(0), a.stride(1), b, b.stride(1), b.stride(0), M)
+
+
+def _product_backward(C, a, b, want_a=True, want_b=True):
+    """(d_a, d_b) = (C @ b, C.T @ a) of M = a @ b.T for the gradient C on M; None for a product that is not wanted.  C is made
+    row-major here: autograd hands over (0, 1)- and (0, 0)-strided gradients."""
+    C = C.contiguous()
+    (Bi, D), Bc = a.shape, b.shape[0]
+    d_a = d_b = None
+    if want_a:
+        d_a = _sgemm(Bi, D, Bc, C, C.stride(0), 1, b, b.stride(0), b.stride(1), torch.empty((Bi, D), dtype=torch.float32, device=a.device))
+    if want_b:
+        d_b = _sgemm(Bc, D, Bi, C, 1, C.stride(0), a, a.stride(0), a.stride(1), torch.empty((Bc, D), dtype=torch.float32, device=a.device))
+    return d_a, d_b
+
+
 class _DotScores(torch.autograd.Function):
     @staticmethod
     def forward(ctx, im, s):
         ctx.save_for_backward(im, s)
-        out = torch.empty((im.shape[0], s.shape[0]), dtype=torch.float32, device=im.device)
-        # C[m][n] = sum_k im[m,k] * s[n,k]
-        return _sgemm(im.shape[0], s.shape[0], im.shape[1], im, im.stride(0), im.stride(1), s, s.stride(1), s.stride(0), out)
+        return _product(im, s)
 
     @staticmethod
     def backward(ctx, dM):
-        im, s = ctx.saved_tensors
-        dM = dM.contiguous()
-        Bi, Bc, D = im.shape[0], s.shape[0], im.shape[1]
-        d_im = torch.empty((Bi, D), dtype=torch.float32, device=im.device)
-        d_s = torch.empty((Bc, D), dtype=torch.float32, device=im.device)
-        _sgemm(Bi, D, Bc, dM, dM.stride(0), 1, s, s.stride(0), s.stride(1), d_im)        # dM @ s
-        _sgemm(Bc, D, Bi, dM, 1, dM.stride(0), im, im.stride(0), im.stride(1), d_s)      # dM.T @ im
-        return d_im, d_s
+        return _product_backward(dM, *ctx.saved_tensors)
 
 
 def dot_scores(im, s):
@@ -243,7 +271,7 @@ class _NNEntropy(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_nn, _g_dist):
         a, b, nn, dist = ctx.saved_tensors
-        g = g.to(torch.float32).contiguous()
+        g = _upstream(g)
         d_img, d_cap = torch.empty_like(a, memory_format=torch.contiguous_format), torch.empty_like(b, memory_format=torch.contiguous_format)
         _lib.check(_lib.load().aladin_nn_entropy_bwd(_ptr(a), _ld(a), _ptr(b), _ld(b), a.shape[0], a.shape[1], _ptr(nn), _ptr(dist),
                                                      _ptr(g), _ptr(d_img), _ptr(d_cap), _stream()), 'nn_entropy_bwd')
@@ -306,12 +334,11 @@ def _xent_raw(scores, log_t, want_grad, want_dt):
     return loss, grads
 
 
-def _xent_scale(grads, g, n):
-    """g * grads[:n] in one launch (g: the upstream gradient, a device scalar)"""
-    out = torch.empty(n, dtype=torch.float32, device=grads.device)
-    _lib.check(_lib.load().aladin_grad_combine(n, _ptr(g), 1.0, _ptr(grads), 0.0, _ptr(None), _ptr(out), 0.0, _ptr(None), _stream()),
-               'grad_combine')
-    return out
+def _xent_scale(grads, g, B, want_dt, t_shape):
+    """-> (g * dS as (B, B), g * d log_temperature in t_shape or None) from _xent_raw's buffer, in one launch"""
+    n = B * B
+    out = _grad_combine(_upstream(g), 1.0, grads, out=torch.empty(n + (1 if want_dt else 0), dtype=torch.float32, device=grads.device))
+    return out[:n].view(B, B), (out[n:].view(t_shape) if want_dt else None)
 
 
 class _CrossEntropy(torch.autograd.Function):
@@ -330,9 +357,8 @@ class _CrossEntropy(torch.autograd.Function):
         (grads,) = ctx.saved_tensors
         if grads is None:
             return None, None
-        n = ctx.B * ctx.B
-        out = _xent_scale(grads, g.to(torch.float32).contiguous(), n + (1 if ctx.want_dt else 0))
-        return (out[:n].view(ctx.B, ctx.B) if ctx.needs_input_grad[0] else None), (out[n:].view(ctx.t_shape) if ctx.want_dt else None)
+        dS, d_t = _xent_scale(grads, g, ctx.B, ctx.want_dt, ctx.t_shape)
+        return (dS if ctx.needs_input_grad[0] else None), d_t
 
 
 def cross_entropy_scores(scores, log_temperature):
@@ -340,8 +366,7 @@ def cross_entropy_scores(scores, log_temperature):
     cross_entropy(L, arange) and cross_entropy(L.T, arange) -- what CrossEntropyCriterion (reference alad/loss.py:190-201) computes
     from its logits.  log_temperature: a one-element float32 GPU tensor (it gets a gradient) or a Python float (a constant).
     One autograd node, two launches forward; the backward scales the saved gradients by the upstream one in one launch."""
-    if not isinstance(scores, torch.Tensor):
-        raise TypeError('aladin_amd: expected a torch.Tensor, got %r' % type(scores))
+    _require_tensors(scores)
     _require_square(scores, 'the cross-entropy criterion', ' (the reference fails in F.cross_entropy, alad/loss.py:198-199)')
     _require_gpu(scores)
     _xent_limit(scores.shape[0])
@@ -358,17 +383,13 @@ class _SemanticHinge(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scores, rel, draws, margin, threshold, flags, want_positives):
         lib = _lib.load()
-        B = scores.shape[0]
-        dev = scores.device
         sc = _unit_cols(scores)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        dS = torch.empty((B, B), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        pos = torch.empty(2 * B, dtype=torch.int32, device=dev) if want_positives else None
-        ws = _workspace(lib.aladin_semantic_hinge_workspace_bytes(B), dev)
+        B, loss, dS, ws = _loss_buffers(scores, ctx.needs_input_grad[0], lib.aladin_semantic_hinge_workspace_bytes)
+        pos = torch.empty(2 * B, dtype=torch.int32, device=scores.device) if want_positives else None
         _lib.check(lib.aladin_semantic_hinge_fwd_bwd(_ptr(sc), _ld(sc), _ptr(rel), rel.stride(0), rel.stride(1), B, float(margin),
                                                      float(threshold), int(flags), _ptr(draws), _ptr(loss), _ptr(dS), _ptr(pos),
                                                      _ptr(ws), _stream()), 'semantic_hinge_fwd_bwd')
-        ctx.dS = dS
+        ctx.save_for_backward(dS)
         if pos is None:
             return loss
         ctx.mark_non_differentiable(pos)
@@ -376,7 +397,7 @@ class _SemanticHinge(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, *_):
-        return (ctx.dS * g if ctx.dS is not None else None), None, None, None, None, None, None
+        return _scaled(ctx.saved_tensors[0], g), None, None, None, None, None, None
 
 
 def semantic_hinge_loss(scores, relevances, margin, threshold=0.4, max_violation=False, *, draws=None, generator=None,
@@ -392,9 +413,7 @@ def semantic_hinge_loss(scores, relevances, margin, threshold=0.4, max_violation
     them back in, 'aligned' gives column j its own.  mask_positives (not in the reference): the costs are also cleared wherever
     relevances > threshold.  return_positives: also the int32 (2B,) choice, every row's column then every column's row.
     One autograd node: four launches ('aligned': three), no host synchronisation."""
-    for t in (scores, relevances):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError('aladin_amd: expected a torch.Tensor, got %r' % type(t))
+    _require_tensors(scores, relevances)
     _require_square(scores, 'the semantic contrastive loss')
     if tuple(relevances.shape) != tuple(scores.shape):
         raise ValueError('aladin_amd: relevances of shape %s expected (aligned with the scores), got %s'
@@ -428,7 +447,6 @@ def semantic_hinge_loss(scores, relevances, margin, threshold=0.4, max_violation
 # ------------------------------------------------------------------------------------------------
 def _attdistill_args(im, s, im_len_t, s_len_t, teacher):
     """the argument run aladin_attdistill_fwd / _bwd share (the views must stay alive until the call returned)"""
-    from .ops import _set_view
     sv_im, sv_s = _set_view(im, im_len_t), _set_view(s, s_len_t)
     Bi, R, D = im.shape
     Bc, T, _ = s.shape
@@ -451,9 +469,8 @@ class _AttDistill(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .ops import _grad_view
         im, s, im_len_t, s_len_t, teacher, ws = ctx.saved_tensors
-        g = g.to(torch.float32).contiguous()
+        g = _upstream(g)
         # fresh row-major outputs; the kernels write every row (slot 0 and masked positions as zeros)
         d_im = torch.empty(im.shape, dtype=torch.float32, device=im.device) if ctx.needs_input_grad[0] else None
         d_s = torch.empty(s.shape, dtype=torch.float32, device=s.device) if ctx.needs_input_grad[1] else None
@@ -474,13 +491,7 @@ def attention_distillation_loss(im_set, s_seq, im_len, s_len, teacher):
     place through its strides (the reference's 69 x 70 tensor as it is); it gets no gradient.  One autograd node: three launches
     forward, one per wanted gradient backward; the (Bi, Bc, R - 1, T - 1) logits tensor is never formed.  Masked regions drop
     out of the loss (behavioural notes)."""
-    _require_gpu(im_set, s_seq)
-    if im_set.dim() != 3 or s_seq.dim() != 3:
-        raise ValueError('aladin_amd: im_set (B,R,D) and s_seq (B,T,D) expected')
-    if len(im_len) != im_set.shape[0] or len(s_len) != s_seq.shape[0]:
-        raise ValueError('aladin_amd: one length per sample expected')
-    if im_set.shape[2] != s_seq.shape[2]:
-        raise ValueError('aladin_amd: feature sizes differ (%d vs %d)' % (im_set.shape[2], s_seq.shape[2]))
+    im_len_t, s_len_t = _check_sets(im_set, s_seq, im_len, s_len)
     Bi, R, _ = im_set.shape
     Bc, T, _ = s_seq.shape
     if Bi < 1 or Bc < 1 or R < 2 or T < 2 or im_set.shape[2] < 1:
@@ -497,8 +508,6 @@ def attention_distillation_loss(im_set, s_seq, im_len, s_len, teacher):
     if (teacher.shape[3] > 1 and teacher.stride(3) != 1) or teacher.stride(2) < teacher.shape[3] or min(teacher.stride()) < 0:
         raise ValueError('aladin_amd: the teacher attentions are read in place and need a unit innermost stride and word rows that '
                          'do not overlap (got strides %s for shape %s)' % (tuple(teacher.stride()), tuple(teacher.shape)))
-    from .ops import _pad_features
-    im_len_t, s_len_t = lengths_tensor(im_len, im_set.device), lengths_tensor(s_len, im_set.device)
     im_set, s_seq = _pad_features(im_set, s_seq)
     return _AttDistill.apply(_rows_inner_contig(im_set), _rows_inner_contig(s_seq), im_len_t, s_len_t, teacher.detach())
 

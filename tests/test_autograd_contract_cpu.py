@@ -6,7 +6,10 @@
   * every input layout yields the strides it claims, back() restores the values, overlapping leaves sum;
   * every upstream composite hands a node the gradient stride it is named for (a dummy Function records it);
   * the registry's gpu_calls bind to the signatures of aladin_amd.ops, and the alignment entries run end to end over the CPU
-    stand-ins of tests/helpers/cpu_standins.py."""
+    stand-ins of tests/helpers/cpu_standins.py;
+  * over a library stand-in that records every call: the entry points each autograd node issues, in order, and what the
+    saved-gradient loss nodes keep for their backward, and for how long."""
+import ctypes
 import inspect
 import os
 import sys
@@ -363,9 +366,9 @@ def test_the_other_fused_nodes_hand_over_rows_that_do_not_overlap(node, monkeypa
     def sgemm(M, N, K, A_, a_rs, a_cs, B_, b_rs, b_cs, out):
         gemms.append((a_rs, a_cs, b_rs, b_cs))
         return out
-    monkeypatch.setattr(ops_heads, '_ld', lambda t: lds.append((real_ld(t), t.shape[1])) or lds[-1][0])
-    monkeypatch.setattr(ops_heads, '_sgemm', sgemm)
+    monkeypatch.setattr(ops_losses, '_sgemm', sgemm)           # the product pair of the four nodes lives there
     for mod in (ops_heads, ops_losses):
+        monkeypatch.setattr(mod, '_ld', lambda t: lds.append((real_ld(t), t.shape[1])) or lds[-1][0])
         monkeypatch.setattr(mod, '_stream', lambda: None)
     monkeypatch.setattr(_lib, 'load', lambda: _AnyCall())
     B, D = 5, 64
@@ -394,3 +397,169 @@ def test_the_other_fused_nodes_hand_over_rows_that_do_not_overlap(node, monkeypa
         assert all(ld >= cols for ld, cols in lds), (node, side, lds)
         assert all(0 not in g for g in gemms), (node, side, gemms)
         assert row.grad is not None and row.grad.shape == (1, D)
+
+
+# ------------------------------------------------------------------------------------------------
+# which entry points a node calls, in which order; what the saved-gradient nodes keep, and for how long
+# ------------------------------------------------------------------------------------------------
+class _RecordingLib:
+    """stands for the loaded library: the host-only functions (the geometry, every workspace size) go to the real one, every other
+    entry point is recorded with its arguments and reports success"""
+
+    def __init__(self, real):
+        self.real, self.calls = real, []
+
+    def __getattr__(self, name):
+        if name == 'aladin_align_geometry' or name.endswith('_workspace_bytes'):
+            return getattr(self.real, name)
+        return lambda *a: self.calls.append((name[len('aladin_'):], a)) or 0
+
+    def names(self):
+        return [n for n, _ in self.calls]
+
+    def null_pointers(self):
+        return sum(isinstance(v, ctypes.c_void_p) and not v.value for _, a in self.calls for v in a)
+
+
+@pytest.fixture
+def recording_lib(monkeypatch):
+    from aladin_amd import _lib, ops, ops_heads, ops_losses
+    lib = _RecordingLib(_lib.load())
+    for mod in (ops, ops_heads, ops_losses):
+        monkeypatch.setattr(mod, '_stream', lambda: None)
+    monkeypatch.setattr(_lib, 'load', lambda: lib)
+    return lib
+
+
+def _node_inputs(B, seed=5):
+    rng = np.random.default_rng(seed)
+    new = lambda *shape: torch.from_numpy(rng.standard_normal(shape).astype(np.float32))
+    leaf = lambda *shape: new(*shape).requires_grad_(True)
+    full = lambda n: torch.full((B,), n, dtype=torch.int32)
+    return new, leaf, full(6), full(8)
+
+
+def _sequence_cases():
+    """name -> (B, run(new, leaf, il, sl) -> the scalar to back-propagate, the expected calls): the table of the parent commit"""
+    from aladin_amd import ops, ops_heads as OH, ops_losses as OL
+    gemm, W = 'sgemm_strided', (1.0, 1.0, 1.0)
+    embs = lambda leaf, B: (leaf(B, 16), leaf(B, 16))
+    sets = lambda leaf, B: (leaf(B, 6, 8), leaf(B, 8, 8))
+    both = lambda out: out[0] + out[1].sum()
+    cases = {
+        '_Hinge': (5, lambda new, leaf, il, sl: OL._Hinge.apply(leaf(5, 5), 0.2, True), ['hinge_fused']),
+        '_ListNet': (5, lambda new, leaf, il, sl: OL._ListNet.apply(new(5, 5), leaf(5, 5), 6.0, 1e-10), ['listnet_fwd_bwd']),
+        '_SemanticHinge': (5, lambda new, leaf, il, sl: OL._SemanticHinge.apply(
+            leaf(5, 5), new(5, 5), torch.zeros(10, dtype=torch.int32), 0.2, 0.4, 0, False), ['semantic_hinge_fwd_bwd']),
+        '_CrossEntropy': (5, lambda new, leaf, il, sl: OL._CrossEntropy.apply(leaf(5, 5), leaf(1)), ['xent_fwd_bwd', 'grad_combine']),
+        '_DotScores': (5, lambda new, leaf, il, sl: OL._DotScores.apply(*embs(leaf, 5)).sum(), [gemm] * 3),
+        '_SmallMatchDistill': (5, lambda new, leaf, il, sl: (lambda o: o[0] + o[1] + o[2].sum())(
+            OH._SmallMatchDistill.apply(*embs(leaf, 5), new(5, 5), 0.2, True, True, 6.0, 1e-10)), ['heads_small_fwd', 'heads_small_bwd']),
+        '_AlignScores': (5, lambda new, leaf, il, sl: ops._AlignScores.apply(*sets(leaf, 5), il, sl, 0, 2).sum(),
+                         ['align_pack', 'align_scores', 'align_bwd']),
+        '_AttDistill': (5, lambda new, leaf, il, sl: OL._AttDistill.apply(*sets(leaf, 5), il, sl, new(5, 5, 7, 5)),
+                        ['attdistill_fwd', 'attdistill_bwd']),
+        '_SmallHeads[7]': (5, lambda new, leaf, il, sl: OH._SmallHeads.apply(*embs(leaf, 5), *sets(leaf, 5), il, sl, 0.2, True, 7, W, 6.0, 1e-10)[0],
+                           ['align_pack', 'align_scores', 'heads_small_fwd_argmax', 'heads_small_bwd', 'align_triplet_bwd']),
+        '_SmallHeads[7,sum]': (5, lambda new, leaf, il, sl: OH._SmallHeads.apply(*embs(leaf, 5), *sets(leaf, 5), il, sl, 0.2, False, 7, W, 6.0, 1e-10)[0],
+                               ['align_pack', 'align_scores', 'heads_small_fwd', 'heads_small_bwd', 'align_bwd']),
+        '_SmallHeads[1]': (5, lambda new, leaf, il, sl: OH._SmallHeads.apply(*embs(leaf, 5), None, None, None, None, 0.2, True, 1, W, 6.0, 1e-10)[0],
+                           ['heads_small_fwd', 'heads_small_bwd']),
+        '_BigHeads[7]': (65, lambda new, leaf, il, sl: OH._BigHeads.apply(*embs(leaf, 65), *sets(leaf, 65), il, sl, 0.2, True, 7, W, 6.0, 1e-10, None)[0],
+                         ['align_triplet_fwd', gemm, 'hinge_fused', 'listnet_fwd_bwd', 'loss_total', 'grad_combine', gemm, gemm, 'align_triplet_bwd']),
+        '_BigHeads[1]': (65, lambda new, leaf, il, sl: OH._BigHeads.apply(*embs(leaf, 65), None, None, None, None, 0.2, True, 1, W, 6.0, 1e-10, None)[0],
+                         [gemm, 'hinge_fused', 'loss_total', 'grad_combine', gemm, gemm]),
+    }
+    for mode in ('mse', 'contrastive', 'ordinal'):
+        cases['_DistillMode[%s]' % mode] = (5, lambda new, leaf, il, sl, mode=mode: OL._DistillMode.apply(
+            new(5, 5), leaf(5, 5), leaf(2), mode, 0.2, 0.1, 3), ['distill_%s_fwd_bwd' % mode])
+    for B in (5, 65):
+        cases['_MatchHinge[%d]' % B] = (B, lambda new, leaf, il, sl, B=B: both(OH._MatchHinge.apply(*embs(leaf, B), 0.2, True)),
+                                        [gemm, 'hinge_fused', 'grad_combine', gemm, gemm])
+        cases['_MatchCrossEntropy[%d]' % B] = (B, lambda new, leaf, il, sl, B=B: both(OH._MatchCrossEntropy.apply(*embs(leaf, B), leaf(1))),
+                                               [gemm, 'xent_fwd_bwd', 'grad_combine', gemm, gemm])
+        cases['_AlignTriplet[%d]' % B] = (B, lambda new, leaf, il, sl, B=B: ops._AlignTriplet.apply(*sets(leaf, B), il, sl, 0.2, True, None)[0],
+                                          ['align_triplet_fwd', 'align_triplet_bwd'])
+    return cases
+
+
+SEQUENCE_NODES = ['_Hinge', '_ListNet', '_DistillMode[mse]', '_DistillMode[contrastive]', '_DistillMode[ordinal]', '_SemanticHinge',
+                  '_CrossEntropy', '_DotScores', '_SmallMatchDistill', '_MatchHinge[5]', '_MatchHinge[65]', '_MatchCrossEntropy[5]',
+                  '_MatchCrossEntropy[65]', '_SmallHeads[7]', '_SmallHeads[7,sum]', '_SmallHeads[1]', '_BigHeads[7]', '_BigHeads[1]',
+                  '_AlignTriplet[5]', '_AlignTriplet[65]', '_AlignScores', '_AttDistill']
+
+
+@pytest.mark.parametrize('name', SEQUENCE_NODES)
+def test_every_node_issues_the_entry_points_of_its_row_in_order(name, recording_lib):
+    """forward, then backward() of the loss (plus M.sum() where M is differentiable), on CPU tensors over the recording library:
+    embeddings (B, 16), sets (B, 6, 8) and (B, 8, 8) at full lengths, hardest-negative hinge, weights (1, 1, 1); B = 65 is the first
+    batch past SMALL_BATCH_MAX.  (The sum of violations at B = 65 asks the density probe about stream capture: the GPU tests' path.)"""
+    cases = _sequence_cases()
+    assert sorted(cases) == sorted(SEQUENCE_NODES)
+    B, run, want = cases[name]
+    new, leaf, il, sl = _node_inputs(B)
+    run(new, leaf, il, sl).backward()
+    assert recording_lib.names() == want, (name, recording_lib.names())
+
+
+def _saved_gradient_cases():
+    """name -> (apply(inputs) -> loss, the differentiable inputs' positions among the node's arguments)"""
+    from aladin_amd import ops_losses as OL
+    draws = torch.zeros(6, dtype=torch.int32)
+    cases = {'_Hinge': (OL._Hinge, lambda x: (x['scores'], 0.2, True), ['scores']),
+             '_ListNet': (OL._ListNet, lambda x: (x['teacher'], x['student'], 6.0, 1e-10), ['student']),
+             '_SemanticHinge': (OL._SemanticHinge, lambda x: (x['scores'], x['teacher'], draws, 0.2, 0.4, 0, False), ['scores'])}
+    for mode in ('mse', 'contrastive', 'ordinal'):
+        cases['_DistillMode[%s]' % mode] = (OL._DistillMode, lambda x, mode=mode: (x['teacher'], x['student'], x['wb'], mode, 0.2, 0.1, 1),
+                                            ['student', 'wb'] if mode == 'mse' else ['student'])
+    return cases
+
+
+@pytest.mark.parametrize('name', ['_Hinge', '_ListNet', '_DistillMode[mse]', '_DistillMode[contrastive]', '_DistillMode[ordinal]',
+                                  '_SemanticHinge'])
+def test_saved_gradient_nodes_keep_their_matrices_until_the_graph_is_released(name, recording_lib):
+    """the loss nodes whose forward leaves the gradient for an upstream 1: the matrices travel through save_for_backward, so two
+    retained backwards accumulate exactly twice the single gradient, a further backward() succeeds and releases them, the one after
+    that raises; an input that takes no gradient gets no buffer (one more null pointer reaches the kernel) and None from backward."""
+    node, args, diff = _saved_gradient_cases()[name]
+    B = 3
+    rng = np.random.default_rng(11)
+    new = lambda *shape: torch.from_numpy(rng.standard_normal(shape).astype(np.float32))
+
+    def inputs(requires):
+        x = {'scores': new(B, B), 'teacher': new(B, B), 'student': new(B, B), 'wb': new(2)}
+        for n in requires:
+            x[n].requires_grad_(True)
+        return x
+
+    x = inputs(diff)
+    loss = node.apply(*args(x))
+    nulls_all = recording_lib.null_pointers()
+    saved = [t for t in loss.grad_fn.saved_tensors if t is not None]          # (the mse mode's dwb slot is empty in the other modes)
+    assert [tuple(t.shape) for t in saved] == [tuple(x[n].shape) for n in diff] and all(t.dtype == torch.float32 for t in saved)
+    assert not any(isinstance(v, torch.Tensor) for v in vars(loss.grad_fn).values()), 'a gradient kept as a plain attribute of ctx'
+    for t in saved:                                  # the recording library wrote nothing: give the saved gradients values
+        t.data.copy_(new(*t.shape))
+    single = [t.clone() for t in saved]
+    loss.backward(retain_graph=True)
+    assert all(torch.equal(x[n].grad, g) for n, g in zip(diff, single))
+    loss.backward(retain_graph=True)
+    assert all(torch.equal(x[n].grad, 2 * g) for n, g in zip(diff, single))
+    loss.backward()
+    assert all(torch.equal(x[n].grad, 3 * g) for n, g in zip(diff, single))
+    with pytest.raises(RuntimeError):
+        loss.backward()
+    # one input at a time without a gradient: no buffer for it, None from backward
+    for off in diff:
+        del recording_lib.calls[:]
+        on = [n for n in diff if n != off]
+        x = inputs(on)
+        loss = node.apply(*args(x))
+        assert recording_lib.null_pointers() == nulls_all + 1, (name, off)
+        if not on:
+            assert loss.grad_fn is None and not loss.requires_grad
+            continue
+        assert [t is None for t in loss.grad_fn.saved_tensors[:len(diff)]] == [n == off for n in diff]
+        out = node.backward(loss.grad_fn, torch.ones(()))
+        for i, v in enumerate(args(x)):
+            assert (out[i] is not None) == (isinstance(v, torch.Tensor) and v.requires_grad), (name, off, i)

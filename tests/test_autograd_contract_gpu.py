@@ -11,6 +11,7 @@ time away from the base case (contiguous leaves, one call, (M * W).sum() or L):
 The alignment entries run under both backward precisions, as the existing gradient tests do.  No tolerance is introduced here.
 tests/test_autograd_contract_cpu.py pins the references, the layouts and the composites."""
 import contextlib
+import gc
 import os
 import sys
 
@@ -363,6 +364,53 @@ def test_h_dense_table_backward_of_a_generic_gradient(bwd_mode):
     d_im, d_s = O.alignment_scores_backward(im, s, il, sl, np.ones((B, B)))
     assert_grads_close(a.grad, d_im, bwd_mode)
     assert_grads_close(b.grad, d_s, bwd_mode)
+
+
+def _square_float_tensors_held_by(node, B, skip):
+    """the (B, B) float32 tensors reachable from an autograd node: its Python attributes (and what they hold) and, while the graph
+    is alive, its saved tensors"""
+    found, seen, todo = [], set(), [node]
+    while todo:
+        obj = todo.pop()
+        if id(obj) in seen:
+            continue
+        seen.add(id(obj))
+        if isinstance(obj, torch.Tensor):
+            if tuple(obj.shape) == (B, B) and obj.dtype == torch.float32 and obj.data_ptr() not in skip:
+                found.append(obj)
+        elif not isinstance(obj, (type, type(gc))):
+            todo.extend(gc.get_referents(obj))
+    try:
+        found += [t for t in node.saved_tensors if t is not None and tuple(t.shape) == (B, B) and t.data_ptr() not in skip]
+    except RuntimeError:          # released: "Trying to backward through the graph a second time ..."
+        pass
+    return found
+
+
+@pytest.mark.parametrize('B', [3, 65])
+@pytest.mark.parametrize('loss_fn', ['hinge_loss', 'listnet_loss'])
+def test_i_saved_gradient_nodes_accumulate_exactly_and_release_their_matrix(loss_fn, B):
+    """the nodes whose forward leaves the gradient for an upstream 1, on the real kernels: two retained backwards give exactly twice
+    the single gradient, and after a plain backward() no (B, B) float32 tensor is reachable from the node any more (the saved
+    tensors are the only holders of the gradient matrix)"""
+    from aladin_amd import ops
+    rng = np.random.default_rng(B)
+    to = AC.to_device(dev(), torch.float32)
+    scores = to(rng.standard_normal((B, B)).astype(np.float32)).requires_grad_(True)
+    teacher = to(rng.standard_normal((B, B)).astype(np.float32))
+    loss = ops.hinge_loss(scores, 0.2, True) if loss_fn == 'hinge_loss' else ops.listnet_loss(teacher, scores)
+    skip = {scores.data_ptr(), teacher.data_ptr()}
+    assert len(_square_float_tensors_held_by(loss.grad_fn, B, skip)) == 1
+    loss.backward(retain_graph=True)
+    single = scores.grad.clone()
+    assert bool(single.any())
+    loss.backward(retain_graph=True)
+    assert torch.equal(scores.grad, 2 * single)
+    assert len(_square_float_tensors_held_by(loss.grad_fn, B, skip | {scores.grad.data_ptr(), single.data_ptr()})) == 1
+    loss.backward()
+    torch.cuda.synchronize()
+    assert torch.equal(scores.grad, 3 * single)
+    assert _square_float_tensors_held_by(loss.grad_fn, B, skip | {scores.grad.data_ptr(), single.data_ptr()}) == []
 
 
 from test_long_sets_gpu import bwd_mode          # noqa: E402,F401  (the fixture of the existing gradient tests)
